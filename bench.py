@@ -12,8 +12,14 @@ coarse_gray_depth=8, GLCM angles {0,45,90,135}, offset 1, matlab binning.
 Per rank (one process per GPU): the same number of tiles (weak scaling), no collective in
 the timed region; the one exchange of a job -- the gather of the final feature table to
 rank 0 (RCCL) -- runs once after the timed steps and is reported as `table_gather`.
-Output: ONE JSON line on rank 0 (contract in the task statement) plus `roofline` and
-`cpu_baseline` objects.
+Output: ONE JSON line on rank 0 (metric, value, unit, higher_is_better, dtype, ms_per_step) with a `roofline`
+object; `--full` adds `cpu_baseline`, the legs and `summary`.
+
+A plain run (`--gpus 1 --steps K --warmup W`) sets up, warms up, times the K steps, writes the last step's table if
+`--dump-outputs DIR` is given, and prints the line.  `--full` adds everything else the line used to carry: the parity gate
+of the headline, the CPU baselines, the informational legs (grey depth 64, BASELINE.json configs[1]-[4], ROI sizes,
+intensity ranges, the fused tile path and its PCIe-inclusive variants) and the `summary`; `--no-check`, `--no-cpu-baseline`,
+`--no-extras` and `--tile-path-tiles` shape that run.
 
 Launching: `python bench.py --gpus N` with N > 1 and no WORLD_SIZE in the environment makes
 this process a launcher: it never touches the GPU, starts N child ranks of this same script
@@ -38,6 +44,8 @@ HBM_PEAK_GBS = 8000.0  # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E peak 8.0 
 FP64_PEAK_TF = 78.6    # AMD Instinct MI355X data sheet: peak fp64 vector = fp64 matrix, 78.6 TFLOP/s (the guide has no fp64 row)
 FP32_PEAK_TF = 157.3   # /opt/skills/guides/MI355X_MICROARCH.md: peak FP32 (vector) 157.3 TFLOPS
 F16_MFMA_PEAK_TF = 2500.0   # same guide: BF16 / F16 MFMA ~2.5 PFLOP/s dense
+DUMP_BUDGET = 60_000_000    # bytes of --dump-outputs (under 64 MB with the .npy header)
+DUMP_SEED = 0               # row sample of --dump-outputs: the same rows for the same --tiles / --families / --gray-depth
 
 
 def gabor_roofline(alg_flops, dt, bbox_w, bbox_h, max_inten, n_filters):
@@ -70,7 +78,18 @@ def parse():
     ap.add_argument("--stub", action="store_true",
                     help="TEST HOOK (tests/test_bench_launcher.py): no GPU, gloo; every rank fills a rank-coded table on the CPU so that "
                          "the launcher, the barrier / max-over-ranks timing and the table gather can run here; the line says \"stub\": true")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run its parity gate, the CPU baselines and the informational legs (the flags above "
+                         "shape them); off: only what the headline needs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write rank 0's table of the last step as DIR/features.npy (float64; a fixed, seeded "
+                         f"sample of rows when the whole table exceeds {DUMP_BUDGET // 1000000} MB)")
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if a.warmup < 0:
+        ap.error("--warmup must be at least 0")
+    return a
 
 
 def under_profiler() -> bool:
@@ -359,6 +378,18 @@ class Bench:
         ctx.sync()                               # raises on a device-side error flag
         self.kern_ms, self.n_launch = e0.elapsed_time(e1) / max(a.steps, 1), a.steps
         self.last, self.t_steps = last, t1 - t0
+
+    def dump_outputs(self, d):
+        """--dump-outputs: the table the last timed step returned (float64, n_roi x n_columns) as d/features.npy -- every row
+        while it fits DUMP_BUDGET, else a sorted sample of rows drawn with DUMP_SEED (the same rows for the same arguments)."""
+        n, row_bytes = self.n_roi, self.ncol * 8
+        k = min(n, DUMP_BUDGET // row_bytes)
+        idx = np.arange(n) if k == n else np.sort(np.random.default_rng(DUMP_SEED).choice(n, k, replace=False))
+        rows = self.last[self.torch.from_numpy(idx).to(self.dev)].cpu().numpy()
+        os.makedirs(d, exist_ok=True)
+        np.save(os.path.join(d, "features.npy"), np.ascontiguousarray(rows, dtype=np.float64))
+        print(f"bench.py: wrote {d}/features.npy: {k} of {n} rows x {self.ncol} columns"
+              + ("" if k == n else f" (rows sampled with seed {DUMP_SEED})"), file=sys.stderr)
 
     def ranks_and_gather(self):
         """Per-rank detail for the one line the driver keeps (which physical device each rank ran on -- two ranks on one device would
@@ -959,24 +990,28 @@ def main():
     b = Bench(a, world, rank, local_rank)
     b.make_batch()
     b.timed_steps()
+    if a.dump_outputs and rank == 0:
+        b.dump_outputs(a.dump_outputs)
     b.ranks_and_gather()
     gate_rc = 0
     if rank == 0:
         b.headline()
-        if not a.no_check:
-            b.headline_gate()
-        if world == 1 and not a.no_cpu_baseline:
-            b.headline_cpu_baseline()
-        # ---- informational legs on the same resident batch: the reference's DEFAULT grey depth, BASELINE.json configs[1]-[4], ROI sizes ----
-        if world == 1 and not a.no_extras and b.mask == 3:
-            b.legs_configs()
-            b.leg_gabor_metric()
-            b.leg_config5()
-            b.legs_sizes()
-        if world == 1 and a.tile_path_tiles > 0:
-            b.leg_tile_path()
+        if a.full:
+            if not a.no_check:
+                b.headline_gate()
+            if world == 1 and not a.no_cpu_baseline:
+                b.headline_cpu_baseline()
+            # ---- informational legs on the same resident batch: the reference's DEFAULT grey depth, BASELINE.json configs[1]-[4], ROI sizes ----
+            if world == 1 and not a.no_extras and b.mask == 3:
+                b.legs_configs()
+                b.leg_gabor_metric()
+                b.leg_config5()
+                b.legs_sizes()
+            if world == 1 and a.tile_path_tiles > 0:
+                b.leg_tile_path()
         gate_rc = apply_gates(b.rec)         # a leg whose features do not match loses its value; exit code 4 below
-        b.summary()
+        if a.full:
+            b.summary()
         print(json.dumps(b.rec))
     if world > 1:
         torch, dist = b.torch, b.dist

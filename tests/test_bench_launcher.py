@@ -39,6 +39,14 @@ def test_single_rank_needs_no_launcher():
     assert rec["n_gpus"] == 1 and rec["rows"] == 12 and rec["row_order_ok"]
 
 
+def test_steps_sets_the_timed_steps_and_must_be_positive():
+    rec = _run(["--gpus", "1", "--steps", "7", "--warmup", "0", "--tiles", "2", "--stub"])
+    assert rec["steps"] == 7 and rec["warmup"] == 0 and rec["ms_per_step"] >= 0
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "0", "--stub"],
+                       capture_output=True, text=True, timeout=120)
+    assert p.returncode == 2 and "--steps must be at least 1" in p.stderr
+
+
 def test_launcher_reports_a_failing_rank():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK")}
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--stub", "--tiles", "-7"], env=env,

@@ -196,7 +196,7 @@ def test_two_gpus_bench_and_sharded_api_agree_with_one():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
-    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--tiles", "16", "--steps", "2", "--warmup", "1", "--no-extras",
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--full", "--tiles", "16", "--steps", "2", "--warmup", "1", "--no-extras",
                         "--tile-path-tiles", "0", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]
     rec = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][0])

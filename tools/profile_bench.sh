@@ -6,7 +6,7 @@ TAG=${1:-r01}; shift || true
 export TMPDIR=/tmp
 OUT=$PWD/gpurun_out/prof_$TAG
 mkdir -p $OUT
-ARGS="--steps 5 --warmup 2 --no-cpu-baseline --no-check $*"
+ARGS="--full --steps 5 --warmup 2 --no-cpu-baseline --no-check $*"
 cd $PWD
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 bench.py $ARGS > $OUT/bench_trace.log 2>&1
 # PMC passes, each alone (no trace domains combined with --pmc)

@@ -3,7 +3,7 @@
 export TMPDIR=/tmp
 for lib in "" $PWD/gpurun_scratch/libscan_*.so; do
   OUT=$PWD/gpurun_out/scan_ab; rm -rf $OUT; mkdir -p $OUT
-  NYXHIP_LIB=$lib rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-check --no-extras --tile-path-tiles 1000 > $OUT/log.txt 2>&1
+  NYXHIP_LIB=$lib rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -- python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-check --no-extras --tile-path-tiles 1000 > $OUT/log.txt 2>&1
   python3 - <<PY
 import csv,glob,json
 name="$(basename "${lib:-default}")"

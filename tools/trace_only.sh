@@ -3,7 +3,7 @@
 export TMPDIR=/tmp
 TAG=$1; shift
 OUT=$PWD/gpurun_out/trace_$TAG; rm -rf $OUT; mkdir -p $OUT
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-check "$@" > $OUT/bench.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-check "$@" > $OUT/bench.log 2>&1
 python3 - <<PY
 import csv,glob
 for f in glob.glob("$OUT/trace/**/*kernel_stats.csv", recursive=True):
