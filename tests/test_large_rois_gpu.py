@@ -11,7 +11,7 @@ import pytest
 
 from nyxus_amd import _abi, _lib
 from oracle import pyoracle as po
-from tests import parity
+from tests import counts, parity
 from tests.test_size_classes_gpu import ellipse_roi
 
 pytestmark = pytest.mark.gpu
@@ -44,7 +44,8 @@ def check(ctx, rois, mask, s, expect_coop=True):
     b = _abi.batch_from_rois(rois)
     G = ctx.featurize_host(b, mask, s)
     O = po.oracle_featurize(b, mask, s)
-    bad = parity.compare_tables(G, O, _lib.column_names(mask, s), batch=b)
+    names = _lib.column_names(mask, s)
+    bad = parity.compare_tables(G, O, names, batch=b) + counts.compare_counts(G, O, names) + counts.compare_tight(G, O, names)
     assert not bad, "\n".join(bad[:20])
     rep = ctx.launch_report()
     if expect_coop:

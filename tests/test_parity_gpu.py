@@ -8,7 +8,7 @@ import pytest
 
 from nyxus_amd import _abi, _lib
 from oracle import pyoracle as po
-from tests import fixtures, parity, synth
+from tests import counts, fixtures, parity, synth
 
 pytestmark = pytest.mark.gpu
 
@@ -16,15 +16,20 @@ MASK = _abi.FAM_INTENSITY | _abi.FAM_GLCM
 CONFIGS = [(8, False, 4), (64, False, 4), (-16, False, 4), (100, False, 2), (20, True, 4), (24, False, 1)]
 
 
+def _with_counts(G, O, names, **kw):
+    """compare_tables, and for the texture families the integer counts (tests/counts.py) and NGTDM at its tight bound."""
+    return parity.compare_tables(G, O, names, **kw) + counts.compare_counts(G, O, names) + counts.compare_tight(G, O, names)
+
+
 def _check(ctx, b, mask, s, against_ref=True):
     names = _lib.column_names(mask, s)
     G = ctx.featurize_host(b, mask, s)
     O = po.oracle_featurize(b, mask, s)
-    bad = parity.compare_tables(G, O, names, batch=b)
+    bad = _with_counts(G, O, names, batch=b)
     assert not bad, "\n".join(bad[:20])
     if against_ref and po.have_ref():
         R = po.ref_featurize(b, mask, s, n_threads=2)
-        bad = parity.compare_tables(G, R, names, batch=b)
+        bad = _with_counts(G, R, names, batch=b)
         assert not bad, "vs reference classes:\n" + "\n".join(bad[:20])
     return G
 
@@ -189,7 +194,7 @@ def test_rois_beyond_lds_use_global_workspace(hip_ctx, gd):
     b = _abi.batch_from_rois(rois)
     G = hip_ctx.featurize_host(b, mask, s)
     O = po.oracle_featurize(b, mask, s)
-    assert not parity.compare_tables(G, O, _lib.column_names(mask, s), batch=b)
+    assert not _with_counts(G, O, _lib.column_names(mask, s), batch=b)
 
 
 def test_large_roi_gabor_is_exact(hip_ctx):
@@ -588,7 +593,7 @@ def test_texture_families_alone_on_spilled_rois(hip_ctx, fam, gd):
     s = _abi.default_settings(gd)
     G = hip_ctx.featurize_host(b, fam, s)
     O = po.oracle_featurize(b, fam, s)
-    assert not parity.compare_tables(G, O, _lib.column_names(fam, s))
+    assert not _with_counts(G, O, _lib.column_names(fam, s))
 
 
 @pytest.mark.parametrize("gd", [17, 20, 32, 48, -8, -24])
@@ -636,9 +641,9 @@ def test_texture_row_scans_at_edge_widths(hip_ctx, gd):
     s = _abi.default_settings(gd)
     G = hip_ctx.featurize_host(b, TEX, s)
     O = po.oracle_featurize(b, TEX, s)
-    assert not parity.compare_tables(G, O, _lib.column_names(TEX, s))
+    assert not _with_counts(G, O, _lib.column_names(TEX, s))
     if po.have_ref():
-        assert not parity.compare_tables(G, po.ref_featurize(b, TEX, s, 2), _lib.column_names(TEX, s))
+        assert not _with_counts(G, po.ref_featurize(b, TEX, s, 2), _lib.column_names(TEX, s))
 
 
 @pytest.mark.parametrize("gd", [3, 8, 40])
@@ -664,10 +669,10 @@ def test_texture_families_on_workspace_rois_wider_than_four_chunks(hip_ctx, gd):
     s = _abi.default_settings(gd)
     G = hip_ctx.featurize_host(b, TEX, s)
     assert any(r["workspace"] for r in hip_ctx.launch_report())
-    assert not parity.compare_tables(G, po.oracle_featurize(b, TEX, s), _lib.column_names(TEX, s))
+    assert not _with_counts(G, po.oracle_featurize(b, TEX, s), _lib.column_names(TEX, s))
     for fam in (_abi.FAM_GLRLM, _abi.FAM_NGTDM):                 # alone: other LDS offsets of the hybrid state
         G1 = hip_ctx.featurize_host(b, fam, s)
-        assert not parity.compare_tables(G1, po.oracle_featurize(b, fam, s), _lib.column_names(fam, s))
+        assert not _with_counts(G1, po.oracle_featurize(b, fam, s), _lib.column_names(fam, s))
 
 
 @pytest.mark.parametrize("gd", [3, 8])
@@ -704,12 +709,12 @@ def test_texture_row_scans_on_boxes_wider_than_a_wave(hip_ctx, gd):
     s = _abi.default_settings(gd)
     G = hip_ctx.featurize_host(b, TEX, s)
     O = po.oracle_featurize(b, TEX, s)
-    assert not parity.compare_tables(G, O, _lib.column_names(TEX, s))
+    assert not _with_counts(G, O, _lib.column_names(TEX, s))
     if po.have_ref():
-        assert not parity.compare_tables(G, po.ref_featurize(b, TEX, s, 2), _lib.column_names(TEX, s))
+        assert not _with_counts(G, po.ref_featurize(b, TEX, s, 2), _lib.column_names(TEX, s))
     for fam in (_abi.FAM_GLSZM, _abi.FAM_GLRLM, _abi.FAM_NGTDM):  # each family alone (its own launch layout)
         G1 = hip_ctx.featurize_host(b, fam, s)
-        assert not parity.compare_tables(G1, po.oracle_featurize(b, fam, s), _lib.column_names(fam, s))
+        assert not _with_counts(G1, po.oracle_featurize(b, fam, s), _lib.column_names(fam, s))
 
 
 @pytest.mark.parametrize("gd", [8, 16, 64])
@@ -819,7 +824,7 @@ def test_dependence_tails_parallel_equals_sequential(hip_ctx, gd, monkeypatch):
     assert np.array_equal(par.view(np.uint64), seq.view(np.uint64))
     monkeypatch.delenv("NYXHIP_DEP_SEQ")
     O = po.oracle_featurize(b, DEP_ALL, s)
-    bad = parity.compare_tables(par, O, _lib.column_names(DEP_ALL, s))
+    bad = _with_counts(par, O, _lib.column_names(DEP_ALL, s))
     assert not bad, "\n".join(bad[:20])
 
 

@@ -5,6 +5,7 @@ import numpy as np
 sys.path.insert(0, ".")
 from nyxus_amd import _abi, _lib
 from oracle import pyoracle as po
+from oracle import counts
 from tests import parity
 
 ctx = _lib.Context(0)
@@ -69,7 +70,7 @@ for rnd in range(rounds):
         continue
     O = po.oracle_featurize(b, mask, s)
     names = _lib.column_names(mask, s)
-    bad = parity.compare_tables(G, O, names, atol=parity.moment_atol(b))
+    bad = parity.compare_tables(G, O, names, atol=parity.moment_atol(b)) + counts.compare_counts(G, O, names) + counts.compare_tight(G, O, names)
     # ill-conditioned weighted-moment rows (w00 cancels) are reported separately
     hard = [x for x in bad if not any(t in x for t in ("WNCM", "WHU", "WT_NORM", "WEIGHTED_HU", "IMOM_WCM", "WEIGHTED_CENTRAL"))]
     total_bad += len(hard)

@@ -9,6 +9,7 @@ import numpy as np
 sys.path.insert(0, ".")
 from nyxus_amd import _abi, _lib
 from oracle import pyoracle as po
+from oracle import counts
 from tests import parity
 
 
@@ -79,7 +80,8 @@ def run(ctx, seed=0, rounds=20, seconds=600, verbose=True):
         #  column scale offers no floor -- differences below 1e-18 absolute are not findings)
         with np.errstate(invalid="ignore"):
             G = np.where(np.abs(G - O) < 1e-18, O, G)
-        bad = parity.compare_tables(G, O, _lib.column_names(mask, s), batch=b)
+        names = _lib.column_names(mask, s)
+        bad = parity.compare_tables(G, O, names, batch=b) + counts.compare_counts(G, O, names) + counts.compare_tight(G, O, names)
         coop = any(r["cooperative"] & 2 for r in ctx.launch_report())
         if verbose:
             print("round", rnd, "mask", mask, "gd", gd, "ibsi", ibsi, "hi", hi, "boxes", [(int(r["x"].max()) + 1, int(r["y"].max()) + 1) for r in rois], "coop", coop,

@@ -7,6 +7,7 @@ import numpy as np
 sys.path.insert(0, ".")
 from nyxus_amd import _abi, _lib
 from oracle import pyoracle as po
+from oracle import counts
 from tests import parity
 
 SOFT = ("WNCM", "WHU", "WT_NORM", "WEIGHTED_HU", "IMOM_WCM", "WEIGHTED_CENTRAL")
@@ -75,7 +76,8 @@ def run(ctx, seed=0, rounds=30, seconds=420, verbose=True):
             print_("round", rnd, "mask", mask, "gd", gd, "ibsi", ibsi, "-> error", str(e)[:100], flush=True)
             continue
         O = po.oracle_featurize(b, mask, s)
-        bad = parity.compare_tables(G, O, _lib.column_names(mask, s), atol=parity.moment_atol(b))
+        names = _lib.column_names(mask, s)
+        bad = parity.compare_tables(G, O, names, atol=parity.moment_atol(b)) + counts.compare_counts(G, O, names) + counts.compare_tight(G, O, names)
         hard = [x for x in bad if not any(t in x for t in SOFT)]
         total_hard += len(hard)
         print_("round", rnd, "mask", mask, "gd", gd, "ibsi", ibsi, "rois", len(rois), "big", big, "wide", wide, "hard", len(hard), hard[:2], flush=True)
