@@ -1,0 +1,224 @@
+// nyxhip_ctx.h -- what the host units of the library share (internal): the context behind include/nyxhip.h, the owner types of its
+// device and pinned memory, error reporting, and the functions the units call in each other.
+//   nyxhip_columns.hip   column catalogue, settings checks, defaults
+//   nyxhip_dispatch.hip  layouts, argument blocks, size classes: a device-resident batch -> kernel launches
+//   nyxhip_tiles.hip     the fused tile path and its host staging
+//   nyxhip_api.hip       context life cycle, the batch entry points, timing, launch report
+#pragma once
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+#include <unistd.h>
+#include <string>
+#include <vector>
+#include <algorithm>
+#include <atomic>
+#include <utility>
+
+#include "../../include/nyxhip.h"
+#include "roi_kernel.h"
+
+// One hipMalloc allocation, grow-only.  hipFree waits for the device's work by itself; the stream handed to reserve() states which
+// work the site knows to be using the old block.
+struct DevBuf {
+    void* p = nullptr;
+    size_t bytes = 0;                  // capacity
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    DevBuf(DevBuf&& o) noexcept : p(o.p), bytes(o.bytes) { o.p = nullptr; o.bytes = 0; }
+    DevBuf& operator=(DevBuf&& o) noexcept
+    {
+        if (this != &o) { release(); p = o.p; bytes = o.bytes; o.p = nullptr; o.bytes = 0; }
+        return *this;
+    }
+    ~DevBuf() { release(); }
+    template <class T> T* as() const { return (T*)p; }
+    explicit operator bool() const { return p != nullptr; }
+    void release()
+    {
+        if (p) (void)hipFree(p);
+        p = nullptr; bytes = 0;
+    }
+    // Ensure capacity >= need.  When it must grow: synchronise `sync` (if non-null), free, allocate `want` bytes (want >= need;
+    // default want == need).  On failure the buffer is empty (null, 0 bytes) and the hipError_t is returned.
+    hipError_t reserve(size_t need, hipStream_t sync, size_t want = 0)
+    {
+        if (need <= bytes) return hipSuccess;
+        hipError_t e = (p && sync) ? hipStreamSynchronize(sync) : hipSuccess;
+        release();
+        if (e == hipSuccess) e = hipMalloc(&p, std::max(want, need));
+        if (e != hipSuccess) { p = nullptr; return e; }
+        bytes = std::max(want, need);
+        return hipSuccess;
+    }
+};
+
+// One page-locked host block and the event of the last copy out of it: complete (both) or empty (neither).
+struct PinnedSlot {
+    void* p = nullptr;
+    hipEvent_t done = nullptr;
+    bool used = false;                 // `done` has been recorded
+    PinnedSlot() = default;
+    PinnedSlot(const PinnedSlot&) = delete;
+    PinnedSlot& operator=(const PinnedSlot&) = delete;
+    ~PinnedSlot()
+    {
+        if (done) (void)hipEventDestroy(done);
+        if (p) (void)hipHostFree(p);
+    }
+    hipError_t ensure(size_t bytes)
+    {
+        if (p) return hipSuccess;
+        if (hipError_t e = hipEventCreateWithFlags(&done, hipEventDisableTiming); e != hipSuccess) { done = nullptr; return e; }
+        if (hipError_t e = hipHostMalloc(&p, bytes, hipHostMallocDefault); e != hipSuccess) {
+            (void)hipEventDestroy(done);
+            p = nullptr; done = nullptr;
+            return e;
+        }
+        return hipSuccess;
+    }
+};
+
+struct Extrema {
+    uint32_t px, area, range, side;
+    uint32_t vmax = 0;           // largest intensity (0: not known -- stated extrema carry none)
+    bool wide_only = false;      // every ROI of the group has an intensity range beyond the counting tables (a wide-range size class)
+};
+struct ClassRun {              // one size class of one call, as launched (nyxhip_launch_report)
+    int cls;                   // 2 * size class + (1: some ROI needs 32-bit tables); -1: the whole batch in one launch group
+    uint32_t count;            // members (0xFFFFFFFF: counted on the device only)
+    Extrema E;                 // extrema the carve-outs were sized for
+    int workspace;             // kernel groups that ran from a global workspace instead of LDS: bit 0 INTENSITY + GLCM, 1 texture, 2 shape, 3 dependence
+    hipEvent_t e0, e1;         // around the class's launches on the main stream (timing enabled), else NULL
+    hipEvent_t e2 = nullptr;   // ... and the end of its launches on its workspace lane
+    int cooperative = 0;       // bit 0: INTENSITY + GLCM by the several-workgroups-per-ROI kernels of roi_large.hip, bit 1: the texture families (roi_large_tex.hip)
+};
+struct ClassTotals {           // sums over the members of a class (class header): what the large-ROI path sizes its workspace from
+    uint64_t px, area, range1; // pixels, bounding-box cells, histogram entries (range + 1 of the members whose range the path serves)
+};
+constexpr int NYXHIP_INTERNAL_NEEDS_CLOUDS = -1000;   // run_class: a launch group of a window-mode call needs the materialised clouds
+
+struct nyxhip_ctx {
+    int device = 0;
+    hipStream_t own_stream = nullptr;
+    hipStream_t user_stream = nullptr;
+    bool use_user_stream = false;
+    DevBuf d_status;                   // int: [0] error flag of the kernels | [1] census: ROIs of <= 256 px met by the scanning form of roi_small_kernel (read with the flag)
+    // census of the recent calls: how many of the ROIs were of the smallest size class.  A batch on stated extrema that mixes that class
+    // with the next one runs either as two filtered whole-batch launches (nothing counted, no host round trip: right when the class is
+    // rare -- the metric configuration) or through the exact class lists (right when it is common: filtered launches spend a workgroup
+    // on every slot they skip).  Both give the same rows; the census only picks the cheaper one.  Host batches are counted on the host.
+    uint64_t census_small = 0, census_total = 0, census_pending = 0;
+    // Gabor filter bank (host-built, gabor.cpp:393-449), re-uploaded when the settings change
+    DevBuf d_bank;                   // doubles
+    DevBuf d_bank32;                 // the bank rounded to fp32 (Gabor screening pass)
+    DevBuf d_bank16;                 // 16 x 16 banks: the band-pass filters as f16 B operands of the MFMA screening stage (ShapeArgs::gabor_bank16)
+    std::vector<double> bank_key;
+    uint32_t bank_zero_rows[NYXHIP_MAX_GABOR_FILTERS + 1] = {};   // ShapeArgs::gabor_zero_rows of the uploaded bank (16 x 16 kernels)
+    uint32_t bank_lp_sep = 0;          // ShapeArgs::gabor_lp_sep / _B / _C of the uploaded bank
+    float bank_lp_B[16] = {}, bank_lp_C[44] = {};
+    uint32_t bank_box_mask = 0;                                  // ShapeArgs::gabor_box_mask of the uploaded bank
+    DevBuf d_stamps;                   // diagnostic (NYXHIP_STAMPS=1 + -DNYX_STAMP build): [32] phase cycle sums
+    std::string err;
+    // grow-only device staging for host-memory batches
+    DevBuf d_stage;
+    // split GLCM: exported co-occurrence counts + matrix orders (grow-only)
+    DevBuf d_glcm_ws;
+    DevBuf d_glcm_ng;                // [n_roi] matrix order of every ROI whose counts were exported in the CURRENT call (0: none) -- cleared per call
+    DevBuf d_logtab;                 // moments: log(sqrt(d) + 0.001) per integer squared distance (roi_moments.hip)
+    uint32_t logtab_n = 0;
+    // contour + moments workspace (grow-only): contour points, contour lengths, per-pixel log distances
+    DevBuf d_mom;
+    // contour planes beyond LDS: index list (launch_moments); per-workgroup global scratch of every workspace launch
+    DevBuf d_spill_list;
+    DevBuf d_spill;
+    // grow-only workspaces of the fused tile path: scan tables + rows | clouds | two staging slots for host tiles
+    DevBuf d_tile;
+    DevBuf d_cloud;
+    DevBuf d_slot[2];
+    hipStream_t copy_stream = nullptr;         // H2D of the next chunk runs beside the kernels of the current one
+    hipEvent_t slot_ready[2] = {nullptr, nullptr}, slot_free[2] = {nullptr, nullptr};
+    // pinned staging ring of the host tile path (staged_h2d of nyxhip_tiles.hip): the library's own page-locked memory between a pageable
+    // caller and the DMA engine
+    static constexpr int kStageSlots = 4;
+    static constexpr size_t kStageSlotBytes = (size_t)32 << 20;
+    PinnedSlot h_stage[kStageSlots];
+    int h_stage_next = 0;
+    nyxhip::WindowSrc win_next = {};                   // set by the tile path for its next launch_device call: read ROIs from their tile windows
+    uint32_t tile_cap_hint = 0;                // per-tile table size that served the last call
+    // result kept for nyxhip_fetch_result() (host-memory calls with out_table == NULL): device-resident, grow-only
+    //   [res_cap x res_cols] doubles | [res_cap] labels | [res_cap] tile indices
+    DevBuf d_res;
+    size_t res_cap = 0, res_rows = 0, res_cols = 0;
+    double* res_table() const { return d_res.as<double>(); }
+    uint32_t* res_label() const { return (uint32_t*)(d_res.as<char>() + (((size_t)res_cap * res_cols * 8 + 255) & ~(size_t)255)); }
+    uint32_t* res_tile() const { return res_label() + res_cap; }
+    // size classes of a call (launch_device_all): ROI indices grouped by class, class headers on the device and their pinned host copy
+    DevBuf d_cls_list;
+    DevBuf d_cls_hdr;
+    PinnedSlot h_cls_hdr;               // (its event is not used)
+    std::vector<ClassRun> runs;         // the classes of the last call as launched (nyxhip_launch_report)
+    // large-ROI path (roi_large.hip): per-ROI blocks of histogram / plane / matrices, and the work maps + offsets + counters
+    // Workspace lanes: the one-workgroup-per-ROI launches of a large class are a chain of dependent passes per ROI (milliseconds)
+    // by a few hundred workgroups at most -- a fraction of the chip.  Each large class runs them on a stream of its own beside the
+    // main stream (which goes on with the several-workgroups-per-ROI kernels and the LDS classes), with scratch of its own; the
+    // lanes are forked from the main stream at the start of a call and joined into it at its end.
+    static constexpr int kLanes = 12;              // 0-3: the large classes; 4-6: the LDS size classes of an exact call (run_class);
+                                                   // 8, 10: contour + moments of a batch with boxes beyond LDS (the bulk | the big boxes);
+                                                   // 9: the dependence trio of a large class; 11: Gabor of size class 2 beside the smaller classes
+    static constexpr int kMomLane = 8, kDepLane = 9, kMomLaneBig = 10, kGaborLane = 11;
+    hipStream_t lane_stream[kLanes] = {};
+    hipEvent_t lane_done[kLanes] = {};
+    hipEvent_t lane_fork = nullptr;
+    DevBuf lane_buf[kLanes];
+    bool lane_used[kLanes] = {};
+    // ... and of the texture families (roi_large_tex.hip): one pair per lane (+ one for the main stream), the lanes run side by side
+    DevBuf ltex_buf[kLanes + 1];
+    DevBuf ltex_aux[kLanes + 1];
+    DevBuf d_large;
+    DevBuf d_large_aux;
+    // timing
+    int timing = 0;            // 0 off | 1 two events around every call (nyxhip_timing_get) | 2 also two events around every launch group (nyxhip_launch_report's ms)
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev;
+    size_t ev_used = 0;
+    hipStream_t stream() const { return use_user_stream ? user_stream : own_stream; }
+};
+
+// families the kernels cover so far
+constexpr uint32_t kTexture = NYXHIP_FAM_GLRLM | NYXHIP_FAM_GLSZM | NYXHIP_FAM_NGTDM;
+constexpr uint32_t kShape = NYXHIP_FAM_GABOR | NYXHIP_FAM_ZERNIKE;
+constexpr uint32_t kDependence = NYXHIP_FAM_GLDZM | NYXHIP_FAM_GLDM | NYXHIP_FAM_NGLDM;
+constexpr uint32_t kMoments = NYXHIP_FAM_SMOMS | NYXHIP_FAM_IMOMS;
+constexpr uint32_t kImplemented = NYXHIP_FAM_INTENSITY | NYXHIP_FAM_GLCM | kTexture | kShape | kDependence | kMoments;
+
+namespace nyxhip __attribute__((visibility("hidden"))) {
+
+extern std::atomic<int> g_ctx_on_device[64];          // live contexts per device (default memory budgets are shared among them)
+
+int fail(nyxhip_ctx* ctx, int code, const std::string& msg);   // records msg (ctx == NULL: for nyxhip_last_error(NULL)), returns code
+
+#define HIP_TRY(ctx, call)                                                                    \
+    do {                                                                                      \
+        hipError_t e__ = (call);                                                              \
+        if (e__ != hipSuccess)                                                                \
+            return fail(ctx, NYXHIP_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e__)); \
+    } while (0)
+
+// nyxhip_columns.hip
+bool settings_ok(const nyxhip_settings* s, uint32_t mask, std::string& why);
+// nyxhip_dispatch.hip
+uint32_t pow2ceil(uint32_t v);
+int make_layout(uint32_t mask, const nyxhip_settings* s, int n_cols, uint32_t max_px, uint32_t max_area, uint32_t max_range, LdsLayout& L,
+                std::string& why, size_t cap = 0, uint32_t vmax = 0, bool wide_only = false);
+int ensure_stage(nyxhip_ctx* ctx, size_t bytes);
+int check_status(nyxhip_ctx* ctx);
+int launch_add_offset(const uint32_t* in, uint32_t add, uint32_t n, uint32_t* out, hipStream_t st);   // out[i] = in[i] + add
+void clear_runs(nyxhip_ctx* ctx);
+int launch_device(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t mask, const nyxhip_settings* s, double* d_out, size_t ld, uint32_t max_px,
+                  uint32_t max_area, uint32_t max_range, uint32_t max_side, bool hinted = true);
+int validate(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t mask, const nyxhip_settings* s, double* out, size_t ld);
+
+} // namespace nyxhip

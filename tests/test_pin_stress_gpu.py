@@ -1,4 +1,4 @@
-"""Stress test of the host side of the tile path (nyxhip_api.hip: staged_h2d / HostPin).
+"""Stress test of the host side of the tile path (nyxhip_tiles.hip: staged_h2d / HostPin).
 
 Rounds 3-5 registered the caller's arrays (hipHostRegister) whenever /proc/self/maps made them look like mappings of their own;
 pages of malloc arenas registered and released left the driver in a state in which a LATER copy faulted on the GPU ("Memory access

@@ -1,4 +1,4 @@
-"""GPU tests of the size-class launches (nyxhip_api.hip: launch_device_all / run_class).
+"""GPU tests of the size-class launches (nyxhip_dispatch.hip: launch_device_all / run_class).
 
 The reference has no coupling between the ROIs of a batch -- every worker thread takes ROIs of any size
 (/root/reference/src/nyx/parallel.h:23-42, roi_cache.h:31-84).  Here a launch is sized by its largest ROI, so a call is split into
@@ -249,7 +249,7 @@ def test_smallest_class_matches_oracle(hip_ctx, mask, gd, hi):
     G = hip_ctx.featurize_host(b, mask, s)
     O = po.oracle_featurize(b, mask, s)
     bad = parity.compare_tables(G, O, _lib.column_names(mask, s), batch=b)
-    assert not bad, "\\n".join(bad[:20])
+    assert not bad, "\n".join(bad[:20])
 
 
 @pytest.mark.parametrize("gd", [8, 64])
@@ -275,11 +275,11 @@ def test_smallest_class_rows_do_not_depend_on_companions_or_options(hip_ctx, gd)
             keep = [i for i, nme in enumerate(names) if nme in _lib.column_names(3, s)]
             assert np.array_equal(T[idx][:, keep].view(np.uint64), alone.view(np.uint64))
             bad = parity.compare_tables(T, po.oracle_featurize(bm, m, s), names, batch=bm)
-            assert not bad, "\\n".join(bad[:10])
+            assert not bad, "\n".join(bad[:10])
     for sym, angles, offset in ((1, (0, 45, 90, 135), 1), (0, (45, 135), 1), (1, (135, 0, 90), 1), (1, (90,), 2), (0, (0, 45, 90, 135), 3)):
         s2 = _abi.default_settings(gd)
         s2.glcm_symmetric = sym; s2.glcm_offset = offset; s2.glcm_n_angles = len(angles)
         for i, a in enumerate(angles): s2.glcm_angles[i] = a
         b = _abi.batch_from_rois(small)
         bad = parity.compare_tables(hip_ctx.featurize_host(b, 3, s2), po.oracle_featurize(b, 3, s2), _lib.column_names(3, s2), batch=b)
-        assert not bad, "\\n".join(bad[:10])
+        assert not bad, "\n".join(bad[:10])
