@@ -61,6 +61,10 @@ enum {
     NYXHIP_FAM_NGLDM     = 1u << 9, /* NGLDMfeature, 19 columns (features/ngldm.h:17-38)  */
     NYXHIP_FAM_SMOMS     = 1u << 10, /* Smoms2D_feature, 90 columns: shape moments (features/2d_geomoments.h:247-340)      */
     NYXHIP_FAM_IMOMS     = 1u << 11, /* Imoms2D_feature, 90 columns: intensity moments (features/2d_geomoments.h:99-193)   */
+    /* the rest of the "low-frequency intensity distribution" block (featureset.h:352-357).  Not part of NYXHIP_FAM_ALL:
+     * that constant keeps the twelve families it named before this one existed; OR this bit in explicitly.
+     * Bit 12 stays unassigned: a mask that holds it is NYXHIP_ERR_INVALID_ARG, as it has always been. */
+    NYXHIP_FAM_RADIAL    = 1u << 13, /* RadialDistributionFeature, 3 x 8 columns: FRAC_AT_D, MEAN_FRAC, RADIAL_CV (features/radial_distribution.h) */
     NYXHIP_FAM_NORTH_STAR = 0x7Fu,  /* the seven families of BASELINE.json's north_star */
     NYXHIP_FAM_ALL       = 0xFFFu
 };
@@ -111,7 +115,12 @@ void nyxhip_default_settings(nyxhip_settings* s);
  * bounding-box origin (LR::aabb), so they fit uint16 for every in-RAM
  * ("trivial") ROI.  Pixel order inside an ROI is the scan order of the caller
  * (column-major for the in-memory API, phase2_2d.cpp:655-656); no kernel
- * result depends on it beyond floating-point summation order.
+ * result depends on it beyond floating-point summation order -- with one
+ * exception, NYXHIP_FAM_RADIAL: its centre pixel is the FIRST pixel, in this
+ * order, that attains the minimum of max_sqdist - min_sqdist to the contour
+ * (Pixel2::find_center, features/pixel.cpp:155 compares with a strict `<`), so
+ * a row of that family depends on the pixel order through this tie-break,
+ * exactly as in the reference.
  *
  * `memory` says where ALL pointers of the struct live. */
 enum { NYXHIP_MEM_HOST = 0, NYXHIP_MEM_DEVICE = 1,

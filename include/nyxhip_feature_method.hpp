@@ -61,7 +61,7 @@ enum class Feature2D : int {
     NGLDM_LDE, NGLDM_HDE, NGLDM_LGLCE, NGLDM_HGLCE, NGLDM_LDLGLE, NGLDM_LDHGLE, NGLDM_HDLGLE, NGLDM_HDHGLE, NGLDM_GLNU,
     NGLDM_GLNUN, NGLDM_DCNU, NGLDM_DCNUN, NGLDM_DCP, NGLDM_GLM, NGLDM_GLV, NGLDM_DCM, NGLDM_DCV, NGLDM_DCENT, NGLDM_DCENE,
     NGTDM_COARSENESS, NGTDM_CONTRAST, NGTDM_BUSYNESS, NGTDM_COMPLEXITY, NGTDM_STRENGTH,
-    GABOR, ZERNIKE2D,
+    FRAC_AT_D, GABOR, MEAN_FRAC, RADIAL_CV, ZERNIKE2D,      // featureset.h:352-357: the radial distribution interleaves with Gabor
     // shape / intensity geometric moments (featureset.h:362-565)
     SPAT_MOMENT_00, SPAT_MOMENT_01, SPAT_MOMENT_02, SPAT_MOMENT_03, SPAT_MOMENT_10, SPAT_MOMENT_11, SPAT_MOMENT_12,
     SPAT_MOMENT_13, SPAT_MOMENT_20, SPAT_MOMENT_21, SPAT_MOMENT_22, SPAT_MOMENT_23, SPAT_MOMENT_30, CENTRAL_MOMENT_00,
@@ -252,7 +252,9 @@ inline void reduce_range(uint32_t mask, size_t start, size_t end, std::vector<in
         if (mask & NYXHIP_FAM_GLDM) put(Feature2D::GLDM_SDE, Feature2D::GLDM_LDHGLE, 1);
         if (mask & NYXHIP_FAM_NGLDM) put(Feature2D::NGLDM_LDE, Feature2D::NGLDM_DCENE, 1);
         if (mask & NYXHIP_FAM_NGTDM) put(Feature2D::NGTDM_COARSENESS, Feature2D::NGTDM_STRENGTH, 1);
+        if (mask & NYXHIP_FAM_RADIAL) put(Feature2D::FRAC_AT_D, Feature2D::FRAC_AT_D, 8);
         if (mask & NYXHIP_FAM_GABOR) put(Feature2D::GABOR, Feature2D::GABOR, s.gabor_n_filters);
+        if (mask & NYXHIP_FAM_RADIAL) put(Feature2D::MEAN_FRAC, Feature2D::RADIAL_CV, 8);
         if (mask & NYXHIP_FAM_ZERNIKE) put(Feature2D::ZERNIKE2D, Feature2D::ZERNIKE2D, 30);
         if (mask & NYXHIP_FAM_SMOMS) put(Feature2D::SPAT_MOMENT_00, Feature2D::WEIGHTED_HU_M7, 1);
         if (mask & NYXHIP_FAM_IMOMS) put(Feature2D::IMOM_RM_00, Feature2D::IMOM_WHU7, 1);
@@ -320,6 +322,31 @@ NYXHIP_FAMILY_CLASS(ZernikeFeature, NYXHIP_FAM_ZERNIKE, ZERNIKE2D, ZERNIKE2D)
 NYXHIP_FAMILY_CLASS(Smoms2D_feature, NYXHIP_FAM_SMOMS, SPAT_MOMENT_00, WEIGHTED_HU_M7)
 NYXHIP_FAMILY_CLASS(Imoms2D_feature, NYXHIP_FAM_IMOMS, IMOM_RM_00, IMOM_WHU7)
 
+// RadialDistributionFeature (features/radial_distribution.h): its three codes are not contiguous in the enum (GABOR sits
+// between FRAC_AT_D and MEAN_FRAC), so the class is spelled out.  The contour it depends on is built inside the call.
+class RadialDistributionFeature : public FeatureMethod {
+public:
+    const static int num_bins = 8, num_features_FracAtD = 8, num_features_MeanFrac = 8, num_features_RadialCV = 8;
+    RadialDistributionFeature() : FeatureMethod("RadialDistributionFeature")
+    {
+        provide_features(Feature2D::FRAC_AT_D, Feature2D::FRAC_AT_D);
+        provide_features(Feature2D::MEAN_FRAC, Feature2D::RADIAL_CV);
+    }
+    static bool required(const FeatureSet& fs) { return fs.anyEnabled({Feature2D::FRAC_AT_D, Feature2D::MEAN_FRAC, Feature2D::RADIAL_CV}); }
+    void calculate(LR& r, const Fsettings& s) override { run_single(NYXHIP_FAM_RADIAL, r, s, Dataset()); }
+    void calculate(LR& r, const Fsettings& s, const Dataset& ds) { run_single(NYXHIP_FAM_RADIAL, r, s, ds); }
+    void save_value(std::vector<std::vector<double>>& fv) override
+    {
+        save_range(fv, Feature2D::FRAC_AT_D, Feature2D::FRAC_AT_D);
+        save_range(fv, Feature2D::MEAN_FRAC, Feature2D::RADIAL_CV);
+    }
+    static void extract(LR& r, const Fsettings& s, const Dataset& ds = Dataset()) { RadialDistributionFeature f; f.calculate(r, s, ds); f.save_value(r.fvals); }
+    static void reduce(size_t start, size_t end, std::vector<int>* labels, std::unordered_map<int, LR>* roiData, const Fsettings& s,
+                       const Dataset& ds) { reduce_range(NYXHIP_FAM_RADIAL, start, end, labels, roiData, s, ds); }
+    static void parallel_process_1_batch(size_t start, size_t end, std::vector<int>* labels, std::unordered_map<int, LR>* roiData,
+                                         const Fsettings& s, const Dataset& ds) { reduce_range(NYXHIP_FAM_RADIAL, start, end, labels, roiData, s, ds); }
+};
+
 // runParallel (parallel.h:23-42): the GPU batch is the parallel unit, so the slices run back to back on the
 // caller's thread -- same observable contract (every label of [0, datasetSize) reduced on return).
 typedef void (*functype)(size_t, size_t, std::vector<int>*, std::unordered_map<int, LR>*, const Fsettings&, const Dataset&);
@@ -343,6 +370,7 @@ inline void reduce_trivial_rois_manual(std::vector<int>& PendingRoisLabels, std:
     if (NGLDMfeature::required(fs)) mask |= NYXHIP_FAM_NGLDM;   // :239-244
     if (NGTDMFeature::required(fs)) mask |= NYXHIP_FAM_NGTDM;
     if (GaborFeature::required(fs)) mask |= NYXHIP_FAM_GABOR;
+    if (RadialDistributionFeature::required(fs)) mask |= NYXHIP_FAM_RADIAL;   // reduce_trivial_rois.cpp (RadialDistributionFeature)
     if (ZernikeFeature::required(fs)) mask |= NYXHIP_FAM_ZERNIKE;
     if (Smoms2D_feature::required(fs)) mask |= NYXHIP_FAM_SMOMS;   // reduce_trivial_rois.cpp:326-331
     if (Imoms2D_feature::required(fs)) mask |= NYXHIP_FAM_IMOMS;   // :320-325

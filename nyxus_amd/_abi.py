@@ -28,6 +28,7 @@ FAM_GLDM = 1 << 8
 FAM_NGLDM = 1 << 9
 FAM_SMOMS = 1 << 10
 FAM_IMOMS = 1 << 11
+FAM_RADIAL = 1 << 13          # (bit 12 stays unassigned) RadialDistributionFeature (FRAC_AT_D, MEAN_FRAC, RADIAL_CV); not part of FAM_ALL
 FAM_NORTH_STAR = 0x7F
 FAM_ALL = 0xFFF
 

@@ -111,8 +111,15 @@ std::vector<std::string> column_names(uint32_t mask, const nyxhip_settings* s)
         for (auto n : kNgldmNames) v.push_back(n);
     if (mask & NYXHIP_FAM_NGTDM)
         for (auto n : kNgtdmNames) v.push_back(n);
+    // FRAC_AT_D, GABOR, MEAN_FRAC, RADIAL_CV, ZERNIKE2D: the enum interleaves the radial distribution with Gabor (featureset.h:352-357)
+    if (mask & NYXHIP_FAM_RADIAL)
+        for (int i = 0; i < kRadialBins; i++) v.push_back("FRAC_AT_D_" + std::to_string(i));          // output_2_buffer.cpp:374-383
     if (mask & NYXHIP_FAM_GABOR)
         for (int i = 0; i < s->gabor_n_filters; i++) v.push_back("GABOR_" + std::to_string(i));       // output_2_buffer.cpp:364-373
+    if (mask & NYXHIP_FAM_RADIAL) {
+        for (int i = 0; i < kRadialBins; i++) v.push_back("MEAN_FRAC_" + std::to_string(i));          // :385-397
+        for (int i = 0; i < kRadialBins; i++) v.push_back("RADIAL_CV_" + std::to_string(i));          // :399-411
+    }
     if (mask & NYXHIP_FAM_ZERNIKE)
         for (int i = 0; i < kZernikeCols; i++) v.push_back("ZERNIKE2D_Z" + std::to_string(i));        // :417-427
     if (mask & NYXHIP_FAM_SMOMS) {     // featureset.h:362-467
@@ -186,6 +193,7 @@ int nyxhip_n_columns(uint32_t family_mask, const nyxhip_settings* s)
     if (family_mask & NYXHIP_FAM_ZERNIKE) n += kZernikeCols;
     if (family_mask & NYXHIP_FAM_SMOMS) n += kMomCols;
     if (family_mask & NYXHIP_FAM_IMOMS) n += kMomCols;
+    if (family_mask & NYXHIP_FAM_RADIAL) n += kRadialCols;
     return n;
 }
 

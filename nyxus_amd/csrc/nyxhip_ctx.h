@@ -19,6 +19,7 @@
 
 #include "../../include/nyxhip.h"
 #include "roi_kernel.h"
+#include "roi_radial.h"
 
 // One hipMalloc allocation, grow-only.  hipFree waits for the device's work by itself; the stream handed to reserve() states which
 // work the site knows to be using the old block.
@@ -132,7 +133,7 @@ struct nyxhip_ctx {
     uint32_t logtab_n = 0;
     // contour + moments workspace (grow-only): contour points, contour lengths, per-pixel log distances
     DevBuf d_mom;
-    // contour planes beyond LDS: index list (launch_moments); per-workgroup global scratch of every workspace launch
+    // contour planes beyond LDS: index list (launch_contour_families); per-workgroup global scratch of every workspace launch
     DevBuf d_spill_list;
     DevBuf d_spill;
     // grow-only workspaces of the fused tile path: scan tables + rows | clouds | two staging slots for host tiles
@@ -192,7 +193,8 @@ constexpr uint32_t kTexture = NYXHIP_FAM_GLRLM | NYXHIP_FAM_GLSZM | NYXHIP_FAM_N
 constexpr uint32_t kShape = NYXHIP_FAM_GABOR | NYXHIP_FAM_ZERNIKE;
 constexpr uint32_t kDependence = NYXHIP_FAM_GLDZM | NYXHIP_FAM_GLDM | NYXHIP_FAM_NGLDM;
 constexpr uint32_t kMoments = NYXHIP_FAM_SMOMS | NYXHIP_FAM_IMOMS;
-constexpr uint32_t kImplemented = NYXHIP_FAM_INTENSITY | NYXHIP_FAM_GLCM | kTexture | kShape | kDependence | kMoments;
+constexpr uint32_t kContourFams = kMoments | NYXHIP_FAM_RADIAL;   // families that read the ROI's ordered contour (launch_contour_families)
+constexpr uint32_t kImplemented = NYXHIP_FAM_INTENSITY | NYXHIP_FAM_GLCM | kTexture | kShape | kDependence | kMoments | NYXHIP_FAM_RADIAL;
 
 namespace nyxhip __attribute__((visibility("hidden"))) {
 

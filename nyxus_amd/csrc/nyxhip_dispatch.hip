@@ -403,8 +403,9 @@ int build_args(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t mask, const nyxh
         g.bbox_w = b->bbox_w; g.bbox_h = b->bbox_h; g.min_inten = b->min_inten; g.max_inten = b->max_inten;
         g.out = d_out; g.ld = ld; g.status = ctx->d_status.as<int>();
         g.mask = mask3;
-        g.col_gabor = n_cols1 + n_cols2 + n_cols4;
-        g.col_zernike = g.col_gabor + ((mask3 & NYXHIP_FAM_GABOR) ? s->gabor_n_filters : 0);
+        // (FRAC_AT_D sits before Gabor, MEAN_FRAC and RADIAL_CV between Gabor and Zernike: featureset.h:352-357)
+        g.col_gabor = n_cols1 + n_cols2 + n_cols4 + ((mask & NYXHIP_FAM_RADIAL) ? kRadialBins : 0);
+        g.col_zernike = g.col_gabor + ((mask3 & NYXHIP_FAM_GABOR) ? s->gabor_n_filters : 0) + ((mask & NYXHIP_FAM_RADIAL) ? 2 * kRadialBins : 0);
         g.soft_nan = s->soft_nan;
         g.small_rois = (E.px <= kClassPx[0] && E.side <= kClassSide[0]) ? 1 : 0;   // the smallest size class (a function of the ROI: roi_class)
         g.gabor_bank = ctx->d_bank.as<double>(); g.gabor_bank32 = ctx->d_bank32.as<float>(); g.gabor_bank16 = ctx->d_bank16.p; { static const int dbg_phase_env = [] { const char* e = getenv("NYXHIP_DBG_PHASE"); return e ? atoi(e) : 0; }(); g.dbg_phase = dbg_phase_env; } g.gabor_nf = s->gabor_n_filters; g.gabor_n = s->gabor_kersize; g.gabor_thr = s->gabor_graythr;
@@ -445,9 +446,11 @@ int use_lane(nyxhip_ctx* ctx, int lane, hipStream_t* st)
     return NYXHIP_OK;
 }
 
-// Contour + 2-D geometric moments (roi_moments.hip).  The contour of every ROI goes to a context-owned workspace at the
-// ROI's CSR offset (a contour never has more points than the ROI has pixels); the moments kernel reads it back.
-int launch_moments(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t mask, const nyxhip_settings* s, double* d_out, size_t ld,
+// Contour (roi_moments.hip) + the families that read it: the 2-D geometric moments (roi_moments.hip) and the radial intensity
+// distribution (roi_radial.hip).  The contour of every ROI goes to a context-owned workspace at the ROI's CSR offset (a contour
+// never has more points than the ROI has pixels) ONCE per call; the moments kernel and / or the radial kernel read it back.
+// (The workspace keeps its per-pixel double plane for a radial-only call too: the contour kernel's walk stack lives there.)
+int launch_contour_families(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t mask, const nyxhip_settings* s, double* d_out, size_t ld,
                    uint32_t max_px, uint32_t max_area, uint32_t max_side)
 {
     hipStream_t st = ctx->stream();
@@ -456,7 +459,7 @@ int launch_moments(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t mask, const 
     // runs beside them (enqueued last, dependent only on the batch).  Its scratch is the lane's, not the main stream's.
     static const bool no_mom_lane = [] { const char* e = getenv("NYXHIP_NO_MOM_LANE"); return e && *e && *e != '0'; }();   // A/B knob
     const bool big_boxes = (uint64_t)kContourWaves * (((uint64_t)max_area + 4ull * max_side + 4 + 15) & ~15ull) > (uint64_t)roi_features_max_lds();
-    const bool on_lane = !no_mom_lane && big_boxes && (mask & ~kMoments) && ctx->lane_fork;
+    const bool on_lane = !no_mom_lane && big_boxes && (mask & ~kContourFams) && ctx->lane_fork;
     if (on_lane)
         if (int lrc = use_lane(ctx, nyxhip_ctx::kMomLane, &st)) return lrc;
     DevBuf& spill = on_lane ? ctx->lane_buf[nyxhip_ctx::kMomLane] : ctx->d_spill;
@@ -473,7 +476,7 @@ int launch_moments(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t mask, const 
     m.px_offset = b->px_offset; m.x = b->x; m.y = b->y; m.inten = b->inten; m.bbox_w = b->bbox_w; m.bbox_h = b->bbox_h;
     m.out = d_out; m.ld = ld; m.status = ctx->d_status.as<int>();
     m.mask = mask & kMoments;
-    m.col_smoms = nyxhip_n_columns(mask & ~kMoments, s);
+    m.col_smoms = nyxhip_n_columns(mask & ~kMoments, s);     // (every other family, the radial distribution included, precedes the moments)
     m.col_imoms = m.col_smoms + ((mask & NYXHIP_FAM_SMOMS) ? kMomCols : 0);
     m.ws_contour = (uint32_t*)(base + o_k); m.n_contour = (uint32_t*)(base + o_n); m.ws_L = (double*)(base + o_l);
     if (!ctx->d_logtab) {                                 // log(sqrt(d) + 0.001), d < 32768: boxes up to 128 x 128 never evaluate a logarithm
@@ -488,6 +491,36 @@ int launch_moments(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t mask, const 
     m.px_cap = std::min<uint32_t>((uint32_t)kMomPxLds, (std::max<uint32_t>(max_px ? max_px : max_area, 1u) + 7u) & ~7u);
     m.k_cap = std::min<uint32_t>((uint32_t)kMomContourLds, std::max<uint32_t>(256u, (4u * std::min<uint32_t>(max_side, 65536u) + 63u) & ~63u));
     m.step_cap = std::min<uint32_t>((uint32_t)kMomStepTab, m.k_cap);
+    const bool do_mom = (mask & kMoments) != 0, do_rad = (mask & NYXHIP_FAM_RADIAL) != 0;
+    RadArgs ra;
+    memset(&ra, 0, sizeof(ra));
+    if (do_rad) {
+        // columns: FRAC_AT_D | GABOR | MEAN_FRAC | RADIAL_CV (enum order)
+        const uint32_t before = NYXHIP_FAM_INTENSITY | NYXHIP_FAM_GLCM | kTexture | kDependence;
+        ra.col_frac = nyxhip_n_columns(mask & before, s);
+        ra.col_mean = ra.col_frac + kRadialBins + ((mask & NYXHIP_FAM_GABOR) ? s->gabor_n_filters : 0);
+        ra.col_cv = ra.col_mean + kRadialBins;
+        // the wedge of the eight directions that lie ON an octant boundary: the reference expression (radial_distribution.cpp:92-96)
+        // on the host's libm, as the reference evaluates it; every other direction is an exact integer test in the kernel
+        static const int kDirX[8] = {1, 1, 0, -1, -1, -1, 0, 1}, kDirY[8] = {0, 1, 1, 1, 0, -1, -1, -1};
+        const double two_pi = 2.0 * 3.14159265358979323846;
+        for (int k = 0; k < 8; k++) {
+            double ang = std::atan2((double)kDirY[k], (double)kDirX[k]);
+            if (ang < 0) ang = two_pi + ang;
+            const double angW = two_pi / double(kRadialBins);
+            const int w_bin = std::min(std::max(int(ang / angW), 0), kRadialBins - 1);
+            ra.wedge_tab |= (uint32_t)w_bin << (4 * k);
+        }
+    }
+    // the readers of a contour launch, on its stream: the moments of `mm` and / or the radial distribution over the same ROIs
+    auto launch_readers = [&](const MomArgs& mm, hipStream_t s_, uint32_t g) -> int {
+        int r = do_mom ? launch_roi_moments(mm, s_, g) : 0;
+        if (r == 0 && do_rad) {
+            ra.m = mm;
+            r = launch_roi_radial(ra, s_, g);
+        }
+        return r;
+    };
     const uint64_t full_plane = (uint64_t)max_area + 4ull * max_side + 4;      // (w + 2)(h + 2) <= area + 2(w + h) + 4
     const uint32_t grid = (uint32_t)b->n_roi;
     const uint32_t lds_cap = (uint32_t)roi_features_max_lds();
@@ -495,7 +528,7 @@ int launch_moments(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t mask, const 
     if ((uint64_t)kContourWaves * ((full_plane + 15) & ~15ull) <= lds_cap) {   // kContourWaves planes per workgroup
         m.plane_cap = (uint32_t)full_plane;
         rc = launch_roi_contour(m, st, grid);
-        if (rc == 0) rc = launch_roi_moments(m, st, grid);
+        if (rc == 0) rc = launch_readers(m, st, grid);
     } else {
         // the bulk of the batch from LDS (16 KiB planes keep ten waves per CU), the oversized ROIs from a global workspace: a wave per ROI,
         // a few hundred waves and ~10 ms of latency for the heavy-tailed batch.  Two independent chains -- big boxes: list, contour over the
@@ -533,17 +566,17 @@ int launch_moments(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t mask, const 
             if (rc == 0) {                                    // moments of the big boxes: the list
                 MomArgs m3 = m;
                 m3.sp.roi_index = d_list;
-                rc = launch_roi_moments(m3, st_big, n_large);
+                rc = launch_readers(m3, st_big, n_large);
             }
         }
         if (rc == 0) {
             m.sp.defer_large = 1;                             // both kernels skip the big boxes
             rc = launch_roi_contour(m, st, grid);
-            if (rc == 0) rc = launch_roi_moments(m, st, grid);
+            if (rc == 0) rc = launch_readers(m, st, grid);
         }
     }
     if (rc != 0)
-        return fail(ctx, NYXHIP_ERR_HIP, std::string("moments kernel launch failed: ") + hipGetErrorString((hipError_t)rc));
+        return fail(ctx, NYXHIP_ERR_HIP, std::string("contour / moments / radial kernel launch failed: ") + hipGetErrorString((hipError_t)rc));
     return NYXHIP_OK;
 }
 
@@ -1254,7 +1287,7 @@ int launch_device_all(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t mask, con
         ctx->runs.push_back(r);
         return rc;
     };
-    if ((mask & ~kMoments) || !hinted) {               // (a batch without stated extrema gets them from the class headers)
+    if ((mask & ~kContourFams) || !hinted) {               // (a batch without stated extrema gets them from the class headers)
         bool done = false;
         static const bool force_exact = [] { const char* e = getenv("NYXHIP_CLASS_SYNC"); return e && *e && *e != '0'; }();   // A/B knob
         // (IBSI co-occurrence matrices are as large as the largest intensity, which a statement about the batch does not carry)
@@ -1339,7 +1372,7 @@ int launch_device_all(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t mask, con
             // A window-mode chunk (no clouds materialised) with a class that reads clouds -- the classes beyond LDS, and the wide-range
             // classes the bitmap kernel serves -- goes back for them BEFORE anything is launched: raised from inside the class loop it
             // made the caller run the whole chunk again, every LDS class computed twice (16-bit tiles: on every chunk).
-            if (ctx->win_next.inten && !b->inten && (mask & ~kMoments)) {
+            if (ctx->win_next.inten && !b->inten && (mask & ~kContourFams)) {
                 static const bool no_wide_pre = [] { const char* e = getenv("NYXHIP_NO_WIDE"); return e && *e && *e != '0'; }();
                 for (int cls = 0; cls < kClasses; cls++) {
                     if (H[cls * H_WORDS + H_COUNT] == 0) continue;
@@ -1349,7 +1382,7 @@ int launch_device_all(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t mask, con
             }
             static const bool no_merge = [] { const char* e = getenv("NYXHIP_NO_MERGE_LARGE"); return e && *e && *e != '0'; }();   // A/B knob
             int first_cls = kClasses - 1;
-            if (!no_merge && (mask & ~kMoments)) {
+            if (!no_merge && (mask & ~kContourFams)) {
                 uint32_t cnt = 0; int top = -1;
                 Extrema Em{0, 0, 0, 0, 0, false};
                 ClassTotals tm{0, 0, 0};
@@ -1367,7 +1400,7 @@ int launch_device_all(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t mask, con
                         return rc;
                 first_cls = 2 * kFirstLargeSizeClass - 1;
             }
-            for (int cls = first_cls; cls >= 0 && (mask & ~kMoments); cls--) {   // largest ROIs first: their long workgroups start early
+            for (int cls = first_cls; cls >= 0 && (mask & ~kContourFams); cls--) {   // largest ROIs first: their long workgroups start early
                 const uint32_t* h = H + cls * H_WORDS;
                 if (h[H_COUNT] == 0) continue;
                 const Extrema E{h[H_PX], h[H_AREA], h[H_RANGE], h[H_SIDE], h[H_VMAX], (cls & 1) != 0 && cls / 2 < kSizeClasses - 1};
@@ -1378,8 +1411,8 @@ int launch_device_all(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t mask, con
             }
         }
     }
-    if (mask & kMoments)
-        if (int mrc = launch_moments(ctx, b, mask, s, d_out, ld, max_px, max_area, max_side))
+    if (mask & kContourFams)
+        if (int mrc = launch_contour_families(ctx, b, mask, s, d_out, ld, max_px, max_area, max_side))
             return mrc;
     return NYXHIP_OK;
 }
@@ -1635,7 +1668,7 @@ int validate(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t mask, const nyxhip
 {
     if (!ctx) return NYXHIP_ERR_INVALID_ARG;
     if (!b || !s || !out) return fail(ctx, NYXHIP_ERR_INVALID_ARG, "null batch / settings / out_table");
-    if (mask == 0 || (mask & ~NYXHIP_FAM_ALL)) return fail(ctx, NYXHIP_ERR_INVALID_ARG, "bad family mask");
+    if (mask == 0 || (mask & ~(NYXHIP_FAM_ALL | NYXHIP_FAM_RADIAL))) return fail(ctx, NYXHIP_ERR_INVALID_ARG, "bad family mask");
     if (mask & ~kImplemented)
         return fail(ctx, NYXHIP_ERR_UNSUPPORTED, "requested feature family is not implemented by the HIP path yet "
                     "(all seven hot-path families are implemented; bad mask?)");

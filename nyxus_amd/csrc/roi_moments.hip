@@ -19,6 +19,7 @@
 #include "device_math.h"
 #include "roi_kernel.h"
 #include "launch_util.h"
+#include "contour_descent.h"
 #include "../../include/nyxhip.h"
 
 namespace nyxhip {
@@ -311,55 +312,6 @@ __device__ __forceinline__ void mom_block_sum(double (&v)[N], double* s_red, dou
     blk_sync<GS>();
 }
 
-// (int)(m / log(m)) for the window widths m the hill descent meets; m <= 10 -> 1 (pixel.cpp:47,66)
-__device__ __forceinline__ int descent_step(size_t m, const uint16_t* tab, int tab_n)
-{
-    if (m <= 10) return 1;
-    if ((int)m < tab_n) return (int)tab[m];
-    return (int)((double)m / log((double)m));
-}
-
-// Pixel2::min_sqdist v2 (pixel.cpp:40-70): hill descent over the ordered contour.  step0 = (int)(n / log(n)).
-// SMALL: every coordinate is below 2^15, so the squared distances are exact in 32-bit integers (24-bit multiplies) and the
-// whole search runs on integer compares; otherwise the distances are formed in double like the reference's.  The index
-// arithmetic is 32-bit either way (a contour has fewer points than the ROI has pixels).
-template <bool SMALL>
-__device__ __forceinline__ double min_sqdist_v2(int px, int py, const uint32_t* K, int n, int step0, const uint16_t* tab, int tab_n)
-{
-    if (n == 0) return 0.0;
-    using dist_t = typename std::conditional<SMALL, uint32_t, double>::type;
-    const uint32_t ppack = ((uint32_t)px & 0xFFFFu) | ((uint32_t)py << 16);
-    auto sqd = [&](uint32_t i) -> dist_t {
-        const uint32_t k = K[i];
-        if (SMALL) {
-            // a contour point is x | y << 16 and both coordinates are below 2^15: the difference is one packed 16-bit subtraction,
-            // dx^2 + dy^2 one two-element dot product (v_pk_sub_i16 + v_dot2_i32_i16 instead of unpack / subtract / square / add)
-            typedef short s16x2 __attribute__((ext_vector_type(2)));
-            const s16x2 d = __builtin_bit_cast(s16x2, k) - __builtin_bit_cast(s16x2, ppack);
-            return (dist_t)(uint32_t)__builtin_amdgcn_sdot2(d, d, 0, false);
-        } else {
-            const double dx = (double)(int)(k & 0xFFFFu) - (double)px, dy = (double)(int)(k >> 16) - (double)py;
-            return (dist_t)(dx * dx + dy * dy);
-        }
-    };
-    dist_t extrem_d = sqd(0);
-    if (n == 1) return (double)extrem_d;
-    uint32_t a = 0, b = (uint32_t)n, extrem_i = 0;
-    uint32_t step = (uint32_t)step0;
-    do {
-        for (uint32_t i = a + step; i < b; i += step) {
-            const dist_t d = sqd(i);
-            if (extrem_d > d) { extrem_d = d; extrem_i = i; }
-        }
-        const uint32_t stepL = extrem_i >= step ? step : extrem_i,
-                       stepR = extrem_i + step < (uint32_t)n ? step : (uint32_t)n - extrem_i;
-        a = extrem_i - stepL;
-        b = extrem_i + stepR;
-        step = (uint32_t)descent_step((size_t)(b - a), tab, tab_n);
-    } while (b - a > 2);
-    return (double)extrem_d;
-}
-
 // The same search for boxes whose squared distances stay below 2^17 and contours below 2^15 - 1 points (every compact-staged ROI but
 // the 255 .. 256-pixel corner case): distance and index travel as ONE word, d << 15 | (i + 1), the incumbent with a zero index field,
 // so a round's "smaller distance wins, the incumbent keeps ties, the first of equal candidates wins" is one v_min_u32 per candidate
@@ -434,14 +386,14 @@ __global__ __launch_bounds__(kMB, OCC) void roi_moments_kernel(const MomArgs A)
 {
     __shared__ double s_red[4 * 16];
     __shared__ double s_raw[2][16], s_cen[2][16], s_wraw[2][10], s_wcen[2][7];
-    // staged pixels | contour | step table: sized per launch from the batch extrema (launch_moments), so that small ROIs do not
+    // staged pixels | contour | step table: sized per launch from the batch extrema (launch_contour_families), so that small ROIs do not
     // pay for the largest ROI the LDS path accepts -- the benchmark ROI needs 25 KB instead of the 38 KB the fixed arrays took
     extern __shared__ __attribute__((aligned(16))) unsigned char mom_lds[];
     uint2* const s_px = (uint2*)mom_lds;                                  // [A.px_cap]
     uint32_t* const s_K = (uint32_t*)(mom_lds + 8u * A.px_cap);           // [A.k_cap]
     uint16_t* const s_step = (uint16_t*)(s_K + A.k_cap);                  // [A.step_cap]
     const int tid = threadIdx.x;
-    const uint64_t roi = A.sp.roi_index ? A.sp.roi_index[blockIdx.x] : blockIdx.x;   // (a list: the big boxes of a batch, launch_moments)
+    const uint64_t roi = A.sp.roi_index ? A.sp.roi_index[blockIdx.x] : blockIdx.x;   // (a list: the big boxes of a batch, launch_contour_families)
     if (roi >= A.n_roi)
         return;
     const uint64_t off = A.px_offset[roi];

@@ -79,9 +79,14 @@ for _n in SMOMS:
 for _n in IMOMS:
     FAMILY_OF[_n] = _abi.FAM_IMOMS
 FAMILY_OF["GABOR"] = _abi.FAM_GABOR
+# RadialDistributionFeature: three codes of RADIAL_BINS values each (radial_distribution.h:36-39)
+RADIAL = ["FRAC_AT_D", "MEAN_FRAC", "RADIAL_CV"]
+RADIAL_BINS = 8
+for _n in RADIAL:
+    FAMILY_OF[_n] = _abi.FAM_RADIAL
 FAMILY_OF["ZERNIKE2D"] = _abi.FAM_ZERNIKE
 
-# group tokens (featureset.cpp:650-665) the HIP path can serve completely
+# group tokens (featureset.cpp:650-665) the HIP path can serve completely (the radial distribution has none, featureset.cpp:650-668)
 GROUPS: Dict[str, List[str]] = {
     "*ALL_INTENSITY*": INTENSITY,
     "*ALL_GLCM*": GLCM_ANGLED + GLCM_AVE,
@@ -98,7 +103,7 @@ GROUPS: Dict[str, List[str]] = {
 
 # enum order of every feature code the path covers (one entry per Feature2D code)
 ENUM_ORDER: List[str] = (INTENSITY + GLCM_ANGLED + GLCM_AVE + GLRLM_ANGLED + GLRLM_AVE + GLDZM + GLSZM + GLDM + NGLDM + NGTDM
-                         + ["GABOR", "ZERNIKE2D"] + SMOMS + IMOMS)
+                         + ["FRAC_AT_D", "GABOR", "MEAN_FRAC", "RADIAL_CV", "ZERNIKE2D"] + SMOMS + IMOMS)   # featureset.h:352-357
 
 
 def expand(features: List[str]) -> Tuple[int, List[str]]:
@@ -116,7 +121,8 @@ def expand(features: List[str]) -> Tuple[int, List[str]]:
     if unknown:
         raise ValueError(
             f"feature(s) {unknown} are not served by the MI355X path. Implemented: groups {sorted(GROUPS)} and the "
-            f"individual features of the intensity, GLCM, GLRLM, GLDZM, GLSZM, GLDM, NGLDM and NGTDM families, GABOR, ZERNIKE2D")
+            f"individual features of the intensity, GLCM, GLRLM, GLDZM, GLSZM, GLDM, NGLDM and NGTDM families, GABOR, ZERNIKE2D, "
+            f"FRAC_AT_D, MEAN_FRAC, RADIAL_CV")
     if not want:
         raise ValueError("no features requested")
     ordered = [n for n in ENUM_ORDER if n in want]
@@ -138,6 +144,8 @@ def column_selector(requested: List[str], all_columns: List[str], glcm_angles: L
             sel += [idx_of[f"{code}_{a}"] for a in (0, 45, 90, 135)]
         elif code == "GABOR":
             sel += [i for i, c in enumerate(all_columns) if c.startswith("GABOR_")]
+        elif code in RADIAL:
+            sel += [idx_of[f"{code}_{i}"] for i in range(RADIAL_BINS)]       # output_2_buffer.cpp:374-411
         elif code == "ZERNIKE2D":
             sel += [i for i, c in enumerate(all_columns) if c.startswith("ZERNIKE2D_Z")]
         else:
