@@ -129,7 +129,10 @@ struct nyxhip_ctx {
     // split GLCM: exported co-occurrence counts + matrix orders (grow-only)
     DevBuf d_glcm_ws;
     DevBuf d_glcm_ng;                // [n_roi] matrix order of every ROI whose counts were exported in the CURRENT call (0: none) -- cleared per call
-    DevBuf d_logtab;                 // moments: log(sqrt(d) + 0.001) per integer squared distance (roi_moments.hip)
+    // deferred intensity closing (RoiArgs::close_rec / close_flag): per-ROI records and pending flags (grow-only; the flags cleared per call)
+    DevBuf d_close_rec;
+    DevBuf d_close_flag;
+    DevBuf d_logtab;                // moments: log(sqrt(d) + 0.001) per integer squared distance (roi_moments.hip)
     uint32_t logtab_n = 0;
     // contour + moments workspace (grow-only): contour points, contour lengths, per-pixel log distances
     DevBuf d_mom;

@@ -354,6 +354,10 @@ int build_args(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t mask, const nyxh
         a.glcm_offset = s->glcm_offset; a.glcm_na = s->glcm_n_angles; a.glcm_symmetric = s->glcm_symmetric;
         for (int i = 0; i < kMaxAngles; i++) a.glcm_angles[i] = s->glcm_angles[i];
         a.n_hist = abs(s->grey_depth);
+        if ((mask1 & NYXHIP_FAM_INTENSITY) && cap == 0) {      // (sized and cleared once per call by launch_device_all)
+            a.close_rec = ctx->d_close_rec.as<double>();
+            a.close_flag = ctx->d_close_flag.as<uint32_t>();
+        }
         // small matrices (order <= 16, all angles in one pass, matlab or IBSI level values 1..Ng): the features run as their
         // own launch with one wave per ROI (glcm_features_kernel); the counts travel through a context-owned workspace
         const int gi = s->ibsi ? 0 : s->grey_depth;
@@ -1273,6 +1277,14 @@ int launch_device_all(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t mask, con
         // 0 = "nothing to derive": an ROI whose feature kernel returns before it states its matrix order (error paths) must not leave
         // glcm_features_kernel a stale order from an earlier call
         HIP_TRY(ctx, hipMemsetAsync(ctx->d_glcm_ng.p, 0, 4ull * n_roi, st));
+    }
+    if (mask & NYXHIP_FAM_INTENSITY) {
+        // records and pending flags of the deferred intensity closing (RoiArgs::close_rec).  intensity_close_kernel clears the flags it
+        // consumes; the clearing here covers a call that ended between a feature launch and its closing launch
+        const size_t need_rec = 8ull * kCloseRec * n_roi + 256, need_flag = 4ull * n_roi + 256;
+        HIP_TRY(ctx, ctx->d_close_rec.reserve(need_rec, st, need_rec + need_rec / 4));
+        HIP_TRY(ctx, ctx->d_close_flag.reserve(need_flag, st, need_flag + need_flag / 4));
+        HIP_TRY(ctx, hipMemsetAsync(ctx->d_close_flag.p, 0, 4ull * n_roi, st));
     }
     auto timed_class = [&](int cls, uint32_t count, const Extrema& E, const uint32_t* lp, uint32_t grid, uint32_t class_mask = 0, uint32_t group_sel = 0xF,
                            const ClassTotals* tot = nullptr) -> int {

@@ -829,7 +829,10 @@ struct KView {
         else return &a;
     }
 };
-template <bool GS, bool C16, bool SPLIT, bool D8, int FAM = 0, int TIER = 4, bool G16 = false, int WIN = 2, int NW = 4>
+// DEFER_P: the single-lane code that only turns finished sums into output columns is left to intensity_close_kernel (a lane per ROI,
+// launched behind this kernel): lane 0 writes the sums to the ROI's record (RoiArgs::close_rec) and raises its flag.  The 64-VGPR
+// builds only -- their limit is vector issue, and an instruction on one lane takes the slot of one on sixty-four.
+template <bool GS, bool C16, bool SPLIT, bool D8, int FAM = 0, int TIER = 4, bool G16 = false, int WIN = 2, int NW = 4, bool DEFER_P = false>
 __device__ __forceinline__ void roi_features_body(const RoiArgs& A, const uint64_t slot)
 {
     // NW = waves per ROI.  Only 4 (one workgroup per ROI) is built.  A one-wave build -- four ROIs per workgroup, for the smallest
@@ -1256,6 +1259,13 @@ __device__ __forceinline__ void roi_features_body(const RoiArgs& A, const uint64
         }
         grp_sync<GS, NW>(); // also: every s_val / s_cnt write of phase 1 is visible
         const bool blank = (vmin == 0 && vmax == 0); // intensity.cpp:121-122
+#if defined(NYX_NO_FUSED) || defined(NYX_NO_DEFER)   // diagnostic builds (A/B timing)
+        constexpr bool DEFER = false;
+#else
+        constexpr bool DEFER = DEFER_P && C16 && !GS;  // (the conditions of the fused sweep below: the record is filled from it)
+#endif
+        const bool defer = DEFER && !blank;            // a blank ROI closes here: it never reaches the sweeps
+        double* const rec = DEFER ? B->close_rec + roi * kCloseRec : nullptr;
         if (tid == 0) {                                // the sums' own outputs leave the registers right away
             double tot = 0, totsq = 0;
             for (int wv = 0; wv < NW; wv++) {
@@ -1266,6 +1276,10 @@ __device__ __forceinline__ void roi_features_body(const RoiArgs& A, const uint64
             s_stat[S_MEAN] = mean;
             if (FAST)                                  // GLCM degenerate guard (glcm.cpp:27-95, on GLCM_GREYDEPTH): two binnings, once per ROI
                 s_stat[S_NG] = bin_pixel(vmin, vmin, vmax, B->glcm_grey_depth) == bin_pixel(vmax, vmin, vmax, B->glcm_grey_depth) ? 1.0 : 0.0;
+            if (defer) {
+                rec[CR_TOT] = tot;
+                rec[CR_TOTSQ] = totsq;
+            } else {
             o[I_MIN] = (double)vmin;                   // intensity.cpp:67-69
             o[I_MAX] = (double)vmax;
             o[I_RANGE] = (double)vmax - (double)vmin;
@@ -1277,6 +1291,7 @@ __device__ __forceinline__ void roi_features_body(const RoiArgs& A, const uint64
             o[I_INTEGRATED_INTENSITY] = tot;
             if (!blank)
                 o[I_UNIFORMITY_PIU] = (1.0 - (double)(vmax - vmin) / (double)(uint32_t)(vmax + vmin)) * 100.0; // :162
+            }
         }
         grp_sync<GS, NW>();
         const double mean = s_stat[S_MEAN];
@@ -1610,8 +1625,10 @@ __device__ __forceinline__ void roi_features_body(const RoiArgs& A, const uint64
                 }
                 if (lane == 0) {
                     o[I_P01] = pq[0]; o[I_P10] = pq[1]; o[I_P25] = pq[2]; o[I_P75] = pq[3]; o[I_P90] = pq[4]; o[I_P99] = pq[5];
-                    o[I_QCOD] = (pq[3] - pq[2]) / (pq[3] + pq[2]);
-                    o[I_INTERQUARTILE_RANGE] = pq[3] - pq[2];
+                    if (!DEFER) {                      // (deferred: derived from the P25 and P75 of the row)
+                        o[I_QCOD] = (pq[3] - pq[2]) / (pq[3] + pq[2]);
+                        o[I_INTERQUARTILE_RANGE] = pq[3] - pq[2];
+                    }
                     s_stat[S_P10] = pq[1];
                     s_stat[S_P90] = pq[4];
                     if (FUSED) {
@@ -1761,6 +1778,17 @@ __device__ __forceinline__ void roi_features_body(const RoiArgs& A, const uint64
                 const uint32_t Sx_all = (uint32_t)xw_pairs<NW>(s_red, 6);
                 const uint32_t Sxu = (uint32_t)__builtin_amdgcn_readfirstlane((int)(Sx_all - n_below * lox - n_above * hix));   // < 2^30
                 const double Sx = (double)Sxu, dK = (double)K;
+                if (DEFER) {
+                    // the totals of the eight exchange slots leave on a lane each (slots 6 and 7 hold integers: exact in either order),
+                    // the scalars of the robust statistics on lane 0
+                    if (tid < 8)
+                        rec[CR_ACC + tid] = xw_chain<NW>(s_red, tid);
+                    if (tid == 0) {
+                        uint32_t* const rw = (uint32_t*)rec;
+                        *(uint4*)(rw + CR_W_NBELOW) = make_uint4(n_below, n_above, K, Sxu);
+                        *(uint4*)(rw + CR_W_LOX) = make_uint4(lox, hix, m2x, ((const uint32_t*)(s_stat + 10))[1]);
+                    }
+                } else
                 if (tid == 0) {
                     double a6[6];
 #pragma unroll
@@ -1811,6 +1839,13 @@ __device__ __forceinline__ void roi_features_body(const RoiArgs& A, const uint64
                     ad1[0] = (double)ad;
                 }
                 block_sum<1, GS, NW>(ad1, (double*)s_lb100, tid);
+                if (DEFER) {
+                    if (tid == 0) {
+                        rec[CR_ADIN] = ad1[0];
+                        ((uint32_t*)rec)[CR_W_FAST32] = fast32 ? 1u : 0u;
+                        B->close_flag[roi] = 1u;
+                    }
+                } else
                 if (tid == 0) {
                     double adin = ad1[0];
                     if (fast32) {                      // (exact: every term is an integer below 2^53)
@@ -2024,11 +2059,22 @@ __device__ __forceinline__ void roi_features_body(const RoiArgs& A, const uint64
             if (dpp) {
                 // dense cell i = (q, r, c) sits at q * (Ng+1)^2 + (r+1) * (Ng+1) + c + 1.  The two small divisions go through
                 // float: (i + 1/2) / d is never closer than 1/(2d) to an integer, far beyond the error of the reciprocal.
+                if ((Ng & (Ng - 1)) == 0 && ((na * NN) & (BS - 1)) == 0) {
+                    // a power-of-two order in whole trips of the workgroup: (q, r, c) by shifts and masks, no bound per lane
+                    const int lg = 31 - __builtin_clz((unsigned)Ng);
+                    const uint32_t cm = (uint32_t)Ng - 1u;
+                    for (int i0 = 0; i0 < na * NN; i0 += BS) {   // (wave-uniform trip count)
+                        const uint32_t i = (uint32_t)(i0 + tid);
+                        const uint32_t q = i >> (2 * lg), r = (i >> lg) & cm, c = i & cm;
+                        dst[i] = s_P[mad24(q, (uint32_t)cells, mad24(r + 1u, (uint32_t)NG1, c + 1u))];
+                    }
+                } else {
                 const float inv_nn = __builtin_amdgcn_rcpf((float)NN), inv_ng = __builtin_amdgcn_rcpf((float)Ng);
                 for (int i = tid; i < na * NN; i += BS) {
                     const uint32_t q = (uint32_t)(((float)i + 0.5f) * inv_nn), rem = (uint32_t)i - mul24(q, (uint32_t)NN);
                     const uint32_t r = (uint32_t)(((float)rem + 0.5f) * inv_ng), c = rem - mul24(r, (uint32_t)Ng);
                     dst[i] = s_P[mad24(q, (uint32_t)cells, mad24(r + 1u, (uint32_t)NG1, c + 1u))];
+                }
                 }
             } else
                 for (int i = tid; i < na * NN; i += BS)
@@ -2648,7 +2694,7 @@ __global__ __launch_bounds__(kBlock, 7) void roi_features_kernel_occ7(const RoiA
 template <int FAM, int WIN>
 __global__ __launch_bounds__(kBlock, 8) void roi_features_kernel_occ8(const RoiArgs A)   // 64 VGPRs: the fully compact build only
 {
-    roi_features_body<false, true, FAM == 1 || FAM == 3, true, FAM, 8, false, WIN>(A, (WIN == 1 && A.win.xcd_swz) ? xcd_slot(blockIdx.x, gridDim.x) : (uint64_t)blockIdx.x);
+    roi_features_body<false, true, FAM == 1 || FAM == 3, true, FAM, 8, false, WIN, 4, FAM == 1 || FAM == 2>(A, (WIN == 1 && A.win.xcd_swz) ? xcd_slot(blockIdx.x, gridDim.x) : (uint64_t)blockIdx.x);
 }
 // The same compile-time family sets and loaders at seven and six workgroups per CU: batches whose largest ROI needs a bigger
 // carve-out than the benchmark's (mixed-size data: the launch is sized by its largest ROI) keep the specialised body instead of
@@ -2812,6 +2858,151 @@ __global__ __launch_bounds__(kBlock, 8) void glcm_features_kernel8(const RoiArgs
     }
 }
 
+// ---- deferred intensity closing ------------------------------------------------------------------------------------------
+// One lane per ROI over the slots of the feature launch in front of it.  A lane whose ROI left a record (RoiArgs::close_flag) evaluates
+// the formulas the feature kernel runs on a single lane of a four-wave workgroup -- the same operations in the same order, the same
+// frcp / frsq / fdiv helpers and IEEE operations (roi_features_body: the sums' own outputs, central_outputs, the robust outputs, QCOD
+// and IQR) -- and clears the flag.  The columns go through LDS (packed: the 26 deferred ones) so that the wave stores a row's columns side by side.
+constexpr int kCloseBlock = 64;
+constexpr uint64_t kCloseCols =
+    (1ull << I_MIN) | (1ull << I_MAX) | (1ull << I_RANGE) | (1ull << I_COVERED_IMAGE_INTENSITY_RANGE) | (1ull << I_MEAN) | (1ull << I_ENERGY) |
+    (1ull << I_ROOT_MEAN_SQUARED) | (1ull << I_INTEGRATED_INTENSITY) | (1ull << I_UNIFORMITY_PIU) | (1ull << I_MEAN_ABSOLUTE_DEVIATION) |
+    (1ull << I_VARIANCE) | (1ull << I_VARIANCE_BIASED) | (1ull << I_STANDARD_DEVIATION) | (1ull << I_STANDARD_DEVIATION_BIASED) | (1ull << I_COV) |
+    (1ull << I_STANDARD_ERROR) | (1ull << I_SKEWNESS) | (1ull << I_KURTOSIS) | (1ull << I_EXCESS_KURTOSIS) | (1ull << I_HYPERSKEWNESS) |
+    (1ull << I_HYPERFLATNESS) | (1ull << I_ROBUST_MEAN) | (1ull << I_MEDIAN_ABSOLUTE_DEVIATION) | (1ull << I_ROBUST_MEAN_ABSOLUTE_DEVIATION) |
+    (1ull << I_QCOD) | (1ull << I_INTERQUARTILE_RANGE);
+__global__ __launch_bounds__(kCloseBlock) void intensity_close_kernel(const RoiArgs A)
+{
+    // The deferred columns of a lane, packed: 64 x 26 doubles = 13 KiB, twelve one-wave workgroups per CU -- the 3063 waves of the
+    // metric launch are resident at once (the launch is a chain of dependent reads per wave: 37 doubles per lane, all columns, held it to
+    // eight per CU and a second round)
+    constexpr int kPitch = __builtin_popcountll(kCloseCols);
+#ifndef NYX_CLOSE_DIRECT
+    __shared__ double s_o[kCloseBlock * kPitch];
+#endif
+    const int lane = (int)threadIdx.x;
+    uint64_t roi = 0;
+    bool mine = roi_of_slot(A.sp, (uint64_t)blockIdx.x * kCloseBlock + (uint64_t)lane, A.n_roi, roi) && glcm_roi_in_launch(A, roi);
+    if (mine) mine = A.close_flag[roi] != 0;
+    const unsigned long long todo = __ballot(mine);
+    if (todo == 0)
+        return;
+#ifdef NYX_CLOSE_DIRECT     // diagnostic build (A/B timing): every lane stores its columns straight into its row
+    double* const o = A.out + roi * A.ld + A.col_intensity;
+    auto O = [&](int c) -> double& { return o[c]; };
+#else
+    double* const o = s_o + lane * kPitch;
+    auto O = [&](int c) -> double& { return o[__builtin_popcountll(kCloseCols & ((1ull << c) - 1ull))]; };   // column -> packed slot
+#endif
+    if (mine) {
+        A.close_flag[roi] = 0;
+        const double* const rec = A.close_rec + roi * kCloseRec;
+        const uint32_t* const rw = (const uint32_t*)rec;
+        const double* const row = A.out + roi * A.ld + A.col_intensity;
+        const uint32_t n = (uint32_t)(A.px_offset[roi + 1] - A.px_offset[roi]);
+        const uint32_t vmin = A.min_inten[roi], vmax = A.max_inten[roi];
+        const double2 s01 = *(const double2*)(rec + CR_TOT);
+        double acc[6];
+#pragma unroll
+        for (int k = 0; k < 6; k += 2) {
+            const double2 t = *(const double2*)(rec + CR_ACC + k);
+            acc[k] = t.x; acc[k + 1] = t.y;
+        }
+        const double sadk = rec[CR_SADK], adin0 = rec[CR_ADIN];
+        const bool fast32 = rw[CR_W_FAST32] != 0;
+        const uint4 w0 = *(const uint4*)(rw + CR_W_NBELOW), w1 = *(const uint4*)(rw + CR_W_LOX);
+        const uint32_t n_below = w0.x, n_above = w0.y, K = w0.z, Sxu = w0.w, lox = w1.x, hix = w1.y, m2x = w1.z, cle = w1.w;
+        const double p25 = row[I_P25], p75 = row[I_P75];
+#pragma unroll
+        for (int c = 0; c < kIntensityCols; c++)
+            if ((kCloseCols >> c) & 1ull) O(c) = 0.0;           // (a column no formula below reaches keeps the zero of the row's fill)
+        const double dn = (double)n;
+        constexpr bool blank = false;                           // (a blank ROI is never deferred)
+        // ---- the sums' own outputs
+        const double tot = s01.x, totsq = s01.y;
+        const double mean = tot / dn;
+        O(I_MIN) = (double)vmin;                   // intensity.cpp:67-69
+        O(I_MAX) = (double)vmax;
+        O(I_RANGE) = (double)vmax - (double)vmin;
+        if (A.slide_min && A.slide_max)            // intensity.cpp:72-77
+            O(I_COVERED_IMAGE_INTENSITY_RANGE) = (double)(vmax - vmin) / (A.slide_max[roi] - A.slide_min[roi]);
+        O(I_MEAN) = mean;                          // intensity.cpp:95-99
+        O(I_ENERGY) = totsq;
+        O(I_ROOT_MEAN_SQUARED) = sqrt(totsq / dn);
+        O(I_INTEGRATED_INTENSITY) = tot;
+        if (!blank)
+            O(I_UNIFORMITY_PIU) = (1.0 - (double)(vmax - vmin) / (double)(uint32_t)(vmax + vmin)) * 100.0; // :162
+        // ---- central_outputs
+        {
+            const double var = acc[1];                 // intensity.cpp:110-118
+            const double inv_n = frcp(dn);
+            O(I_MEAN_ABSOLUTE_DEVIATION) = acc[0] * inv_n;
+            const double variance = dn > 1 ? var * frcp(dn - 1) : 0.0;
+            const double variance_b = dn > 1 ? var * inv_n : 0.0;
+            const double rsd = variance > 0 ? frsq(variance) : 0.0;     // 1 / sd (0 stands for "sd == 0": every use below tests it)
+            const double sd = variance * rsd;
+            const double rs_n = frsq(dn);
+            O(I_VARIANCE) = variance;
+            O(I_VARIANCE_BIASED) = variance_b;
+            O(I_STANDARD_DEVIATION) = sd;
+            O(I_STANDARD_DEVIATION_BIASED) = variance_b > 0 ? variance_b * frsq(variance_b) : 0.0;
+            O(I_COV) = sd / mean;                      // (IEEE: a zero mean must give the reference's inf / NaN)
+            O(I_STANDARD_ERROR) = sd * rs_n;
+            if (!blank) {
+                const double M2 = acc[1], M3 = acc[2], M4 = acc[3]; // moments.h:79-109
+                if (M2 != 0.0) {
+                    const double r = frsq(M2), r2 = r * r;           // 1 / sqrt(M2), 1 / M2
+                    const double kurt = n > 4 ? (dn * M4) * (r2 * r2) : 0.0;
+                    O(I_SKEWNESS) = n > 3 ? ((dn * rs_n) * M3) * (r2 * r) : 0.0;   // sqrt(n) M3 / pow(M2, 1.5)
+                    O(I_KURTOSIS) = kurt;
+                    O(I_EXCESS_KURTOSIS) = n > 4 ? kurt - 3 : 0.0;
+                }
+                // n * pow(sd, 5), n * pow(sd, 6), intensity.cpp:186-191; a zero denominator gives 0
+                const double rsd2 = rsd * rsd, t5 = inv_n * (rsd2 * rsd2 * rsd);
+                O(I_HYPERSKEWNESS) = acc[4] * t5;
+                O(I_HYPERFLATNESS) = acc[5] * (t5 * rsd);
+            }
+        }
+        // ---- robust outputs
+        {
+            const double Sx = (double)Sxu, dK = (double)K;
+            // sum |2x - m2x| = 2 sum |x - kmed| + (2 #(x <= kmed) - n  when m2x is odd)
+            const double sadt = 2.0 * sadk + ((m2x & 1u) ? 2.0 * (double)cle - dn : 0.0);
+            O(I_ROBUST_MEAN) = K ? (Sx + dK * (double)vmin) / dK : 0.0;   // exact integer sum / count, as the reference's
+            O(I_MEDIAN_ABSOLUTE_DEVIATION) = fdiv(sadt * 0.5, dn);
+            const uint32_t Ku = K;
+            double adin = adin0;
+            if (fast32) {                      // (exact: every term is an integer below 2^53)
+                const double klo = (double)Ku * (double)lox, khi = (double)Ku * (double)hix;
+                adin -= (double)n_below * fabs(klo - Sx) + (double)n_above * fabs(khi - Sx);
+            }
+            O(I_ROBUST_MEAN_ABSOLUTE_DEVIATION) = K ? fdiv(fdiv(adin, dK), dK) : 0.0;
+        }
+        O(I_QCOD) = (p75 - p25) / (p75 + p25);
+        O(I_INTERQUARTILE_RANGE) = p75 - p25;
+    }
+#ifndef NYX_CLOSE_DIRECT
+    __syncthreads();                                            // (one wave: orders the LDS writes before the row-wise reads)
+    // row r of the block by the whole wave: lane j stores the j-th deferred column
+    int mycol = -1;
+    {
+        int rank = 0;
+#pragma unroll
+        for (int c = 0; c < kIntensityCols; c++)
+            if ((kCloseCols >> c) & 1ull) { if (rank == lane) mycol = c; rank++; }
+    }
+    const uint32_t roi_lo = (uint32_t)roi, roi_hi = (uint32_t)(roi >> 32);
+    double* const dst0 = A.out + A.col_intensity + (mycol >= 0 ? mycol : 0);
+#pragma unroll 8
+    for (int r = 0; r < kCloseBlock; r++) {                     // (several rows' LDS reads in flight per trip)
+        if (!((todo >> r) & 1ull)) continue;
+        const uint64_t rr = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)roi_hi, r) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)roi_lo, r);
+        if (mycol >= 0)
+            dst0[rr * A.ld] = s_o[r * kPitch + lane];
+    }
+#endif
+}
+
 size_t glcm_features8_lds(uint32_t ng_cap)
 {
     return (2 * glcm8_cnt_bytes(ng_cap) + 8ull * (2 * kMaxAngles * 16 + 2 * kMaxAngles * 32)) * kWaves;
@@ -2841,8 +3032,9 @@ int no_static_lds(const void* f)
 }
 
 template <bool C16, bool SPLIT, bool D8>
-int launch_lds_variant(const RoiArgs& a, hipStream_t st, uint32_t grid)
+int launch_lds_variant(const RoiArgs& a, hipStream_t st, uint32_t grid, bool& deferred)
 {
+    deferred = false;
     static DeviceOnce optin;
     if (int orc = optin.run([]() -> int {
         const void* fns[22] = {(const void*)roi_features_kernel<false, C16, SPLIT, D8>, (const void*)roi_features_kernel_occ5<C16, SPLIT, D8>,
@@ -2881,6 +3073,17 @@ int launch_lds_variant(const RoiArgs& a, hipStream_t st, uint32_t grid)
     if (const char* e = getenv("NYXHIP_MAX_OCC")) occ = occ < atoi(e) ? occ : (atoi(e) < 4 ? 4 : atoi(e));   // tuning knob (bench experiments)
     const bool win = a.win.inten != nullptr;
     if (win && a.win.xcd_swz) grid = (grid + 7u) & ~7u;               // (xcd_slot: every XCD walks its own eighth of the slots)
+    // the 64-VGPR builds with the intensity block leave their closing math to intensity_close_kernel (launch_roi_features)
+    // (what roi_features_body decides from DEFER_P: occ == 8 implies a compile-time family set, C16 and an LDS launch.  A build with
+    //  -DNYX_NO_DEFER / -DNYX_NO_FUSED closes in-kernel and launches no closing kernel, but launch_device_all still clears the flags:
+    //  for timing against the in-kernel closing it is close to, not the same as, a build without the mechanism)
+#if defined(NYX_NO_FUSED) || defined(NYX_NO_DEFER)
+    deferred = false;
+#else
+    deferred = occ == 8 && (a.mask & NYXHIP_FAM_INTENSITY) != 0;
+#endif
+    if (deferred && !(a.close_rec && a.close_flag))
+        return (int)hipErrorInvalidValue;
     if (fam_ok && glcm_only && occ >= 6) {
         if (occ == 8) { if (win) hipLaunchKernelGGL((roi_features_kernel_occ8<3, 1>), dim3(grid), dim3(kBlock), a.L.total, st, a);
                         else hipLaunchKernelGGL((roi_features_kernel_occ8<3, 0>), dim3(grid), dim3(kBlock), a.L.total, st, a); }
@@ -2955,11 +3158,16 @@ int launch_roi_features(const RoiArgs& a, void* stream, uint32_t grid)
     // the GLCM code, so it can run the fully compact build (and its 64-VGPR tier) as well
     const bool d8 = a.L.dense8 != 0 || (c16 && !(a.mask & NYXHIP_FAM_GLCM));
     int rc;
+    bool deferred = false;
     if (a.small_class && !no_small && (c16 || !(a.mask & NYXHIP_FAM_INTENSITY)) && roi_small_supported(a)) rc = launch_roi_small(a, st, grid, a.small_class == 2);
     else
-    rc = d8 ? launch_lds_variant<true, true, true>(a, st, grid)
-           : c16 ? (split ? launch_lds_variant<true, true, false>(a, st, grid) : launch_lds_variant<true, false, false>(a, st, grid))
-                 : (split ? launch_lds_variant<false, true, false>(a, st, grid) : launch_lds_variant<false, false, false>(a, st, grid));
+    rc = d8 ? launch_lds_variant<true, true, true>(a, st, grid, deferred)
+           : c16 ? (split ? launch_lds_variant<true, true, false>(a, st, grid, deferred) : launch_lds_variant<true, false, false>(a, st, grid, deferred))
+                 : (split ? launch_lds_variant<false, true, false>(a, st, grid, deferred) : launch_lds_variant<false, false, false>(a, st, grid, deferred));
+    if (rc == 0 && deferred) {                    // the closing math of the ROIs that launch deferred, over the same slots
+        hipLaunchKernelGGL(intensity_close_kernel, dim3((grid + kCloseBlock - 1) / kCloseBlock), dim3(kCloseBlock), 0, st, a);
+        rc = (int)hipGetLastError();
+    }
     if (rc == 0 && split && a.glcm_feats != 1) {
         static const bool no_pairs = [] { const char* e = getenv("NYXHIP_GLCM_NO_PAIRS"); return e && *e && *e != '0'; }();   // A/B knob
         RoiArgs af = a;

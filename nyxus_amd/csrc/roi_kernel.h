@@ -126,6 +126,19 @@ struct WindowSrc {
 // Workgroup -> slot of a window-mode launch (grid rounded up to a multiple of 8): XCD b & 7 walks slots [x per, (x + 1) per).
 __host__ __device__ inline uint64_t xcd_slot(uint32_t b, uint32_t grid) { const uint32_t per = (grid + 7u) >> 3; return (uint64_t)(b & 7u) * per + (b >> 3); }
 
+// Record of a deferred intensity closing, in doubles (RoiArgs::close_rec): what the single-lane output code of the feature kernel
+// read from registers and LDS.  The ROI's pixel count, extrema and slide extrema are inputs of the call and are read from there.
+constexpr int kCloseRec = 16;           // doubles per record (128 B)
+enum {
+    CR_TOT = 0, CR_TOTSQ,               // sum and sum of squares of the intensities
+    CR_ACC,                             // [6] central sums: sum |d|, d^2 .. d^6
+    CR_SADK = 9,                        // sum |x - kmed| over all values (slot 8: the clamped sum, not used)
+    CR_ADIN,                            // sweep 2: sum |K clamp(x) - Sx| before the out-of-range correction
+    CR_W_FAST32 = 22,                   // 32-bit words from here on: sweep 2 ran in its 32-bit form (the correction applies)
+    CR_W_NBELOW = 24, CR_W_NABOVE, CR_W_K, CR_W_SXU,
+    CR_W_LOX, CR_W_HIX, CR_W_M2X, CR_W_CLE
+};
+
 struct RoiArgs {
     uint64_t n_roi;
     const uint64_t* px_offset;
@@ -160,6 +173,10 @@ struct RoiArgs {
                              // launch whose stated extrema promise class 0 only -> the wave-per-ROI kernel of roi_small.hip; 0 = roi_features_kernel
     uint32_t glcm_feats;     // split GLCM launches: 0 = glcm_features_kernel follows this launch over the same slots; 1 = not after this launch (the next
                              // launch group of the call derives this group's ROIs as well); 2 = it follows over ALL slots, class filter off
+    // deferred intensity closing (the 64-VGPR builds of roi_features_kernel): one lane leaves the ROI's finished sums in a record,
+    // intensity_close_kernel -- a lane per ROI, launched behind the feature kernel -- turns them into the output columns
+    double* close_rec;       // [n_roi][kCloseRec] records (CloseRec below)
+    uint32_t* close_flag;    // [n_roi] 1 = the ROI's record waits for intensity_close_kernel (which clears it); cleared per call as well
     SpillArgs sp;
     WindowSrc win;
     LdsLayout L;

@@ -41,7 +41,13 @@ if g:
     gn = [x[0] for x in g if x[1] == gmax]
     k1 = sum(ns) / len(ns) / 1e6 if d else 0.0
     k2 = sum(gn) / len(gn) / 1e6
-    print(f"== launch group: roi_features_kernel {k1:.3f} ms + glcm_features_kernel {k2:.3f} ms = {k1 + k2:.3f} ms ==")
+    # (+ intensity_close_kernel behind the builds that defer their closing math)
+    c = [(int(r["End_Timestamp"]) - int(r["Start_Timestamp"]), int(r.get("Grid_Size_X") or 0)) for f, r in rows("trace/**/*kernel_trace.csv")
+         if "intensity_close_kernel" in r.get("Kernel_Name", "")]
+    cn = [x[0] for x in c if x[1] == max(y[1] for y in c)] if c else []
+    k3 = sum(cn) / len(cn) / 1e6 if cn else 0.0
+    print(f"== launch group: roi_features_kernel {k1:.3f} ms + glcm_features_kernel {k2:.3f} ms = {k1 + k2:.3f} ms ==" +
+          (f" + intensity_close_kernel {k3:.4f} ms = {k1 + k2 + k3:.3f} ms" if cn else ""))
 
 print("== PMC (per dispatch of roi_features_kernel, averaged) ==")
 acc = defaultdict(list)
@@ -56,3 +62,15 @@ if "FETCH_SIZE" in acc:
 if "WRITE_SIZE" in acc:
     w = sum(acc["WRITE_SIZE"]) / len(acc["WRITE_SIZE"])
     print(f"WRITE_SIZE KB -> bytes: {w*1024:.4g}")
+
+# the closing launch of the deferred intensity outputs, per dispatch of the metric workload (its largest grid)
+cacc = defaultdict(list)
+cr = [(r, int(r.get("Grid_Size") or r.get("Grid_Size_X") or 0)) for f, r in rows("pmc_*/**/*counter_collection.csv") if "intensity_close_kernel" in r.get("Kernel_Name", "")]
+if cr:
+    cg = max(g_ for _, g_ in cr)
+    for r, g_ in cr:
+        if g_ == cg:
+            cacc[r["Counter_Name"]].append(float(r["Counter_Value"]))
+    print("== PMC (per dispatch of intensity_close_kernel, averaged) ==")
+    for k, v in sorted(cacc.items()):
+        print(f"CLOSE_{k}: n={len(v)} mean={sum(v)/len(v):.6g}")

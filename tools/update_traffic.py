@@ -6,12 +6,20 @@ tag = sys.argv[1]
 txt = open(os.path.join(ROOT, "gpurun_out", f"prof_{tag}", "summary.txt")).read()
 fetch = float(re.search(r"FETCH_SIZE: n=\d+ mean=([0-9.e+]+)", txt).group(1))
 write = float(re.search(r"WRITE_SIZE: n=\d+ mean=([0-9.e+]+)", txt).group(1))
+# the closing launch of the deferred intensity outputs belongs to the launch group.  ASSUMPTION, not measured: its reads are 128-byte
+# records and two doubles of a row per lane, not wide coalesced streams, so its FETCH_SIZE is taken as it is, without the x2 (the term is
+# under 1 % of the total either way); stated in the record's `correction`
+cf, cw = re.search(r"CLOSE_FETCH_SIZE: n=\d+ mean=([0-9.e+]+)", txt), re.search(r"CLOSE_WRITE_SIZE: n=\d+ mean=([0-9.e+]+)", txt)
+close_bytes = (float(cf.group(1)) + float(cw.group(1))) * 1024 if cf and cw else 0.0
 kern = re.search(r"launch group: roi_features_kernel ([0-9.]+) ms \+ glcm_features_kernel ([0-9.]+) ms", txt)
+kclose = re.search(r"\+ intensity_close_kernel ([0-9.]+) ms", txt)
 rec = {"round": tag, "kernel": "roi_features_kernel_occ8<1, 0>", "tiles": 1000, "gray_depth": 8,
        "FETCH_SIZE_KB": fetch, "WRITE_SIZE_KB": write,
-       "correction": "gfx950: FETCH_SIZE counts 64 B per 128-B request on wide coalesced streams -> x2 (MI355X_MICROARCH.md, HBM); WRITE_SIZE exact",
-       "hbm_bytes_per_launch": 2 * fetch * 1024 + write * 1024,
-       "rocprof_kernel_ms": [float(kern.group(1)), float(kern.group(2))] if kern else None,
+       "correction": "gfx950: FETCH_SIZE counts 64 B per 128-B request on wide coalesced streams -> x2 (MI355X_MICROARCH.md, HBM); WRITE_SIZE exact; "
+                     "intensity_close_kernel: FETCH_SIZE + WRITE_SIZE without the x2 (assumed: scattered 128-byte records, not measured)",
+       "hbm_bytes_per_launch": 2 * fetch * 1024 + write * 1024 + close_bytes, "intensity_close_bytes": close_bytes,
+       "rocprof_kernel_ms": ([float(kern.group(1)), float(kern.group(2))] + ([float(kclose.group(1))] if kclose else [])) if kern else None,
+       "rocprof_kernels": ["roi_features_kernel", "glcm_features_kernel"] + (["intensity_close_kernel"] if kclose else []),
        "kernel_source_sha256": hashlib.sha256(b"".join(open(os.path.join(ROOT, "nyxus_amd", "csrc", f_), "rb").read()
                                                        for f_ in ("roi_features.hip", "glcm_rows.h", "device_math.h", "roi_kernel.h"))).hexdigest(),
        "collected": f"rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE in separate passes (tools/profile_bench.sh {tag}), bench.py --steps 5 --warmup 2; "
