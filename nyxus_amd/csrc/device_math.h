@@ -151,17 +151,18 @@ __device__ __forceinline__ unsigned long long dpp_mov0(unsigned long long u)
     uint32_t lo = dpp_mov0<CTRL, ROW_MASK>((uint32_t)u), hi = dpp_mov0<CTRL, ROW_MASK>((uint32_t)(u >> 32));
     return ((unsigned long long)hi << 32) | lo;
 }
-__device__ __forceinline__ double readlane63(double v)
+// a 64-bit value out of lane `lane` (wave-uniform): two v_readlane_b32
+__device__ __forceinline__ unsigned long long readlane_u64(unsigned long long u, int lane)
 {
-    unsigned long long u = (unsigned long long)__double_as_longlong(v);
-    uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)u, 63), hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(u >> 32), 63);
-    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
-}
-__device__ __forceinline__ unsigned long long readlane63(unsigned long long u)
-{
-    uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)u, 63), hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(u >> 32), 63);
+    uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)u, lane), hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(u >> 32), lane);
     return ((unsigned long long)hi << 32) | lo;
 }
+__device__ __forceinline__ double readlane_f64(double v, int lane)
+{
+    return __longlong_as_double((long long)readlane_u64((unsigned long long)__double_as_longlong(v), lane));
+}
+__device__ __forceinline__ double readlane63(double v) { return readlane_f64(v, 63); }
+__device__ __forceinline__ unsigned long long readlane63(unsigned long long u) { return readlane_u64(u, 63); }
 __device__ __forceinline__ uint32_t readlane63(uint32_t v) { return (uint32_t)__builtin_amdgcn_readlane((int)v, 63); }
 
 // DPP control words (GFX9 ISA): row_shr:n = 0x110+n, row_bcast:15 = 0x142, row_bcast:31 = 0x143

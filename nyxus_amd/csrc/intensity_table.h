@@ -19,6 +19,7 @@
 #include "device_math.h"
 #include "roi_kernel.h"
 #include "glcm_rows.h"
+#include "intensity_close.h"
 
 namespace nyxhip {
 
@@ -134,19 +135,8 @@ __device__ __forceinline__ void intensity_from_table(const TAB& tab, const SUMS&
     const double dn = (double)n;
     const double mean = tot / dn;
     const bool blank = vmin == 0 && vmax == 0;                                // intensity.cpp:121-122
-    if (tid == 0) {
-        o[I_MIN] = (double)vmin;                                               // intensity.cpp:67-69
-        o[I_MAX] = (double)vmax;
-        o[I_RANGE] = (double)vmax - (double)vmin;
-        if (have_slide)                                                        // intensity.cpp:72-77
-            o[I_COVERED_IMAGE_INTENSITY_RANGE] = (double)(vmax - vmin) / slide_range;
-        o[I_MEAN] = mean;                                                      // intensity.cpp:95-99
-        o[I_ENERGY] = totsq;
-        o[I_ROOT_MEAN_SQUARED] = sqrt(totsq / dn);
-        o[I_INTEGRATED_INTENSITY] = tot;
-        if (!blank)
-            o[I_UNIFORMITY_PIU] = (1.0 - (double)(vmax - vmin) / (double)(uint32_t)(vmax + vmin)) * 100.0;   // :162
-    }
+    const RowColumns O{o};
+    if (tid == 0) close_sums(O, dn, vmin, vmax, tot, totsq, mean, have_slide, [=] { return slide_range; }, blank);
     // ---- sweep 1: central sums (intensity.cpp:102-109, :177-183; M2..M4 of moments.h:53-74 equal the plain central sums) and
     // the mode (largest count, smallest value on ties: histogram.h:289-309)
     double acc[6] = {0, 0, 0, 0, 0, 0};
@@ -155,28 +145,7 @@ __device__ __forceinline__ void intensity_from_table(const TAB& tab, const SUMS&
     wg4_sum<6>(acc, S.x, tid);
     if (tid == 0) {
         if (!blank) o[I_MODE] = (double)(vmin + mode_off);
-        // everything that depends only on the central sums (intensity.cpp:110-118, :166-191)
-        o[I_MEAN_ABSOLUTE_DEVIATION] = acc[0] / dn;
-        const double variance = dn > 1 ? acc[1] / (dn - 1) : 0.0, variance_b = dn > 1 ? acc[1] / dn : 0.0;
-        const double sd = sqrt(variance);
-        o[I_VARIANCE] = variance;
-        o[I_VARIANCE_BIASED] = variance_b;
-        o[I_STANDARD_DEVIATION] = sd;
-        o[I_STANDARD_DEVIATION_BIASED] = sqrt(variance_b);
-        o[I_COV] = sd / mean;
-        o[I_STANDARD_ERROR] = sd / sqrt(dn);
-        if (!blank) {
-            const double M2 = acc[1], M3 = acc[2], M4 = acc[3];               // moments.h:79-109
-            if (M2 != 0.0) {
-                const double kurt = n > 4 ? (dn * M4) / (M2 * M2) : 0.0;
-                o[I_SKEWNESS] = n > 3 ? (sqrt(dn) * M3) / (M2 * sqrt(M2)) : 0.0;
-                o[I_KURTOSIS] = kurt;
-                o[I_EXCESS_KURTOSIS] = n > 4 ? kurt - 3 : 0.0;
-            }
-            const double sd2 = sd * sd, d5 = dn * (sd2 * sd2 * sd), d6 = dn * (sd2 * sd2 * sd2);   // intensity.cpp:186-191
-            o[I_HYPERSKEWNESS] = d5 == 0. ? 0. : acc[4] / d5;
-            o[I_HYPERFLATNESS] = d6 == 0. ? 0. : acc[5] / d6;
-        }
+        close_central_ieee(O, acc, n, dn, mean, blank);
     }
     if (blank) { __syncthreads(); return; }
     // ---- histogram bin populations (histogram.h:55-78): lower bounds of the 100 percentile bins and the n custom bins -- the bin
@@ -246,8 +215,7 @@ __device__ __forceinline__ void intensity_from_table(const TAB& tab, const SUMS&
         if (lane == 0) {
             const double* const pq = S.pq;
             o[I_P01] = pq[0]; o[I_P10] = pq[1]; o[I_P25] = pq[2]; o[I_P75] = pq[3]; o[I_P90] = pq[4]; o[I_P99] = pq[5];
-            o[I_QCOD] = (pq[3] - pq[2]) / (pq[3] + pq[2]);
-            o[I_INTERQUARTILE_RANGE] = pq[3] - pq[2];
+            close_quartiles(O, pq[2], pq[3]);
             S.stat[0] = pq[1];
             S.stat[1] = pq[4];
         }

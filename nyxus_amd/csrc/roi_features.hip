@@ -33,6 +33,7 @@
 #include "launch_util.h"
 #include "glcm_rows.h"
 #include "glcm_w64.h"
+#include "intensity_close.h"
 #include "sort_lds.h"
 #include "../../include/nyxhip.h"
 
@@ -1280,17 +1281,8 @@ __device__ __forceinline__ void roi_features_body(const RoiArgs& A, const uint64
                 rec[CR_TOT] = tot;
                 rec[CR_TOTSQ] = totsq;
             } else {
-            o[I_MIN] = (double)vmin;                   // intensity.cpp:67-69
-            o[I_MAX] = (double)vmax;
-            o[I_RANGE] = (double)vmax - (double)vmin;
-            if (B->slide_min && B->slide_max)            // intensity.cpp:72-77
-                o[I_COVERED_IMAGE_INTENSITY_RANGE] = (double)(vmax - vmin) / (B->slide_max[roi] - B->slide_min[roi]);
-            o[I_MEAN] = mean;                          // intensity.cpp:95-99
-            o[I_ENERGY] = totsq;
-            o[I_ROOT_MEAN_SQUARED] = sqrt(totsq / dn);
-            o[I_INTEGRATED_INTENSITY] = tot;
-            if (!blank)
-                o[I_UNIFORMITY_PIU] = (1.0 - (double)(vmax - vmin) / (double)(uint32_t)(vmax + vmin)) * 100.0; // :162
+                close_sums(RowColumns{o}, dn, vmin, vmax, tot, totsq, mean, B->slide_min && B->slide_max,
+                           [&] { return B->slide_max[roi] - B->slide_min[roi]; }, blank);
             }
         }
         grp_sync<GS, NW>();
@@ -1448,39 +1440,6 @@ __device__ __forceinline__ void roi_features_body(const RoiArgs& A, const uint64
         constexpr bool FUSED = C16 && !GS;
 #endif
         double acc[6] = {0, 0, 0, 0, 0, 0};
-        auto central_outputs = [&](const double (&acc)[6]) {   // everything that depends only on the sums (single lane)
-            // Tolerance-class outputs: the quotients and roots go through reciprocal / reciprocal-square-root estimates with two
-            // Newton steps (1-2 ulp) and are shared -- 1/n, 1/(n-1), 1/sqrt(variance), 1/sqrt(M2), 1/sqrt(n) -- instead of ten
-            // IEEE divisions and five IEEE roots on one lane (which the whole wave waits for): ~90 instead of ~250 instructions.
-            const double var = acc[1];                 // intensity.cpp:110-118
-            const double inv_n = frcp(dn);
-            o[I_MEAN_ABSOLUTE_DEVIATION] = acc[0] * inv_n;
-            const double variance = dn > 1 ? var * frcp(dn - 1) : 0.0;
-            const double variance_b = dn > 1 ? var * inv_n : 0.0;
-            const double rsd = variance > 0 ? frsq(variance) : 0.0;     // 1 / sd (0 stands for "sd == 0": every use below tests it)
-            const double sd = variance * rsd;
-            const double rs_n = frsq(dn);
-            o[I_VARIANCE] = variance;
-            o[I_VARIANCE_BIASED] = variance_b;
-            o[I_STANDARD_DEVIATION] = sd;
-            o[I_STANDARD_DEVIATION_BIASED] = variance_b > 0 ? variance_b * frsq(variance_b) : 0.0;
-            o[I_COV] = sd / mean;                      // (IEEE: a zero mean must give the reference's inf / NaN)
-            o[I_STANDARD_ERROR] = sd * rs_n;
-            if (!blank) {
-                const double M2 = acc[1], M3 = acc[2], M4 = acc[3]; // moments.h:79-109
-                if (M2 != 0.0) {
-                    const double r = frsq(M2), r2 = r * r;           // 1 / sqrt(M2), 1 / M2
-                    const double kurt = n > 4 ? (dn * M4) * (r2 * r2) : 0.0;
-                    o[I_SKEWNESS] = n > 3 ? ((dn * rs_n) * M3) * (r2 * r) : 0.0;   // sqrt(n) M3 / pow(M2, 1.5)
-                    o[I_KURTOSIS] = kurt;
-                    o[I_EXCESS_KURTOSIS] = n > 4 ? kurt - 3 : 0.0;
-                }
-                // n * pow(sd, 5), n * pow(sd, 6), intensity.cpp:186-191; a zero denominator gives 0
-                const double rsd2 = rsd * rsd, t5 = inv_n * (rsd2 * rsd2 * rsd);
-                o[I_HYPERSKEWNESS] = acc[4] * t5;
-                o[I_HYPERFLATNESS] = acc[5] * (t5 * rsd);
-            }
-        };
         if (!FUSED || blank) {
             if (!blank) {
                 for (uint32_t i = tid; i < n; i += BS) {
@@ -1495,8 +1454,8 @@ __device__ __forceinline__ void roi_features_body(const RoiArgs& A, const uint64
                 }
                 block_sum<6, GS, NW>(acc, s_red, tid);
             }
-            if (tid == 0)
-                central_outputs(acc);
+            if (tid == 0)                              // everything that depends only on the sums (single lane)
+                close_central<CovDiv::ieee>(RowColumns{o}, acc, n, dn, mean, blank);
         }
         STAMP(4);
 
@@ -1619,16 +1578,12 @@ __device__ __forceinline__ void roi_features_body(const RoiArgs& A, const uint64
                 double pq[6];
 #pragma unroll
                 for (int q = 0; q < 6; q++) {
-                    const unsigned long long u = (unsigned long long)__double_as_longlong(pv);
-                    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)u, q), hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(u >> 32), q);
-                    pq[q] = __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
+                    pq[q] = readlane_f64(pv, q);
                 }
                 if (lane == 0) {
                     o[I_P01] = pq[0]; o[I_P10] = pq[1]; o[I_P25] = pq[2]; o[I_P75] = pq[3]; o[I_P90] = pq[4]; o[I_P99] = pq[5];
-                    if (!DEFER) {                      // (deferred: derived from the P25 and P75 of the row)
-                        o[I_QCOD] = (pq[3] - pq[2]) / (pq[3] + pq[2]);
-                        o[I_INTERQUARTILE_RANGE] = pq[3] - pq[2];
-                    }
+                    if (!DEFER)                        // (deferred: derived from the P25 and P75 of the row)
+                        close_quartiles(RowColumns{o}, pq[2], pq[3]);
                     s_stat[S_P10] = pq[1];
                     s_stat[S_P90] = pq[4];
                     if (FUSED) {
@@ -1777,7 +1732,7 @@ __device__ __forceinline__ void roi_features_body(const RoiArgs& A, const uint64
                 const uint32_t K = n_upto - n_below, n_above = n - n_upto;                 // (wave-uniform: the products below run on the scalar unit)
                 const uint32_t Sx_all = (uint32_t)xw_pairs<NW>(s_red, 6);
                 const uint32_t Sxu = (uint32_t)__builtin_amdgcn_readfirstlane((int)(Sx_all - n_below * lox - n_above * hix));   // < 2^30
-                const double Sx = (double)Sxu, dK = (double)K;
+                const double Sx = (double)Sxu;
                 if (DEFER) {
                     // the totals of the eight exchange slots leave on a lane each (slots 6 and 7 hold integers: exact in either order),
                     // the scalars of the robust statistics on lane 0
@@ -1796,12 +1751,10 @@ __device__ __forceinline__ void roi_features_body(const RoiArgs& A, const uint64
                         a6[k] = xw_chain<NW>(s_red, k);
                         asm volatile("" : "+v"(a6[k]) :: "memory");   // one total at a time: 28 reads in flight (or their adds sunk into the output code) would spill
                     }
-                    // sum |2x - m2x| = 2 sum |x - kmed| + (2 #(x <= kmed) - n  when m2x is odd)
                     const double sadk = xw_pairs<NW>(s_red, 7);
-                    const double sadt = 2.0 * sadk + ((m2x & 1u) ? 2.0 * (double)((const uint32_t*)(s_stat + 10))[1] - dn : 0.0);
-                    central_outputs(a6);
-                    o[I_ROBUST_MEAN] = K ? (Sx + dK * (double)vmin) / dK : 0.0;   // exact integer sum / count, as the reference's
-                    o[I_MEDIAN_ABSOLUTE_DEVIATION] = fdiv(sadt * 0.5, dn);
+                    const uint32_t cle = ((const uint32_t*)(s_stat + 10))[1];
+                    close_central<CovDiv::ieee>(RowColumns{o}, a6, n, dn, mean, blank);
+                    close_robust_mad(RowColumns{o}, sadk, m2x, cle, K, Sx, vmin, dn);
                 }
                 // sweep 2: robust MAD about mean1090 = S / K (histogram.h:102-112): sum |a - S/K| = sum |K x - Sx| / K, exact in integers.
                 // The clamp again: sum over ALL values of |K clamp(x) - Sx|, minus what the values outside contribute
@@ -1846,14 +1799,8 @@ __device__ __forceinline__ void roi_features_body(const RoiArgs& A, const uint64
                         B->close_flag[roi] = 1u;
                     }
                 } else
-                if (tid == 0) {
-                    double adin = ad1[0];
-                    if (fast32) {                      // (exact: every term is an integer below 2^53)
-                        const double klo = (double)Ku * (double)lox, khi = (double)Ku * (double)hix;
-                        adin -= (double)n_below * fabs(klo - Sx) + (double)n_above * fabs(khi - Sx);
-                    }
-                    o[I_ROBUST_MEAN_ABSOLUTE_DEVIATION] = K ? fdiv(fdiv(adin, dK), dK) : 0.0;
-                }
+                if (tid == 0)
+                    close_robust_rmad(RowColumns{o}, ad1[0], fast32, K, Sx, lox, hix, n_below, n_above);
             } else {
             // sweep 1: sum and count inside [p10, p90], and the median absolute deviation (it only needs the median)
             double rb[3] = {0, 0, 0};
@@ -2859,10 +2806,10 @@ __global__ __launch_bounds__(kBlock, 8) void glcm_features_kernel8(const RoiArgs
 }
 
 // ---- deferred intensity closing ------------------------------------------------------------------------------------------
-// One lane per ROI over the slots of the feature launch in front of it.  A lane whose ROI left a record (RoiArgs::close_flag) evaluates
-// the formulas the feature kernel runs on a single lane of a four-wave workgroup -- the same operations in the same order, the same
-// frcp / frsq / fdiv helpers and IEEE operations (roi_features_body: the sums' own outputs, central_outputs, the robust outputs, QCOD
-// and IQR) -- and clears the flag.  The columns go through LDS (packed: the 26 deferred ones) so that the wave stores a row's columns side by side.
+// One lane per ROI over the slots of the feature launch in front of it.  A lane whose ROI left a record (RoiArgs::close_flag) closes the
+// columns the feature kernel closes on a single lane of a four-wave workgroup, through the same functions (intensity_close.h: the sums'
+// own outputs, the central block, the robust outputs, QCOD and IQR), and clears the flag.  The columns go through LDS (packed: the 26
+// deferred ones) so that the wave stores a row's columns side by side.
 constexpr int kCloseBlock = 64;
 constexpr uint64_t kCloseCols =
     (1ull << I_MIN) | (1ull << I_MAX) | (1ull << I_RANGE) | (1ull << I_COVERED_IMAGE_INTENSITY_RANGE) | (1ull << I_MEAN) | (1ull << I_ENERGY) |
@@ -2918,68 +2865,14 @@ __global__ __launch_bounds__(kCloseBlock) void intensity_close_kernel(const RoiA
             if ((kCloseCols >> c) & 1ull) O(c) = 0.0;           // (a column no formula below reaches keeps the zero of the row's fill)
         const double dn = (double)n;
         constexpr bool blank = false;                           // (a blank ROI is never deferred)
-        // ---- the sums' own outputs
         const double tot = s01.x, totsq = s01.y;
         const double mean = tot / dn;
-        O(I_MIN) = (double)vmin;                   // intensity.cpp:67-69
-        O(I_MAX) = (double)vmax;
-        O(I_RANGE) = (double)vmax - (double)vmin;
-        if (A.slide_min && A.slide_max)            // intensity.cpp:72-77
-            O(I_COVERED_IMAGE_INTENSITY_RANGE) = (double)(vmax - vmin) / (A.slide_max[roi] - A.slide_min[roi]);
-        O(I_MEAN) = mean;                          // intensity.cpp:95-99
-        O(I_ENERGY) = totsq;
-        O(I_ROOT_MEAN_SQUARED) = sqrt(totsq / dn);
-        O(I_INTEGRATED_INTENSITY) = tot;
-        if (!blank)
-            O(I_UNIFORMITY_PIU) = (1.0 - (double)(vmax - vmin) / (double)(uint32_t)(vmax + vmin)) * 100.0; // :162
-        // ---- central_outputs
-        {
-            const double var = acc[1];                 // intensity.cpp:110-118
-            const double inv_n = frcp(dn);
-            O(I_MEAN_ABSOLUTE_DEVIATION) = acc[0] * inv_n;
-            const double variance = dn > 1 ? var * frcp(dn - 1) : 0.0;
-            const double variance_b = dn > 1 ? var * inv_n : 0.0;
-            const double rsd = variance > 0 ? frsq(variance) : 0.0;     // 1 / sd (0 stands for "sd == 0": every use below tests it)
-            const double sd = variance * rsd;
-            const double rs_n = frsq(dn);
-            O(I_VARIANCE) = variance;
-            O(I_VARIANCE_BIASED) = variance_b;
-            O(I_STANDARD_DEVIATION) = sd;
-            O(I_STANDARD_DEVIATION_BIASED) = variance_b > 0 ? variance_b * frsq(variance_b) : 0.0;
-            O(I_COV) = sd / mean;                      // (IEEE: a zero mean must give the reference's inf / NaN)
-            O(I_STANDARD_ERROR) = sd * rs_n;
-            if (!blank) {
-                const double M2 = acc[1], M3 = acc[2], M4 = acc[3]; // moments.h:79-109
-                if (M2 != 0.0) {
-                    const double r = frsq(M2), r2 = r * r;           // 1 / sqrt(M2), 1 / M2
-                    const double kurt = n > 4 ? (dn * M4) * (r2 * r2) : 0.0;
-                    O(I_SKEWNESS) = n > 3 ? ((dn * rs_n) * M3) * (r2 * r) : 0.0;   // sqrt(n) M3 / pow(M2, 1.5)
-                    O(I_KURTOSIS) = kurt;
-                    O(I_EXCESS_KURTOSIS) = n > 4 ? kurt - 3 : 0.0;
-                }
-                // n * pow(sd, 5), n * pow(sd, 6), intensity.cpp:186-191; a zero denominator gives 0
-                const double rsd2 = rsd * rsd, t5 = inv_n * (rsd2 * rsd2 * rsd);
-                O(I_HYPERSKEWNESS) = acc[4] * t5;
-                O(I_HYPERFLATNESS) = acc[5] * (t5 * rsd);
-            }
-        }
-        // ---- robust outputs
-        {
-            const double Sx = (double)Sxu, dK = (double)K;
-            // sum |2x - m2x| = 2 sum |x - kmed| + (2 #(x <= kmed) - n  when m2x is odd)
-            const double sadt = 2.0 * sadk + ((m2x & 1u) ? 2.0 * (double)cle - dn : 0.0);
-            O(I_ROBUST_MEAN) = K ? (Sx + dK * (double)vmin) / dK : 0.0;   // exact integer sum / count, as the reference's
-            O(I_MEDIAN_ABSOLUTE_DEVIATION) = fdiv(sadt * 0.5, dn);
-            const uint32_t Ku = K;
-            double adin = adin0;
-            if (fast32) {                      // (exact: every term is an integer below 2^53)
-                const double klo = (double)Ku * (double)lox, khi = (double)Ku * (double)hix;
-                adin -= (double)n_below * fabs(klo - Sx) + (double)n_above * fabs(khi - Sx);
-            }
-            O(I_ROBUST_MEAN_ABSOLUTE_DEVIATION) = K ? fdiv(fdiv(adin, dK), dK) : 0.0;
-        }
-        O(I_QCOD) = (p75 - p25) / (p75 + p25);
-        O(I_INTERQUARTILE_RANGE) = p75 - p25;
+        close_sums(O, dn, vmin, vmax, tot, totsq, mean, A.slide_min && A.slide_max, [&] { return A.slide_max[roi] - A.slide_min[roi]; }, blank);
+        close_central<CovDiv::ieee>(O, acc, n, dn, mean, blank);
+        const double Sx = (double)Sxu;
+        close_robust_mad(O, sadk, m2x, cle, K, Sx, vmin, dn);
+        close_robust_rmad(O, adin0, fast32, K, Sx, lox, hix, n_below, n_above);
+        close_quartiles(O, p25, p75);
     }
 #ifndef NYX_CLOSE_DIRECT
     __syncthreads();                                            // (one wave: orders the LDS writes before the row-wise reads)
@@ -2991,12 +2884,11 @@ __global__ __launch_bounds__(kCloseBlock) void intensity_close_kernel(const RoiA
         for (int c = 0; c < kIntensityCols; c++)
             if ((kCloseCols >> c) & 1ull) { if (rank == lane) mycol = c; rank++; }
     }
-    const uint32_t roi_lo = (uint32_t)roi, roi_hi = (uint32_t)(roi >> 32);
     double* const dst0 = A.out + A.col_intensity + (mycol >= 0 ? mycol : 0);
 #pragma unroll 8
     for (int r = 0; r < kCloseBlock; r++) {                     // (several rows' LDS reads in flight per trip)
         if (!((todo >> r) & 1ull)) continue;
-        const uint64_t rr = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)roi_hi, r) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)roi_lo, r);
+        const uint64_t rr = readlane_u64(roi, r);
         if (mycol >= 0)
             dst0[rr * A.ld] = s_o[r * kPitch + lane];
     }

@@ -26,6 +26,7 @@
 #include "roi_kernel.h"
 #include "glcm_rows.h"
 #include "glcm_w64.h"
+#include "intensity_close.h"
 #include "launch_util.h"
 #include "../../include/nyxhip.h"
 
@@ -287,12 +288,7 @@ __device__ __forceinline__ void small_one(const RoiArgs& A, const uint64_t slot,
         else if (lane == 3) { qn = (double)range; qd = 100.; }
         else if (lane == 4 && A.slide_min && A.slide_max) { qn = (double)(vmax - vmin); qd = A.slide_max[roi] - A.slide_min[roi]; }
         const double qq = qn / qd;
-        auto lane_d = [&](double x, int l) -> double {
-            const unsigned long long u = (unsigned long long)__double_as_longlong(x);
-            return __longlong_as_double((long long)(((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(u >> 32), l) << 32) |
-                                                    (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)u, l)));
-        };
-        const double mean = lane_d(qq, 0);
+        const double mean = readlane_f64(qq, 0);
         if (lane == 0) {
             o[I_MIN] = (double)vmin;                                       // intensity.cpp:67-69
             o[I_MAX] = (double)vmax;
@@ -317,45 +313,11 @@ __device__ __forceinline__ void small_one(const RoiArgs& A, const uint64_t slot,
             double t8[8] = {acc[0], acc[1], acc[2], acc[3], acc[4], acc[5], 0.0, 0.0};
             const double tot8 = wave_transpose_sum8(t8, lane);
 #pragma unroll
-            for (int k = 0; k < 6; k++) {
-                const unsigned long long u = (unsigned long long)__double_as_longlong(tot8);
-                acc[k] = __longlong_as_double((long long)(((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(u >> 32), 8 * k) << 32) |
-                                                         (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)u, 8 * k)));
-            }
+            for (int k = 0; k < 6; k++) acc[k] = readlane_f64(tot8, 8 * k);
         }
-        if (lane == 0) {
-            // everything that depends only on the central sums (intensity.cpp:110-118, :166-191, moments.h:79-109).  Tolerance-class outputs:
-            // the quotients and roots go through reciprocal / reciprocal-square-root estimates with two Newton steps (1-2 ulp) and are
-            // shared, as in roi_features_kernel's central_outputs -- ten IEEE divisions and five IEEE roots on one lane were a fifth of
-            // this kernel's instructions
-            const double var = acc[1];
-            const double inv_n = frcp(dn);
-            o[I_MEAN_ABSOLUTE_DEVIATION] = acc[0] * inv_n;
-            const double variance = dn > 1 ? var * frcp(dn - 1) : 0.0;
-            const double variance_b = dn > 1 ? var * inv_n : 0.0;
-            const double rsd = variance > 0 ? frsq(variance) : 0.0;       // 1 / sd (0 stands for "sd == 0": every use below tests it)
-            const double sd = variance * rsd;
-            const double rs_n = frsq(dn);
-            o[I_VARIANCE] = variance;
-            o[I_VARIANCE_BIASED] = variance_b;
-            o[I_STANDARD_DEVIATION] = sd;
-            o[I_STANDARD_DEVIATION_BIASED] = variance_b > 0 ? variance_b * frsq(variance_b) : 0.0;
-            o[I_COV] = mean != 0.0 ? fdiv(sd, mean) : sd / mean;           // (a zero mean must give the reference's inf / NaN: the IEEE quotient then)
-            o[I_STANDARD_ERROR] = sd * rs_n;
-            if (!blank) {
-                const double M2 = acc[1], M3 = acc[2], M4 = acc[3];
-                if (M2 != 0.0) {
-                    const double r = frsq(M2), r2 = r * r;                 // 1 / sqrt(M2), 1 / M2
-                    const double kurt = n > 4 ? (dn * M4) * (r2 * r2) : 0.0;
-                    o[I_SKEWNESS] = n > 3 ? ((dn * rs_n) * M3) * (r2 * r) : 0.0;   // sqrt(n) M3 / pow(M2, 1.5)
-                    o[I_KURTOSIS] = kurt;
-                    o[I_EXCESS_KURTOSIS] = n > 4 ? kurt - 3 : 0.0;
-                }
-                const double rsd2 = rsd * rsd, t5 = inv_n * (rsd2 * rsd2 * rsd);   // 1 / (n sd^5); a zero denominator gives 0 (intensity.cpp:186-191)
-                o[I_HYPERSKEWNESS] = acc[4] * t5;
-                o[I_HYPERFLATNESS] = acc[5] * (t5 * rsd);
-            }
-        }
+        // everything that depends only on the central sums: the estimate form of roi_features_kernel -- ten IEEE divisions and five IEEE
+        // roots on one lane were a fifth of this kernel's instructions
+        if (lane == 0) close_central<CovDiv::fast_nonzero>(RowColumns{o}, acc, n, dn, mean, blank);
         SMALL_EXIT(2);
         if (!blank) {
             // ---- sort the offsets (padding = 0xFFFFFFFF sorts to the end): a bitonic network in REGISTERS -- position e = NV * lane + k,
@@ -375,7 +337,7 @@ __device__ __forceinline__ void small_one(const RoiArgs& A, const uint64_t slot,
             wav_sync<false>();
             SMALL_EXIT(3);
             // ---- histogram bin populations (histogram.h:55-78): lower bounds of the 100 percentile bins and the n custom bins ------------
-            const double binW100 = lane_d(qq, 3);                          // (double)range / 100.
+            const double binW100 = readlane_f64(qq, 3);                          // (double)range / 100.
             if (n <= 64 && nb <= 64) {
                 // one value per lane: the reference's own bin function per pixel (two IEEE divisions), LDS counters, a wave scan -- a third of
                 // the three binary searches per lane below
@@ -452,8 +414,7 @@ __device__ __forceinline__ void small_one(const RoiArgs& A, const uint64_t slot,
             const double p10 = pq[1], p90 = pq[4];
             if (lane == 0) {
                 o[I_P01] = pq[0]; o[I_P10] = pq[1]; o[I_P25] = pq[2]; o[I_P75] = pq[3]; o[I_P90] = pq[4]; o[I_P99] = pq[5];
-                o[I_QCOD] = (pq[3] - pq[2]) / (pq[3] + pq[2]);
-                o[I_INTERQUARTILE_RANGE] = pq[3] - pq[2];
+                close_quartiles(RowColumns{o}, pq[2], pq[3]);
             }
             {
                 // entropy / uniformity over the n + 1 slots (histogram.h:145-151): slot n is empty
