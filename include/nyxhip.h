@@ -65,6 +65,12 @@ enum {
      * that constant keeps the twelve families it named before this one existed; OR this bit in explicitly.
      * Bit 12 stays unassigned: a mask that holds it is NYXHIP_ERR_INVALID_ARG, as it has always been. */
     NYXHIP_FAM_RADIAL    = 1u << 13, /* RadialDistributionFeature, 3 x 8 columns: FRAC_AT_D, MEAN_FRAC, RADIAL_CV (features/radial_distribution.h) */
+    /* three classes of the shape block that need no absolute ROI position (featureset.h:46-160).  Like NYXHIP_FAM_RADIAL they are
+     * not part of NYXHIP_FAM_ALL; bits 12 and 14 stay unassigned (NYXHIP_ERR_INVALID_ARG).  The columns follow the intensity block.
+     * Undefined in the reference, hence here: ROI_RADIUS_* of an ROI whose merged contour is a single point. */
+    NYXHIP_FAM_FRACTAL   = 1u << 15, /* FractalDimensionFeature, 2 columns: FRACT_DIM_BOXCOUNT, FRACT_DIM_PERIMETER (features/fractal_dim.h) */
+    NYXHIP_FAM_EULER     = 1u << 16, /* EulerNumberFeature, 1 column: EULER_NUMBER, mode 8 (features/euler_number.h)                        */
+    NYXHIP_FAM_ROI_RADIUS = 1u << 17, /* RoiRadiusFeature, 3 columns: ROI_RADIUS_MEAN, ROI_RADIUS_MAX, ROI_RADIUS_MEDIAN (features/roi_radius.h) */
     NYXHIP_FAM_NORTH_STAR = 0x7Fu,  /* the seven families of BASELINE.json's north_star */
     NYXHIP_FAM_ALL       = 0xFFFu
 };

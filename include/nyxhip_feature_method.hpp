@@ -38,6 +38,8 @@ enum class Feature2D : int {
     MEDIAN_ABSOLUTE_DEVIATION, MIN, MODE, P01, P10, P25, P75, P90, P99, QCOD, RANGE, ROBUST_MEAN,
     ROBUST_MEAN_ABSOLUTE_DEVIATION, ROOT_MEAN_SQUARED, SKEWNESS, STANDARD_DEVIATION, STANDARD_DEVIATION_BIASED,
     STANDARD_ERROR, VARIANCE, VARIANCE_BIASED, UNIFORMITY, UNIFORMITY_PIU,
+    // three classes of the shape block (featureset.h:46-160), in enum position: between the intensity block and GLCM
+    FRACT_DIM_BOXCOUNT, FRACT_DIM_PERIMETER, EULER_NUMBER, ROI_RADIUS_MEAN, ROI_RADIUS_MAX, ROI_RADIUS_MEDIAN,
     GLCM_ASM, GLCM_ACOR, GLCM_CLUPROM, GLCM_CLUSHADE, GLCM_CLUTEND, GLCM_CONTRAST, GLCM_CORRELATION, GLCM_DIFAVE,
     GLCM_DIFENTRO, GLCM_DIFVAR, GLCM_DIS, GLCM_ENERGY, GLCM_ENTROPY, GLCM_HOM1, GLCM_HOM2, GLCM_ID, GLCM_IDN,
     GLCM_IDM, GLCM_IDMN, GLCM_INFOMEAS1, GLCM_INFOMEAS2, GLCM_IV, GLCM_JAVE, GLCM_JE, GLCM_JMAX, GLCM_JVAR,
@@ -245,6 +247,9 @@ inline void reduce_range(uint32_t mask, size_t start, size_t end, std::vector<in
             for (int f = (int)first; f <= (int)last; f++) { r.fvals[f].assign(p, p + width); p += width; }
         };
         if (mask & NYXHIP_FAM_INTENSITY) put(Feature2D::COV, Feature2D::UNIFORMITY_PIU, 1);
+        if (mask & NYXHIP_FAM_FRACTAL) put(Feature2D::FRACT_DIM_BOXCOUNT, Feature2D::FRACT_DIM_PERIMETER, 1);
+        if (mask & NYXHIP_FAM_EULER) put(Feature2D::EULER_NUMBER, Feature2D::EULER_NUMBER, 1);
+        if (mask & NYXHIP_FAM_ROI_RADIUS) put(Feature2D::ROI_RADIUS_MEAN, Feature2D::ROI_RADIUS_MEDIAN, 1);
         if (mask & NYXHIP_FAM_GLCM) { put(Feature2D::GLCM_ASM, Feature2D::GLCM_VARIANCE, na); put(Feature2D::GLCM_ASM_AVE, Feature2D::GLCM_SUMVARIANCE_AVE, 1); }
         if (mask & NYXHIP_FAM_GLRLM) { put(Feature2D::GLRLM_SRE, Feature2D::GLRLM_LRHGLE, 4); put(Feature2D::GLRLM_SRE_AVE, Feature2D::GLRLM_LRHGLE_AVE, 1); }
         if (mask & NYXHIP_FAM_GLDZM) put(Feature2D::GLDZM_SDE, Feature2D::GLDZM_ZDE, 1);
@@ -321,6 +326,10 @@ NYXHIP_FAMILY_CLASS(ZernikeFeature, NYXHIP_FAM_ZERNIKE, ZERNIKE2D, ZERNIKE2D)
 // the contour the weighted moments depend on (ContourFeature::reduce, reduce_trivial_rois.cpp:98-111) is built inside the call
 NYXHIP_FAMILY_CLASS(Smoms2D_feature, NYXHIP_FAM_SMOMS, SPAT_MOMENT_00, WEIGHTED_HU_M7)
 NYXHIP_FAMILY_CLASS(Imoms2D_feature, NYXHIP_FAM_IMOMS, IMOM_RM_00, IMOM_WHU7)
+// features/fractal_dim.h, euler_number.h (mode 8), roi_radius.h: the contour the first and the last depend on is built inside the call
+NYXHIP_FAMILY_CLASS(FractalDimensionFeature, NYXHIP_FAM_FRACTAL, FRACT_DIM_BOXCOUNT, FRACT_DIM_PERIMETER)
+NYXHIP_FAMILY_CLASS(EulerNumberFeature, NYXHIP_FAM_EULER, EULER_NUMBER, EULER_NUMBER)
+NYXHIP_FAMILY_CLASS(RoiRadiusFeature, NYXHIP_FAM_ROI_RADIUS, ROI_RADIUS_MEAN, ROI_RADIUS_MEDIAN)
 
 // RadialDistributionFeature (features/radial_distribution.h): its three codes are not contiguous in the enum (GABOR sits
 // between FRAC_AT_D and MEAN_FRAC), so the class is spelled out.  The contour it depends on is built inside the call.
@@ -362,6 +371,9 @@ inline void reduce_trivial_rois_manual(std::vector<int>& PendingRoisLabels, std:
 {
     uint32_t mask = 0;
     if (PixelIntensityFeatures::required(fs)) mask |= NYXHIP_FAM_INTENSITY;
+    if (FractalDimensionFeature::required(fs)) mask |= NYXHIP_FAM_FRACTAL;
+    if (EulerNumberFeature::required(fs)) mask |= NYXHIP_FAM_EULER;
+    if (RoiRadiusFeature::required(fs)) mask |= NYXHIP_FAM_ROI_RADIUS;
     if (GLCMFeature::required(fs)) mask |= NYXHIP_FAM_GLCM;
     if (GLRLMFeature::required(fs)) mask |= NYXHIP_FAM_GLRLM;
     if (GLDZMFeature::required(fs)) mask |= NYXHIP_FAM_GLDZM;   // reduce_trivial_rois.cpp:215-220

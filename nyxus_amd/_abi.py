@@ -29,6 +29,10 @@ FAM_NGLDM = 1 << 9
 FAM_SMOMS = 1 << 10
 FAM_IMOMS = 1 << 11
 FAM_RADIAL = 1 << 13          # (bit 12 stays unassigned) RadialDistributionFeature (FRAC_AT_D, MEAN_FRAC, RADIAL_CV); not part of FAM_ALL
+# three classes of the shape block (columns behind the intensity block); not part of FAM_ALL, bits 12 and 14 stay unassigned
+FAM_FRACTAL = 1 << 15         # FractalDimensionFeature (FRACT_DIM_BOXCOUNT, FRACT_DIM_PERIMETER)
+FAM_EULER = 1 << 16           # EulerNumberFeature (EULER_NUMBER)
+FAM_ROI_RADIUS = 1 << 17      # RoiRadiusFeature (ROI_RADIUS_MEAN, ROI_RADIUS_MAX, ROI_RADIUS_MEDIAN)
 FAM_NORTH_STAR = 0x7F
 FAM_ALL = 0xFFF
 

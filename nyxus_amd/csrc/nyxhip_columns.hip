@@ -90,6 +90,10 @@ std::vector<std::string> column_names(uint32_t mask, const nyxhip_settings* s)
     std::vector<std::string> v;
     if (mask & NYXHIP_FAM_INTENSITY)
         for (auto n : kIntensityNames) v.push_back(n);
+    // the shape block follows the intensity block (featureset.h:46-160)
+    if (mask & NYXHIP_FAM_FRACTAL) { v.push_back("FRACT_DIM_BOXCOUNT"); v.push_back("FRACT_DIM_PERIMETER"); }
+    if (mask & NYXHIP_FAM_EULER) v.push_back("EULER_NUMBER");
+    if (mask & NYXHIP_FAM_ROI_RADIUS) { v.push_back("ROI_RADIUS_MEAN"); v.push_back("ROI_RADIUS_MAX"); v.push_back("ROI_RADIUS_MEDIAN"); }
     if (mask & NYXHIP_FAM_GLCM) {
         for (auto n : kGlcmNames)
             for (int a = 0; a < s->glcm_n_angles; a++)
@@ -182,6 +186,9 @@ int nyxhip_n_columns(uint32_t family_mask, const nyxhip_settings* s)
     if (!s) return 0;
     int n = 0;
     if (family_mask & NYXHIP_FAM_INTENSITY) n += kIntensityCols;
+    if (family_mask & NYXHIP_FAM_FRACTAL) n += kFractalCols;
+    if (family_mask & NYXHIP_FAM_EULER) n += kEulerCols;
+    if (family_mask & NYXHIP_FAM_ROI_RADIUS) n += kRoiRadiusCols;
     if (family_mask & NYXHIP_FAM_GLCM) n += kGlcmAngled * s->glcm_n_angles + kGlcmAve;
     if (family_mask & NYXHIP_FAM_GLRLM) n += kGlrlmCols;
     if (family_mask & NYXHIP_FAM_GLDZM) n += kGldzmCols;

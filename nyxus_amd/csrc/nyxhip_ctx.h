@@ -20,6 +20,7 @@
 #include "../../include/nyxhip.h"
 #include "roi_kernel.h"
 #include "roi_radial.h"
+#include "roi_outline.h"
 
 // One hipMalloc allocation, grow-only.  hipFree waits for the device's work by itself; the stream handed to reserve() states which
 // work the site knows to be using the old block.
@@ -139,6 +140,9 @@ struct nyxhip_ctx {
     // contour planes beyond LDS: index list (launch_contour_families); per-workgroup global scratch of every workspace launch
     DevBuf d_spill_list;
     DevBuf d_spill;
+    // outline kernel (roi_outline.hip): list of the ROIs whose bit planes exceed LDS, and their global bit planes
+    DevBuf d_outline_list;
+    DevBuf d_outline_bits;
     // grow-only workspaces of the fused tile path: scan tables + rows | clouds | two staging slots for host tiles
     DevBuf d_tile;
     DevBuf d_cloud;
@@ -196,8 +200,11 @@ constexpr uint32_t kTexture = NYXHIP_FAM_GLRLM | NYXHIP_FAM_GLSZM | NYXHIP_FAM_N
 constexpr uint32_t kShape = NYXHIP_FAM_GABOR | NYXHIP_FAM_ZERNIKE;
 constexpr uint32_t kDependence = NYXHIP_FAM_GLDZM | NYXHIP_FAM_GLDM | NYXHIP_FAM_NGLDM;
 constexpr uint32_t kMoments = NYXHIP_FAM_SMOMS | NYXHIP_FAM_IMOMS;
-constexpr uint32_t kContourFams = kMoments | NYXHIP_FAM_RADIAL;   // families that read the ROI's ordered contour (launch_contour_families)
-constexpr uint32_t kImplemented = NYXHIP_FAM_INTENSITY | NYXHIP_FAM_GLCM | kTexture | kShape | kDependence | kMoments | NYXHIP_FAM_RADIAL;
+constexpr uint32_t kOutline = NYXHIP_FAM_FRACTAL | NYXHIP_FAM_EULER | NYXHIP_FAM_ROI_RADIUS;   // roi_outline.hip; their columns follow the intensity block
+// families that read the ROI's ordered contour (launch_contour_families)
+constexpr uint32_t kContourFams = kMoments | NYXHIP_FAM_RADIAL | NYXHIP_FAM_FRACTAL | NYXHIP_FAM_ROI_RADIUS;
+constexpr uint32_t kTailFams = kContourFams | NYXHIP_FAM_EULER;   // ... and everything else launch_contour_families serves (no size classes)
+constexpr uint32_t kImplemented = NYXHIP_FAM_INTENSITY | NYXHIP_FAM_GLCM | kTexture | kShape | kDependence | kMoments | NYXHIP_FAM_RADIAL | kOutline;
 
 namespace nyxhip __attribute__((visibility("hidden"))) {
 

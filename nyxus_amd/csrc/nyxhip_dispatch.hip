@@ -325,7 +325,13 @@ int build_args(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t mask, const nyxh
                const Extrema& E, size_t cap, RoiArgs& a, TexArgs& t, ShapeArgs& g, DepArgs& d, std::string& why, uint32_t groups = 0xF)
 {   // groups: bit 0 features (INTENSITY + GLCM), 1 texture, 2 shape, 3 dependence -- the kernel groups to build (columns always follow `mask`)
     const uint32_t mask1 = mask & (NYXHIP_FAM_INTENSITY | NYXHIP_FAM_GLCM), mask2 = mask & kTexture, mask3 = mask & kShape, mask4 = mask & kDependence;
-    const int n_cols1 = nyxhip_n_columns(mask1, s), n_cols2 = nyxhip_n_columns(mask2, s), n_cols4 = nyxhip_n_columns(mask4, s);
+    const int n_cols2 = nyxhip_n_columns(mask2, s), n_cols4 = nyxhip_n_columns(mask4, s);
+    // The outline families (roi_outline.hip) sit between the intensity block and GLCM: every base behind the intensity block moves by
+    // their columns.  n_cols1: where the INTENSITY + GLCM span ends.  The feature kernels zero and fill one span of columns from
+    // column 0, so a launch with GLCM covers the outline columns as well (launch_device_all enqueues the outline kernel behind it).
+    const int outline_cols = nyxhip_n_columns(mask & kOutline, s);
+    const int n_cols1 = nyxhip_n_columns(mask1, s) + outline_cols;
+    const int n_cols_feat = (mask1 & NYXHIP_FAM_GLCM) ? n_cols1 : n_cols1 - outline_cols;   // columns the feature kernel owns
     memset(&a, 0, sizeof(a));
     memset(&t, 0, sizeof(t));
     memset(&g, 0, sizeof(g));
@@ -335,7 +341,7 @@ int build_args(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t mask, const nyxh
     int c_glszm = c_gldzm + ((mask & NYXHIP_FAM_GLDZM) ? kGldzmCols : 0), c_gldm = c_glszm + ((mask & NYXHIP_FAM_GLSZM) ? kGlszmCols : 0);
     int c_ngldm = c_gldm + ((mask & NYXHIP_FAM_GLDM) ? kGldmCols : 0);
     if (mask1 && (groups & 1)) {
-        if (int lrc = make_layout(mask1, s, n_cols1, E.px, E.area, E.range, a.L, why, cap, E.vmax, E.wide_only))
+        if (int lrc = make_layout(mask1, s, n_cols_feat, E.px, E.area, E.range, a.L, why, cap, E.vmax, E.wide_only))
             return lrc;
         a.n_roi = b->n_roi;
         a.px_offset = b->px_offset; a.x = b->x; a.y = b->y; a.inten = b->inten;
@@ -344,10 +350,11 @@ int build_args(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t mask, const nyxh
         a.out = d_out; a.ld = ld; a.status = ctx->d_status.as<int>();
         a.stamps = ctx->d_stamps.as<unsigned long long>();
         if (cap == 0) a.win = ctx->win_next;   // LDS launches only (the tile path asks for windows only when everything fits LDS)
-        a.mask = mask1; a.n_cols = n_cols1;
+        a.mask = mask1; a.n_cols = n_cols_feat;
         int c = 0;
         a.col_intensity = a.col_glcm = -1;
         if (mask1 & NYXHIP_FAM_INTENSITY) { a.col_intensity = c; c += kIntensityCols; }
+        c += outline_cols;
         if (mask1 & NYXHIP_FAM_GLCM) { a.col_glcm = c; c += kGlcmAngled * s->glcm_n_angles + kGlcmAve; }
         a.soft_nan = s->soft_nan;
         a.grey_depth = s->grey_depth; a.ibsi = s->ibsi; a.glcm_grey_depth = s->glcm_grey_depth;
@@ -454,16 +461,77 @@ int use_lane(nyxhip_ctx* ctx, int lane, hipStream_t* st)
 // distribution (roi_radial.hip).  The contour of every ROI goes to a context-owned workspace at the ROI's CSR offset (a contour
 // never has more points than the ROI has pixels) ONCE per call; the moments kernel and / or the radial kernel read it back.
 // (The workspace keeps its per-pixel double plane for a radial-only call too: the contour kernel's walk stack lives there.)
+// The outline kernel (roi_outline.hip) is the third reader; a mask that holds none of the contour families (EULER_NUMBER alone) skips
+// the contour chain and launches it by itself.  allow_lane = false: everything stays on the call's stream (the caller has joined the
+// lanes: the feature kernels of a GLCM launch zero the outline columns, so the outline kernel must follow all of them).
 int launch_contour_families(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t mask, const nyxhip_settings* s, double* d_out, size_t ld,
-                   uint32_t max_px, uint32_t max_area, uint32_t max_side)
+                   uint32_t max_px, uint32_t max_area, uint32_t max_side, bool allow_lane)
 {
     hipStream_t st = ctx->stream();
+    const bool do_out = (mask & kOutline) != 0, need_contour = (mask & kContourFams) != 0;
+    OutArgs oa;
+    memset(&oa, 0, sizeof(oa));
+    bool out_deferred = false;                             // some ROI's bit planes may exceed LDS: a list launch follows the readers
+    if (do_out) {
+        oa.fams = mask & kOutline;
+        oa.has_contour = need_contour ? 1u : 0u;
+        oa.col_fractal = nyxhip_n_columns(mask & NYXHIP_FAM_INTENSITY, s);
+        oa.col_euler = oa.col_fractal + ((mask & NYXHIP_FAM_FRACTAL) ? kFractalCols : 0);
+        oa.col_radius = oa.col_euler + ((mask & NYXHIP_FAM_EULER) ? kEulerCols : 0);
+        if (mask & (NYXHIP_FAM_FRACTAL | NYXHIP_FAM_EULER)) {
+            // bound of outline_bit_words over boxes of at most max_area cells and max_side a side: rows of w / 32 + 1 words, the pyramid
+            // at most as much again plus a word and a row per level
+            const uint64_t bound = 2ull * ((uint64_t)max_area / 32u + max_side) + 2ull * max_side + 64u;
+            oa.bits_cap = (uint32_t)std::min<uint64_t>(kOutlineBitsLds, bound);
+            out_deferred = bound > kOutlineBitsLds;
+            oa.defer_bits = out_deferred ? 1u : 0u;
+        }
+    }
+    // the ROIs the outline launches deferred, from global bit planes: on `s_`, behind everything that wrote their contours
+    auto launch_outline_deferred = [&](hipStream_t s_) -> int {
+        if (!out_deferred) return NYXHIP_OK;
+        const size_t list_bytes = 4ull * b->n_roi + 512;
+        HIP_TRY(ctx, ctx->d_outline_list.reserve(list_bytes, s_));
+        uint32_t* d_cnt = ctx->d_outline_list.as<uint32_t>();
+        uint32_t* d_list = d_cnt + 64;
+        HIP_TRY(ctx, hipMemsetAsync(d_cnt, 0, 4, s_));
+        const uint32_t pyramid = (mask & NYXHIP_FAM_FRACTAL) ? 1u : 0u;
+        if (launch_outline_classify(b->n_roi, b->bbox_w, b->bbox_h, pyramid, oa.bits_cap, d_list, d_cnt, s_) != 0)
+            return fail(ctx, NYXHIP_ERR_HIP, "outline classifier: launch failed");
+        uint32_t n_big = 0;
+        HIP_TRY(ctx, hipMemcpyAsync(&n_big, d_cnt, 4, hipMemcpyDeviceToHost, s_));
+        HIP_TRY(ctx, hipStreamSynchronize(s_));
+        if (!n_big) return NYXHIP_OK;
+        const uint32_t sd = std::min<uint32_t>(max_side, 65535u);
+        const uint64_t stride = (std::min<uint64_t>(2ull * ((uint64_t)max_area / 32u + max_side) + 2ull * max_side + 64u, outline_bit_words(sd, sd, pyramid != 0)) + 63) & ~63ull;
+        const uint32_t chunk = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(n_big, ((uint64_t)1 << 30) / (4 * stride)));
+        HIP_TRY(ctx, ctx->d_outline_bits.reserve((size_t)(4 * stride * chunk), s_));
+        OutArgs ob = oa;
+        ob.defer_bits = 0; ob.bits_ws = ctx->d_outline_bits.as<uint32_t>(); ob.bits_stride = stride;
+        ob.m.sp.defer_large = 0;
+        for (uint32_t o = 0; o < n_big; o += chunk) {
+            ob.m.sp.roi_index = d_list + o;
+            if (launch_roi_outline(ob, s_, std::min(chunk, n_big - o)) != 0)
+                return fail(ctx, NYXHIP_ERR_HIP, "outline kernel: launch failed");
+        }
+        return NYXHIP_OK;
+    };
+    if (!need_contour) {
+        // EULER_NUMBER alone: no contour, no staged pixels -- the bit plane only
+        MomArgs& m = oa.m;
+        m.n_roi = b->n_roi;
+        m.px_offset = b->px_offset; m.x = b->x; m.y = b->y; m.inten = b->inten; m.bbox_w = b->bbox_w; m.bbox_h = b->bbox_h;
+        m.out = d_out; m.ld = ld; m.status = ctx->d_status.as<int>();
+        if (launch_roi_outline(oa, st, (uint32_t)b->n_roi) != 0)
+            return fail(ctx, NYXHIP_ERR_HIP, "outline kernel: launch failed");
+        return launch_outline_deferred(st);
+    }
     // A batch with boxes beyond the LDS plane sends those to a wave per ROI over a global workspace (a few hundred waves, ~10 ms of
     // latency for the heavy-tailed batch): with other families in the call the whole moments chain goes to a lane of its own and
     // runs beside them (enqueued last, dependent only on the batch).  Its scratch is the lane's, not the main stream's.
     static const bool no_mom_lane = [] { const char* e = getenv("NYXHIP_NO_MOM_LANE"); return e && *e && *e != '0'; }();   // A/B knob
     const bool big_boxes = (uint64_t)kContourWaves * (((uint64_t)max_area + 4ull * max_side + 4 + 15) & ~15ull) > (uint64_t)roi_features_max_lds();
-    const bool on_lane = !no_mom_lane && big_boxes && (mask & ~kContourFams) && ctx->lane_fork;
+    const bool on_lane = allow_lane && !no_mom_lane && big_boxes && (mask & ~kTailFams) && ctx->lane_fork;
     if (on_lane)
         if (int lrc = use_lane(ctx, nyxhip_ctx::kMomLane, &st)) return lrc;
     DevBuf& spill = on_lane ? ctx->lane_buf[nyxhip_ctx::kMomLane] : ctx->d_spill;
@@ -500,7 +568,7 @@ int launch_contour_families(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t mas
     memset(&ra, 0, sizeof(ra));
     if (do_rad) {
         // columns: FRAC_AT_D | GABOR | MEAN_FRAC | RADIAL_CV (enum order)
-        const uint32_t before = NYXHIP_FAM_INTENSITY | NYXHIP_FAM_GLCM | kTexture | kDependence;
+        const uint32_t before = NYXHIP_FAM_INTENSITY | kOutline | NYXHIP_FAM_GLCM | kTexture | kDependence;
         ra.col_frac = nyxhip_n_columns(mask & before, s);
         ra.col_mean = ra.col_frac + kRadialBins + ((mask & NYXHIP_FAM_GABOR) ? s->gabor_n_filters : 0);
         ra.col_cv = ra.col_mean + kRadialBins;
@@ -523,12 +591,17 @@ int launch_contour_families(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t mas
             ra.m = mm;
             r = launch_roi_radial(ra, s_, g);
         }
+        if (r == 0 && do_out) {
+            oa.m = mm;
+            r = launch_roi_outline(oa, s_, g);
+        }
         return r;
     };
     const uint64_t full_plane = (uint64_t)max_area + 4ull * max_side + 4;      // (w + 2)(h + 2) <= area + 2(w + h) + 4
     const uint32_t grid = (uint32_t)b->n_roi;
     const uint32_t lds_cap = (uint32_t)roi_features_max_lds();
     int rc;
+    hipStream_t st_join = nullptr;                         // the big boxes' stream when it is not `st`
     if ((uint64_t)kContourWaves * ((full_plane + 15) & ~15ull) <= lds_cap) {   // kContourWaves planes per workgroup
         m.plane_cap = (uint32_t)full_plane;
         rc = launch_roi_contour(m, st, grid);
@@ -542,6 +615,7 @@ int launch_contour_families(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t mas
         hipStream_t st_big = st;
         if (on_lane)
             if (int lrc = use_lane(ctx, nyxhip_ctx::kMomLaneBig, &st_big)) return lrc;
+        if (st_big != st) st_join = st_big;
         const size_t list_bytes = 4ull * b->n_roi + 256;
         HIP_TRY(ctx, ctx->d_spill_list.reserve(list_bytes, st_big));
         uint32_t* d_cnt = ctx->d_spill_list.as<uint32_t>();
@@ -580,7 +654,15 @@ int launch_contour_families(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t mas
         }
     }
     if (rc != 0)
-        return fail(ctx, NYXHIP_ERR_HIP, std::string("contour / moments / radial kernel launch failed: ") + hipGetErrorString((hipError_t)rc));
+        return fail(ctx, NYXHIP_ERR_HIP, std::string("contour / moments / radial / outline kernel launch failed: ") + hipGetErrorString((hipError_t)rc));
+    if (out_deferred) {
+        if (st_join) {                                     // the deferred ROIs' contours may come from the big boxes' lane
+            HIP_TRY(ctx, hipEventRecord(ctx->lane_done[nyxhip_ctx::kMomLaneBig], st_join));
+            HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->lane_done[nyxhip_ctx::kMomLaneBig], 0));
+        }
+        oa.m = m;
+        return launch_outline_deferred(st);
+    }
     return NYXHIP_OK;
 }
 
@@ -702,9 +784,10 @@ static int run_large(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t mask, cons
     a.bbox_w = b->bbox_w; a.bbox_h = b->bbox_h; a.min_inten = b->min_inten; a.max_inten = b->max_inten;
     a.slide_min = b->slide_min; a.slide_max = b->slide_max;
     a.out = d_out; a.ld = ld; a.status = ctx->d_status.as<int>();
-    a.mask = mask1; a.n_cols = nyxhip_n_columns(mask1, s);
+    const int outline_cols = nyxhip_n_columns(mask & kOutline, s);   // between the intensity block and GLCM (build_args)
+    a.mask = mask1; a.n_cols = nyxhip_n_columns(mask1, s) + ((mask1 & NYXHIP_FAM_GLCM) ? outline_cols : 0);
     a.col_intensity = (mask1 & NYXHIP_FAM_INTENSITY) ? 0 : -1;
-    a.col_glcm = (mask1 & NYXHIP_FAM_GLCM) ? ((mask1 & NYXHIP_FAM_INTENSITY) ? kIntensityCols : 0) : -1;
+    a.col_glcm = (mask1 & NYXHIP_FAM_GLCM) ? ((mask1 & NYXHIP_FAM_INTENSITY) ? kIntensityCols : 0) + outline_cols : -1;
     a.soft_nan = s->soft_nan;
     a.grey_depth = s->grey_depth; a.ibsi = s->ibsi; a.glcm_grey_depth = s->glcm_grey_depth;
     a.glcm_offset = s->glcm_offset; a.glcm_na = s->glcm_n_angles; a.glcm_symmetric = s->glcm_symmetric;
@@ -844,7 +927,7 @@ static int run_large_tex(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t full, 
     a.bbox_w = b->bbox_w; a.bbox_h = b->bbox_h; a.min_inten = b->min_inten; a.max_inten = b->max_inten;
     a.out = d_out; a.ld = ld; a.status = ctx->d_status.as<int>();
     a.mask = mask2; a.n_cols = nyxhip_n_columns(mask2, s);
-    a.col0 = nyxhip_n_columns(full & (NYXHIP_FAM_INTENSITY | NYXHIP_FAM_GLCM), s);
+    a.col0 = nyxhip_n_columns(full & (NYXHIP_FAM_INTENSITY | NYXHIP_FAM_GLCM | kOutline), s);
     a.gap_after_glrlm = (full & NYXHIP_FAM_GLDZM) ? kGldzmCols : 0;
     a.gap_after_glszm = ((full & NYXHIP_FAM_GLDM) ? kGldmCols : 0) + ((full & NYXHIP_FAM_NGLDM) ? kNgldmCols : 0);
     a.soft_nan = s->soft_nan; a.grey_depth = s->grey_depth; a.ibsi = s->ibsi;
@@ -1058,11 +1141,11 @@ int run_class(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t mask, const nyxhi
             if ((a.mask & both) == both && a.L.g16 && !getenv("NYXHIP_G16_FUSED")) {
                 RoiArgs ai = a, ag = a;
                 std::string w2;
-                const int ncol_g = a.n_cols - kIntensityCols;
+                const int ncol_g = a.n_cols - a.col_glcm;              // (col_glcm: behind the intensity block and the outline columns)
                 if (make_layout(NYXHIP_FAM_INTENSITY, s, kIntensityCols, E.px, E.area, E.range, ai.L, w2) == NYXHIP_OK &&
                     make_layout(NYXHIP_FAM_GLCM, s, ncol_g, E.px, E.area, E.range, ag.L, w2) == NYXHIP_OK && ag.L.g16) {
                     ai.mask = NYXHIP_FAM_INTENSITY; ai.n_cols = kIntensityCols; ai.col_intensity = 0; ai.col_glcm = -1;
-                    ag.mask = NYXHIP_FAM_GLCM; ag.n_cols = ncol_g; ag.col_glcm = 0; ag.col_intensity = -1; ag.out = a.out + kIntensityCols;
+                    ag.mask = NYXHIP_FAM_GLCM; ag.n_cols = ncol_g; ag.col_glcm = 0; ag.col_intensity = -1; ag.out = a.out + a.col_glcm;
                     ag.census = nullptr;                               // (the intensity launch counts)
                     if (int r1 = launch_roi_features(ag, st, grid)) return r1;
                     return launch_roi_features(ai, st, grid);
@@ -1086,9 +1169,9 @@ int run_class(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t mask, const nyxhi
             const bool with_glcm = (a.mask & NYXHIP_FAM_GLCM) != 0;
             if (with_glcm) {
                 std::string w2;
-                const int ncol_g = a.n_cols - kIntensityCols;
+                const int ncol_g = a.n_cols - a.col_glcm;
                 if (make_layout(NYXHIP_FAM_GLCM, s, ncol_g, E.px, E.area, std::min(E.range, 0xFFFFu), ag.L, w2, 0, E.vmax) != NYXHIP_OK) return 0;
-                ag.mask = NYXHIP_FAM_GLCM; ag.n_cols = ncol_g; ag.col_glcm = 0; ag.col_intensity = -1; ag.out = a.out + kIntensityCols;
+                ag.mask = NYXHIP_FAM_GLCM; ag.n_cols = ncol_g; ag.col_glcm = 0; ag.col_intensity = -1; ag.out = a.out + a.col_glcm;
                 if (a.glcm_ws && ag.L.ng_cap != a.L.ng_cap) return 0;          // (the count workspace was sized for the fused layout)
             }
             if (!b->inten) return NYXHIP_INTERNAL_NEEDS_CLOUDS;               // window-mode chunk: this kernel reads the clouds
@@ -1260,7 +1343,7 @@ int launch_device_all(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t mask, con
     HIP_TRY(ctx, hipEventRecord(ctx->lane_fork, st));
     struct LaneJoin {
         nyxhip_ctx* c; hipStream_t st;
-        ~LaneJoin() {
+        void join() {
             for (int k = 0; k < nyxhip_ctx::kLanes; k++)
                 if (c->lane_used[k]) {
                     (void)hipEventRecord(c->lane_done[k], c->lane_stream[k]);
@@ -1268,6 +1351,7 @@ int launch_device_all(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t mask, con
                     c->lane_used[k] = false;
                 }
         }
+        ~LaneJoin() { join(); }
     } lane_join{ctx, st};
     if (mask & NYXHIP_FAM_GLCM) {
         // matrix orders of the split GLCM launches (RoiArgs::glcm_ng).  A table of its own: the count workspace may be re-allocated
@@ -1299,7 +1383,7 @@ int launch_device_all(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t mask, con
         ctx->runs.push_back(r);
         return rc;
     };
-    if ((mask & ~kContourFams) || !hinted) {               // (a batch without stated extrema gets them from the class headers)
+    if ((mask & ~kTailFams) || !hinted) {               // (a batch without stated extrema gets them from the class headers)
         bool done = false;
         static const bool force_exact = [] { const char* e = getenv("NYXHIP_CLASS_SYNC"); return e && *e && *e != '0'; }();   // A/B knob
         // (IBSI co-occurrence matrices are as large as the largest intensity, which a statement about the batch does not carry)
@@ -1384,7 +1468,7 @@ int launch_device_all(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t mask, con
             // A window-mode chunk (no clouds materialised) with a class that reads clouds -- the classes beyond LDS, and the wide-range
             // classes the bitmap kernel serves -- goes back for them BEFORE anything is launched: raised from inside the class loop it
             // made the caller run the whole chunk again, every LDS class computed twice (16-bit tiles: on every chunk).
-            if (ctx->win_next.inten && !b->inten && (mask & ~kContourFams)) {
+            if (ctx->win_next.inten && !b->inten && (mask & ~kTailFams)) {
                 static const bool no_wide_pre = [] { const char* e = getenv("NYXHIP_NO_WIDE"); return e && *e && *e != '0'; }();
                 for (int cls = 0; cls < kClasses; cls++) {
                     if (H[cls * H_WORDS + H_COUNT] == 0) continue;
@@ -1394,7 +1478,7 @@ int launch_device_all(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t mask, con
             }
             static const bool no_merge = [] { const char* e = getenv("NYXHIP_NO_MERGE_LARGE"); return e && *e && *e != '0'; }();   // A/B knob
             int first_cls = kClasses - 1;
-            if (!no_merge && (mask & ~kContourFams)) {
+            if (!no_merge && (mask & ~kTailFams)) {
                 uint32_t cnt = 0; int top = -1;
                 Extrema Em{0, 0, 0, 0, 0, false};
                 ClassTotals tm{0, 0, 0};
@@ -1412,7 +1496,7 @@ int launch_device_all(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t mask, con
                         return rc;
                 first_cls = 2 * kFirstLargeSizeClass - 1;
             }
-            for (int cls = first_cls; cls >= 0 && (mask & ~kContourFams); cls--) {   // largest ROIs first: their long workgroups start early
+            for (int cls = first_cls; cls >= 0 && (mask & ~kTailFams); cls--) {   // largest ROIs first: their long workgroups start early
                 const uint32_t* h = H + cls * H_WORDS;
                 if (h[H_COUNT] == 0) continue;
                 const Extrema E{h[H_PX], h[H_AREA], h[H_RANGE], h[H_SIDE], h[H_VMAX], (cls & 1) != 0 && cls / 2 < kSizeClasses - 1};
@@ -1423,9 +1507,14 @@ int launch_device_all(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t mask, con
             }
         }
     }
-    if (mask & kContourFams)
-        if (int mrc = launch_contour_families(ctx, b, mask, s, d_out, ld, max_px, max_area, max_side))
+    if (mask & kTailFams) {
+        // A feature launch with GLCM zeroes and fills its columns from column 0, across the outline columns: the outline kernel goes
+        // behind every feature launch of the call -- the lanes join here and the contour chain stays on the call's stream.
+        const bool after_all = (mask & kOutline) && (mask & NYXHIP_FAM_GLCM);
+        if (after_all) lane_join.join();
+        if (int mrc = launch_contour_families(ctx, b, mask, s, d_out, ld, max_px, max_area, max_side, !after_all))
             return mrc;
+    }
     return NYXHIP_OK;
 }
 
@@ -1680,7 +1769,7 @@ int validate(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t mask, const nyxhip
 {
     if (!ctx) return NYXHIP_ERR_INVALID_ARG;
     if (!b || !s || !out) return fail(ctx, NYXHIP_ERR_INVALID_ARG, "null batch / settings / out_table");
-    if (mask == 0 || (mask & ~(NYXHIP_FAM_ALL | NYXHIP_FAM_RADIAL))) return fail(ctx, NYXHIP_ERR_INVALID_ARG, "bad family mask");
+    if (mask == 0 || (mask & ~(NYXHIP_FAM_ALL | NYXHIP_FAM_RADIAL | kOutline))) return fail(ctx, NYXHIP_ERR_INVALID_ARG, "bad family mask");
     if (mask & ~kImplemented)
         return fail(ctx, NYXHIP_ERR_UNSUPPORTED, "requested feature family is not implemented by the HIP path yet "
                     "(all seven hot-path families are implemented; bad mask?)");

@@ -85,6 +85,16 @@ RADIAL_BINS = 8
 for _n in RADIAL:
     FAMILY_OF[_n] = _abi.FAM_RADIAL
 FAMILY_OF["ZERNIKE2D"] = _abi.FAM_ZERNIKE
+# three classes of the shape block (featureset.h:46-160): one column per code, between the intensity block and GLCM_ASM
+FRACTAL = ["FRACT_DIM_BOXCOUNT", "FRACT_DIM_PERIMETER"]
+EULER = ["EULER_NUMBER"]
+ROI_RADIUS = ["ROI_RADIUS_MEAN", "ROI_RADIUS_MAX", "ROI_RADIUS_MEDIAN"]
+for _n in FRACTAL:
+    FAMILY_OF[_n] = _abi.FAM_FRACTAL
+for _n in EULER:
+    FAMILY_OF[_n] = _abi.FAM_EULER
+for _n in ROI_RADIUS:
+    FAMILY_OF[_n] = _abi.FAM_ROI_RADIUS
 
 # group tokens (featureset.cpp:650-665) the HIP path can serve completely (the radial distribution has none, featureset.cpp:650-668)
 GROUPS: Dict[str, List[str]] = {
@@ -104,6 +114,9 @@ GROUPS: Dict[str, List[str]] = {
 # enum order of every feature code the path covers (one entry per Feature2D code)
 ENUM_ORDER: List[str] = (INTENSITY + GLCM_ANGLED + GLCM_AVE + GLRLM_ANGLED + GLRLM_AVE + GLDZM + GLSZM + GLDM + NGLDM + NGTDM
                          + ["FRAC_AT_D", "GABOR", "MEAN_FRAC", "RADIAL_CV", "ZERNIKE2D"] + SMOMS + IMOMS)   # featureset.h:352-357
+# ... and the order expand() returns codes in: ENUM_ORDER with the shape-block codes at their enum position (ENUM_ORDER itself
+# keeps the codes of the twelve FAM_ALL families and the radial distribution)
+OUTPUT_ORDER: List[str] = INTENSITY + FRACTAL + EULER + ROI_RADIUS + ENUM_ORDER[len(INTENSITY):]
 
 
 def expand(features: List[str]) -> Tuple[int, List[str]]:
@@ -122,10 +135,11 @@ def expand(features: List[str]) -> Tuple[int, List[str]]:
         raise ValueError(
             f"feature(s) {unknown} are not served by the MI355X path. Implemented: groups {sorted(GROUPS)} and the "
             f"individual features of the intensity, GLCM, GLRLM, GLDZM, GLSZM, GLDM, NGLDM and NGTDM families, GABOR, ZERNIKE2D, "
-            f"FRAC_AT_D, MEAN_FRAC, RADIAL_CV")
+            f"FRAC_AT_D, MEAN_FRAC, RADIAL_CV, FRACT_DIM_BOXCOUNT, FRACT_DIM_PERIMETER, EULER_NUMBER, ROI_RADIUS_MEAN, ROI_RADIUS_MAX, "
+            f"ROI_RADIUS_MEDIAN")
     if not want:
         raise ValueError("no features requested")
-    ordered = [n for n in ENUM_ORDER if n in want]
+    ordered = [n for n in OUTPUT_ORDER if n in want]
     mask = 0
     for n in ordered:
         mask |= FAMILY_OF[n]
