@@ -71,6 +71,15 @@ enum {
     NYXHIP_FAM_FRACTAL   = 1u << 15, /* FractalDimensionFeature, 2 columns: FRACT_DIM_BOXCOUNT, FRACT_DIM_PERIMETER (features/fractal_dim.h) */
     NYXHIP_FAM_EULER     = 1u << 16, /* EulerNumberFeature, 1 column: EULER_NUMBER, mode 8 (features/euler_number.h)                        */
     NYXHIP_FAM_ROI_RADIUS = 1u << 17, /* RoiRadiusFeature, 3 columns: ROI_RADIUS_MEAN, ROI_RADIUS_MAX, ROI_RADIUS_MEDIAN (features/roi_radius.h) */
+    /* the three caliper classes (featureset.h:93-114, features/caliper.h): statistics of diameters of the convex hull turned in steps of
+     * 10 degrees.  Not part of NYXHIP_FAM_ALL.  Their columns sit between FRACT_DIM_PERIMETER and EULER_NUMBER (enum order).  These are the
+     * only bits that read the ROI origin of nyxhip_featurize_batch_at(): the reference stores every rotated hull vertex as `float`
+     * (features/rotation.cpp:37-68), so its values depend on where the ROI lies in its image.  Through the entries without an origin
+     * the rows are those of an ROI whose bounding box starts at (0, 0).  An ROI of fewer than 2 pixels has no hull: all columns of
+     * the requested classes are settings.soft_nan (caliper_feret.cpp:19-32). */
+    NYXHIP_FAM_FERET     = 1u << 18, /* CaliperFeretFeature, 8 columns: MIN_FERET_ANGLE, MAX_FERET_ANGLE, STAT_FERET_DIAM_{MIN,MAX,MEAN,MEDIAN,STDDEV,MODE} */
+    NYXHIP_FAM_MARTIN    = 1u << 19, /* CaliperMartinFeature, 6 columns: STAT_MARTIN_DIAM_{MIN,MAX,MEAN,MEDIAN,STDDEV,MODE}                                */
+    NYXHIP_FAM_NASSENSTEIN = 1u << 20, /* CaliperNassensteinFeature, 6 columns: STAT_NASSENSTEIN_DIAM_{MIN,MAX,MEAN,MEDIAN,STDDEV,MODE}                    */
     NYXHIP_FAM_NORTH_STAR = 0x7Fu,  /* the seven families of BASELINE.json's north_star */
     NYXHIP_FAM_ALL       = 0xFFFu
 };
@@ -208,6 +217,14 @@ int nyxhip_featurize_batch_async(nyxhip_ctx* ctx, const nyxhip_batch* batch,
                                  uint32_t family_mask, const nyxhip_settings* s,
                                  double* out_table, size_t out_ld);
 int nyxhip_sync(nyxhip_ctx* ctx);
+
+/* The two calls above with the ROIs' positions: origin_x[r] / origin_y[r] = aabb.xmin / aabb.ymin of ROI r in its image ([n_roi],
+ * in the memory of the batch's other pointers, batch->memory).  Both NULL = every origin (0, 0): exactly nyxhip_featurize_batch
+ * [_async].  Only NYXHIP_FAM_FERET / _MARTIN / _NASSENSTEIN read the origin; every other column is the same with and without it. */
+int nyxhip_featurize_batch_at(nyxhip_ctx* ctx, const nyxhip_batch* batch, const uint32_t* origin_x, const uint32_t* origin_y,
+                              uint32_t family_mask, const nyxhip_settings* s, double* out_table, size_t out_ld);
+int nyxhip_featurize_batch_async_at(nyxhip_ctx* ctx, const nyxhip_batch* batch, const uint32_t* origin_x, const uint32_t* origin_y,
+                                    uint32_t family_mask, const nyxhip_settings* s, double* out_table, size_t out_ld);
 
 /* Host-side NaN/inf -> soft_nan replacement over a host table, as
  * save_features_2_buffer does per value (output_2_buffer.cpp:296,...). */

@@ -39,7 +39,13 @@ enum class Feature2D : int {
     ROBUST_MEAN_ABSOLUTE_DEVIATION, ROOT_MEAN_SQUARED, SKEWNESS, STANDARD_DEVIATION, STANDARD_DEVIATION_BIASED,
     STANDARD_ERROR, VARIANCE, VARIANCE_BIASED, UNIFORMITY, UNIFORMITY_PIU,
     // three classes of the shape block (featureset.h:46-160), in enum position: between the intensity block and GLCM
-    FRACT_DIM_BOXCOUNT, FRACT_DIM_PERIMETER, EULER_NUMBER, ROI_RADIUS_MEAN, ROI_RADIUS_MAX, ROI_RADIUS_MEDIAN,
+    FRACT_DIM_BOXCOUNT, FRACT_DIM_PERIMETER,
+    // the caliper classes (featureset.h:93-114)
+    MIN_FERET_ANGLE, MAX_FERET_ANGLE, STAT_FERET_DIAM_MIN, STAT_FERET_DIAM_MAX, STAT_FERET_DIAM_MEAN, STAT_FERET_DIAM_MEDIAN, STAT_FERET_DIAM_STDDEV,
+    STAT_FERET_DIAM_MODE, STAT_MARTIN_DIAM_MIN, STAT_MARTIN_DIAM_MAX, STAT_MARTIN_DIAM_MEAN, STAT_MARTIN_DIAM_MEDIAN, STAT_MARTIN_DIAM_STDDEV,
+    STAT_MARTIN_DIAM_MODE, STAT_NASSENSTEIN_DIAM_MIN, STAT_NASSENSTEIN_DIAM_MAX, STAT_NASSENSTEIN_DIAM_MEAN, STAT_NASSENSTEIN_DIAM_MEDIAN,
+    STAT_NASSENSTEIN_DIAM_STDDEV, STAT_NASSENSTEIN_DIAM_MODE,
+    EULER_NUMBER, ROI_RADIUS_MEAN, ROI_RADIUS_MAX, ROI_RADIUS_MEDIAN,
     GLCM_ASM, GLCM_ACOR, GLCM_CLUPROM, GLCM_CLUSHADE, GLCM_CLUTEND, GLCM_CONTRAST, GLCM_CORRELATION, GLCM_DIFAVE,
     GLCM_DIFENTRO, GLCM_DIFVAR, GLCM_DIS, GLCM_ENERGY, GLCM_ENTROPY, GLCM_HOM1, GLCM_HOM2, GLCM_ID, GLCM_IDN,
     GLCM_IDM, GLCM_IDMN, GLCM_INFOMEAS1, GLCM_INFOMEAS2, GLCM_IV, GLCM_JAVE, GLCM_JE, GLCM_JMAX, GLCM_JVAR,
@@ -213,7 +219,7 @@ inline void reduce_range(uint32_t mask, size_t start, size_t end, std::vector<in
     if (end <= start) return;
     nyxhip_settings s = make_settings(fst);
     const size_t n = end - start;
-    std::vector<uint32_t> lab(n), bw(n), bh(n), mn(n), mx(n), inten;
+    std::vector<uint32_t> lab(n), bw(n), bh(n), mn(n), mx(n), ox(n), oy(n), inten;
     std::vector<uint64_t> off(n + 1, 0);
     std::vector<uint16_t> x, y;
     std::vector<double> smin(n), smax(n);
@@ -222,6 +228,7 @@ inline void reduce_range(uint32_t mask, size_t start, size_t end, std::vector<in
         LR& r = (*roiData)[(*labels)[start + i]];
         lab[i] = (uint32_t)r.label; bw[i] = (uint32_t)r.aabb.get_width(); bh[i] = (uint32_t)r.aabb.get_height();
         mn[i] = r.aux_min; mx[i] = r.aux_max;
+        ox[i] = (uint32_t)r.aabb.get_xmin(); oy[i] = (uint32_t)r.aabb.get_ymin();   // the ROI's position (read by the caliper classes only)
         for (const Pixel2& p : r.raw_pixels) { x.push_back((uint16_t)(p.x - r.aabb.get_xmin())); y.push_back((uint16_t)(p.y - r.aabb.get_ymin())); inten.push_back(p.inten); }
         off[i + 1] = inten.size();
         if (r.slide_idx >= 0 && (size_t)r.slide_idx < ds.dataset_props.size()) { smin[i] = ds.dataset_props[r.slide_idx].min_preroi_inten; smax[i] = ds.dataset_props[r.slide_idx].max_preroi_inten; }
@@ -236,8 +243,8 @@ inline void reduce_range(uint32_t mask, size_t start, size_t end, std::vector<in
     const int ncol = nyxhip_n_columns(mask, &s);
     std::vector<double> table(n * (size_t)ncol);
     nyxhip_ctx* ctx = context();
-    if (nyxhip_featurize_batch(ctx, &b, mask, &s, table.data(), (size_t)ncol) != NYXHIP_OK)
-        throw std::runtime_error(std::string("nyxhip_featurize_batch: ") + nyxhip_last_error(ctx));
+    if (nyxhip_featurize_batch_at(ctx, &b, ox.data(), oy.data(), mask, &s, table.data(), (size_t)ncol) != NYXHIP_OK)
+        throw std::runtime_error(std::string("nyxhip_featurize_batch_at: ") + nyxhip_last_error(ctx));
     // table columns are Feature2D order with angle / index expansion (output_2_buffer.cpp:303-584)
     const int na = s.glcm_n_angles;
     for (size_t i = 0; i < n; i++) {
@@ -248,6 +255,9 @@ inline void reduce_range(uint32_t mask, size_t start, size_t end, std::vector<in
         };
         if (mask & NYXHIP_FAM_INTENSITY) put(Feature2D::COV, Feature2D::UNIFORMITY_PIU, 1);
         if (mask & NYXHIP_FAM_FRACTAL) put(Feature2D::FRACT_DIM_BOXCOUNT, Feature2D::FRACT_DIM_PERIMETER, 1);
+        if (mask & NYXHIP_FAM_FERET) put(Feature2D::MIN_FERET_ANGLE, Feature2D::STAT_FERET_DIAM_MODE, 1);
+        if (mask & NYXHIP_FAM_MARTIN) put(Feature2D::STAT_MARTIN_DIAM_MIN, Feature2D::STAT_MARTIN_DIAM_MODE, 1);
+        if (mask & NYXHIP_FAM_NASSENSTEIN) put(Feature2D::STAT_NASSENSTEIN_DIAM_MIN, Feature2D::STAT_NASSENSTEIN_DIAM_MODE, 1);
         if (mask & NYXHIP_FAM_EULER) put(Feature2D::EULER_NUMBER, Feature2D::EULER_NUMBER, 1);
         if (mask & NYXHIP_FAM_ROI_RADIUS) put(Feature2D::ROI_RADIUS_MEAN, Feature2D::ROI_RADIUS_MEDIAN, 1);
         if (mask & NYXHIP_FAM_GLCM) { put(Feature2D::GLCM_ASM, Feature2D::GLCM_VARIANCE, na); put(Feature2D::GLCM_ASM_AVE, Feature2D::GLCM_SUMVARIANCE_AVE, 1); }
@@ -330,6 +340,10 @@ NYXHIP_FAMILY_CLASS(Imoms2D_feature, NYXHIP_FAM_IMOMS, IMOM_RM_00, IMOM_WHU7)
 NYXHIP_FAMILY_CLASS(FractalDimensionFeature, NYXHIP_FAM_FRACTAL, FRACT_DIM_BOXCOUNT, FRACT_DIM_PERIMETER)
 NYXHIP_FAMILY_CLASS(EulerNumberFeature, NYXHIP_FAM_EULER, EULER_NUMBER, EULER_NUMBER)
 NYXHIP_FAMILY_CLASS(RoiRadiusFeature, NYXHIP_FAM_ROI_RADIUS, ROI_RADIUS_MEAN, ROI_RADIUS_MEDIAN)
+// features/caliper.h: the convex hull they depend on is built inside the call; they read LR::aabb's origin
+NYXHIP_FAMILY_CLASS(CaliperFeretFeature, NYXHIP_FAM_FERET, MIN_FERET_ANGLE, STAT_FERET_DIAM_MODE)
+NYXHIP_FAMILY_CLASS(CaliperMartinFeature, NYXHIP_FAM_MARTIN, STAT_MARTIN_DIAM_MIN, STAT_MARTIN_DIAM_MODE)
+NYXHIP_FAMILY_CLASS(CaliperNassensteinFeature, NYXHIP_FAM_NASSENSTEIN, STAT_NASSENSTEIN_DIAM_MIN, STAT_NASSENSTEIN_DIAM_MODE)
 
 // RadialDistributionFeature (features/radial_distribution.h): its three codes are not contiguous in the enum (GABOR sits
 // between FRAC_AT_D and MEAN_FRAC), so the class is spelled out.  The contour it depends on is built inside the call.
@@ -372,6 +386,9 @@ inline void reduce_trivial_rois_manual(std::vector<int>& PendingRoisLabels, std:
     uint32_t mask = 0;
     if (PixelIntensityFeatures::required(fs)) mask |= NYXHIP_FAM_INTENSITY;
     if (FractalDimensionFeature::required(fs)) mask |= NYXHIP_FAM_FRACTAL;
+    if (CaliperFeretFeature::required(fs)) mask |= NYXHIP_FAM_FERET;
+    if (CaliperMartinFeature::required(fs)) mask |= NYXHIP_FAM_MARTIN;
+    if (CaliperNassensteinFeature::required(fs)) mask |= NYXHIP_FAM_NASSENSTEIN;
     if (EulerNumberFeature::required(fs)) mask |= NYXHIP_FAM_EULER;
     if (RoiRadiusFeature::required(fs)) mask |= NYXHIP_FAM_ROI_RADIUS;
     if (GLCMFeature::required(fs)) mask |= NYXHIP_FAM_GLCM;

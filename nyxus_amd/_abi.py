@@ -33,6 +33,12 @@ FAM_RADIAL = 1 << 13          # (bit 12 stays unassigned) RadialDistributionFeat
 FAM_FRACTAL = 1 << 15         # FractalDimensionFeature (FRACT_DIM_BOXCOUNT, FRACT_DIM_PERIMETER)
 FAM_EULER = 1 << 16           # EulerNumberFeature (EULER_NUMBER)
 FAM_ROI_RADIUS = 1 << 17      # RoiRadiusFeature (ROI_RADIUS_MEAN, ROI_RADIUS_MAX, ROI_RADIUS_MEDIAN)
+# the three caliper classes (columns between FRACT_DIM_PERIMETER and EULER_NUMBER); not part of FAM_ALL.  The only families that read
+# the ROI origin (HostBatch.origin_x / origin_y, nyxhip_featurize_batch_at)
+FAM_FERET = 1 << 18           # CaliperFeretFeature (MIN_FERET_ANGLE, MAX_FERET_ANGLE, STAT_FERET_DIAM_*)
+FAM_MARTIN = 1 << 19          # CaliperMartinFeature (STAT_MARTIN_DIAM_*)
+FAM_NASSENSTEIN = 1 << 20     # CaliperNassensteinFeature (STAT_NASSENSTEIN_DIAM_*)
+FAM_CALIPER = FAM_FERET | FAM_MARTIN | FAM_NASSENSTEIN
 FAM_NORTH_STAR = 0x7F
 FAM_ALL = 0xFFF
 
@@ -157,6 +163,9 @@ class HostBatch:
     max_inten: np.ndarray
     slide_min: Optional[np.ndarray] = None
     slide_max: Optional[np.ndarray] = None
+    origin_x: Optional[np.ndarray] = None    # [n_roi] aabb.xmin / aabb.ymin of the ROIs in their image, or None: (0, 0)
+    origin_y: Optional[np.ndarray] = None
+    origin_unrepresentable: bool = False     # built from ROIs whose origins do not fit uint32 (batch_from_rois)
 
     def __post_init__(self):
         self.roi_label = np.ascontiguousarray(self.roi_label, np.uint32)
@@ -172,6 +181,13 @@ class HostBatch:
             self.slide_min = np.ascontiguousarray(self.slide_min, np.float64)
             self.slide_max = np.ascontiguousarray(self.slide_max, np.float64)
         n = len(self.roi_label)
+        if (self.origin_x is None) != (self.origin_y is None):
+            raise ValueError("origin_x and origin_y must both be given or both None")
+        if self.origin_x is not None:
+            self.origin_x = np.ascontiguousarray(self.origin_x, np.uint32)
+            self.origin_y = np.ascontiguousarray(self.origin_y, np.uint32)
+            if len(self.origin_x) != n or len(self.origin_y) != n:
+                raise ValueError("origin_x / origin_y must have n_roi entries")
         if len(self.px_offset) != n + 1:
             raise ValueError("px_offset must have n_roi+1 entries")
         if int(self.px_offset[-1]) != len(self.inten) or len(self.x) != len(self.inten) or len(self.y) != len(self.inten):
@@ -207,6 +223,7 @@ def batch_from_rois(rois: Sequence[dict]) -> HostBatch:
     (what phase 1 of the reference records in LR::aux_min/aux_max,
     /root/reference/src/nyx/pixel_feed.cpp:19-43)."""
     labels, offs, xs, ys, it, bw, bh, mn, mx = [], [0], [], [], [], [], [], [], []
+    ox, oy = [], []
     smin, smax = [], []
     for k, r in enumerate(rois):
         x = np.asarray(r["x"], np.int64)
@@ -215,6 +232,8 @@ def batch_from_rois(rois: Sequence[dict]) -> HostBatch:
         if len(v) == 0:
             raise ValueError("empty ROI")
         x0, y0 = x.min(), y.min()
+        ox.append(int(x0))
+        oy.append(int(y0))
         xs.append((x - x0).astype(np.uint16))
         ys.append((y - y0).astype(np.uint16))
         it.append(v)
@@ -228,7 +247,15 @@ def batch_from_rois(rois: Sequence[dict]) -> HostBatch:
             smin.append(float(r["slide_min"]))
             smax.append(float(r["slide_max"]))
     has_slide = len(smin) == len(rois) and len(rois) > 0
-    return HostBatch(
+    hb = HostBatch(
         np.array(labels), np.array(offs), np.concatenate(xs), np.concatenate(ys), np.concatenate(it),
         np.array(bw), np.array(bh), np.array(mn), np.array(mx),
         np.array(smin) if has_slide else None, np.array(smax) if has_slide else None)
+    # the box origins (the caliper families read them).  Origins below 0 or beyond 32 bits cannot cross the ABI: the batch is marked,
+    # and a call that asks for a caliper family on it is an error (Context.featurize_host) instead of rows computed at (0, 0)
+    if rois and min(ox + oy) >= 0 and max(ox + oy) < 2 ** 32:
+        hb.origin_x = np.array(ox, np.uint32)
+        hb.origin_y = np.array(oy, np.uint32)
+    else:
+        hb.origin_unrepresentable = bool(rois)
+    return hb

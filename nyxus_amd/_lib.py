@@ -27,7 +27,7 @@ ABI_SYMBOLS = [
     "nyxhip_featurize_batch_async", "nyxhip_sync", "nyxhip_finalize_table", "nyxhip_featurize_tile", "nyxhip_featurize_tiles",
     "nyxhip_timing_enable", "nyxhip_timing_reset", "nyxhip_timing_get",
     "nyxhip_featurize_tiles_v2", "nyxhip_fetch_result", "nyxhip_featurize_tiles_sharded", "nyxhip_fetch_result_sharded",
-    "nyxhip_launch_report",
+    "nyxhip_launch_report", "nyxhip_featurize_batch_at", "nyxhip_featurize_batch_async_at",
 ]
 
 
@@ -77,6 +77,10 @@ def load() -> C.CDLL:
     for name in ("nyxhip_featurize_batch", "nyxhip_featurize_batch_async"):
         f = getattr(lib, name)
         f.argtypes = [C.c_void_p, P(_abi.Batch), C.c_uint32, P(_abi.Settings), C.c_void_p, C.c_size_t]
+        f.restype = C.c_int
+    for name in ("nyxhip_featurize_batch_at", "nyxhip_featurize_batch_async_at"):
+        f = getattr(lib, name)
+        f.argtypes = [C.c_void_p, P(_abi.Batch), C.c_void_p, C.c_void_p, C.c_uint32, P(_abi.Settings), C.c_void_p, C.c_size_t]
         f.restype = C.c_int
     lib.nyxhip_sync.argtypes = [C.c_void_p]
     lib.nyxhip_sync.restype = C.c_int
@@ -186,12 +190,24 @@ class Context:
         ncol = self.n_columns(mask, s)
         out = np.empty((batch.n_roi, ncol), np.float64)
         cb = batch.c_struct()
-        self._check(self._lib.nyxhip_featurize_batch(self._h, C.byref(cb), mask, C.byref(s), out.ctypes.data, ncol))
+        if (mask & _abi.FAM_CALIPER) and batch.origin_unrepresentable:
+            raise ValueError("the caliper families need the ROIs' origins, and this batch's lie below 0 or beyond 32 bits")
+        if batch.origin_x is not None:           # the ROIs' positions: read by the caliper families only
+            self._check(self._lib.nyxhip_featurize_batch_at(self._h, C.byref(cb), batch.origin_x.ctypes.data, batch.origin_y.ctypes.data, mask,
+                                                            C.byref(s), out.ctypes.data, ncol))
+        else:
+            self._check(self._lib.nyxhip_featurize_batch(self._h, C.byref(cb), mask, C.byref(s), out.ctypes.data, ncol))
         return out
 
-    def featurize_device_async(self, cb: _abi.Batch, mask: int, s: _abi.Settings, out_ptr: int, ld: int):
-        """Device pointers in ``cb``; enqueues the kernel on the context's stream."""
-        self._check(self._lib.nyxhip_featurize_batch_async(self._h, C.byref(cb), mask, C.byref(s), C.c_void_p(out_ptr), ld))
+    def featurize_device_async(self, cb: _abi.Batch, mask: int, s: _abi.Settings, out_ptr: int, ld: int, origin_x_ptr: Optional[int] = None,
+                               origin_y_ptr: Optional[int] = None):
+        """Device pointers in ``cb``; enqueues the kernel on the context's stream.  origin_*_ptr: device arrays [n_roi] of the
+        ROIs' box origins (nyxhip_featurize_batch_async_at)."""
+        if origin_x_ptr is not None:
+            self._check(self._lib.nyxhip_featurize_batch_async_at(self._h, C.byref(cb), C.c_void_p(origin_x_ptr), C.c_void_p(origin_y_ptr), mask,
+                                                                  C.byref(s), C.c_void_p(out_ptr), ld))
+        else:
+            self._check(self._lib.nyxhip_featurize_batch_async(self._h, C.byref(cb), mask, C.byref(s), C.c_void_p(out_ptr), ld))
 
     def featurize_tile_host(self, inten: np.ndarray, label: np.ndarray, mask: int, s: _abi.Settings, max_label: Optional[int] = None):
         """One intensity / label tile pair (host arrays) through the fused device path: label scan + ROI assembly + reduce.

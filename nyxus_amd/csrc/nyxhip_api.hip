@@ -100,11 +100,13 @@ int nyxhip_sync(nyxhip_ctx* ctx)
     return check_status(ctx);
 }
 
-int nyxhip_featurize_batch_async(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t mask, const nyxhip_settings* s,
-                                 double* out, size_t ld)
+int nyxhip_featurize_batch_async_at(nyxhip_ctx* ctx, const nyxhip_batch* b, const uint32_t* origin_x, const uint32_t* origin_y,
+                                    uint32_t mask, const nyxhip_settings* s, double* out, size_t ld)
 {
     int rc = validate(ctx, b, mask, s, out, ld);
     if (rc) return rc;
+    if ((origin_x == nullptr) != (origin_y == nullptr))
+        return fail(ctx, NYXHIP_ERR_INVALID_ARG, "origin_x and origin_y must both be given or both NULL");
     if (b->memory != NYXHIP_MEM_DEVICE)
         return fail(ctx, NYXHIP_ERR_INVALID_ARG, "the async form takes device-resident batches only");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -112,16 +114,31 @@ int nyxhip_featurize_batch_async(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_
     // batch extrema: the caller's statement when given (all of max_px / max_bbox_area / max_bbox_side non-zero), else the size
     // classifier of launch_device_all derives them on the device
     const bool hinted = b->max_px != 0 && b->max_bbox_area != 0 && b->max_bbox_side != 0;
+    OriginScope origins(ctx, origin_x, origin_y);
     return launch_device(ctx, b, mask, s, out, ld, b->max_px, b->max_bbox_area, b->max_inten_range, b->max_bbox_side, hinted);
+}
+
+int nyxhip_featurize_batch_async(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t mask, const nyxhip_settings* s,
+                                 double* out, size_t ld)
+{
+    return nyxhip_featurize_batch_async_at(ctx, b, nullptr, nullptr, mask, s, out, ld);
 }
 
 int nyxhip_featurize_batch(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t mask, const nyxhip_settings* s,
                            double* out, size_t ld)
 {
+    return nyxhip_featurize_batch_at(ctx, b, nullptr, nullptr, mask, s, out, ld);
+}
+
+int nyxhip_featurize_batch_at(nyxhip_ctx* ctx, const nyxhip_batch* b, const uint32_t* origin_x, const uint32_t* origin_y,
+                              uint32_t mask, const nyxhip_settings* s, double* out, size_t ld)
+{
     int rc = validate(ctx, b, mask, s, out, ld);
     if (rc) return rc;
+    if ((origin_x == nullptr) != (origin_y == nullptr))
+        return fail(ctx, NYXHIP_ERR_INVALID_ARG, "origin_x and origin_y must both be given or both NULL");
     if (b->memory == NYXHIP_MEM_DEVICE) {
-        rc = nyxhip_featurize_batch_async(ctx, b, mask, s, out, ld);
+        rc = nyxhip_featurize_batch_async_at(ctx, b, origin_x, origin_y, mask, s, out, ld);
         if (rc) return rc;
         return nyxhip_sync(ctx);
     }
@@ -149,7 +166,8 @@ int nyxhip_featurize_batch(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t mask
     auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
     size_t o_off = 0, o_x = al(o_off + 8 * (nr + 1)), o_y = al(o_x + 2 * npx), o_i = al(o_y + 2 * npx),
            o_bw = al(o_i + 4 * npx), o_bh = al(o_bw + 4 * nr), o_mn = al(o_bh + 4 * nr), o_mx = al(o_mn + 4 * nr),
-           o_smin = al(o_mx + 4 * nr), o_smax = al(o_smin + 8 * nr), o_out = al(o_smax + 8 * nr),
+           o_smin = al(o_mx + 4 * nr), o_smax = al(o_smin + 8 * nr), o_ox = al(o_smax + 8 * nr), o_oy = al(o_ox + (origin_x ? 4 * nr : 0)),
+           o_out = al(o_oy + (origin_x ? 4 * nr : 0)),
            total = al(o_out + 8ull * nr * n_cols);
     rc = ensure_stage(ctx, total);
     if (rc) return rc;
@@ -167,6 +185,10 @@ int nyxhip_featurize_batch(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t mask
         HIP_TRY(ctx, hipMemcpyAsync(base + o_smin, b->slide_min, 8 * nr, hipMemcpyHostToDevice, st));
         HIP_TRY(ctx, hipMemcpyAsync(base + o_smax, b->slide_max, 8 * nr, hipMemcpyHostToDevice, st));
     }
+    if (origin_x) {
+        HIP_TRY(ctx, hipMemcpyAsync(base + o_ox, origin_x, 4 * nr, hipMemcpyHostToDevice, st));
+        HIP_TRY(ctx, hipMemcpyAsync(base + o_oy, origin_y, 4 * nr, hipMemcpyHostToDevice, st));
+    }
     nyxhip_batch d = *b;
     d.memory = NYXHIP_MEM_DEVICE;
     d.px_offset = (const uint64_t*)(base + o_off);
@@ -177,7 +199,10 @@ int nyxhip_featurize_batch(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t mask
     d.slide_max = b->slide_max ? (const double*)(base + o_smax) : nullptr;
     double* d_out = (double*)(base + o_out);
     ctx->census_small = n_small; ctx->census_total = nr; ctx->census_pending = 0;
-    rc = launch_device(ctx, &d, mask, s, d_out, (size_t)n_cols, max_px, max_area, max_range, max_side);
+    {
+        OriginScope origins(ctx, origin_x ? (const uint32_t*)(base + o_ox) : nullptr, origin_x ? (const uint32_t*)(base + o_oy) : nullptr);
+        rc = launch_device(ctx, &d, mask, s, d_out, (size_t)n_cols, max_px, max_area, max_range, max_side);
+    }
     if (rc) return rc;
     HIP_TRY(ctx, hipMemcpy2DAsync(out, ld * sizeof(double), d_out, (size_t)n_cols * sizeof(double),
                                   (size_t)n_cols * sizeof(double), nr, hipMemcpyDeviceToHost, st));

@@ -92,6 +92,17 @@ std::vector<std::string> column_names(uint32_t mask, const nyxhip_settings* s)
         for (auto n : kIntensityNames) v.push_back(n);
     // the shape block follows the intensity block (featureset.h:46-160)
     if (mask & NYXHIP_FAM_FRACTAL) { v.push_back("FRACT_DIM_BOXCOUNT"); v.push_back("FRACT_DIM_PERIMETER"); }
+    {   // the caliper classes (featureset.h:93-114; names: featureset.cpp:181-203)
+        const char* st[6] = {"MIN", "MAX", "MEAN", "MEDIAN", "STDDEV", "MODE"};
+        if (mask & NYXHIP_FAM_FERET) {
+            v.push_back("MIN_FERET_ANGLE"); v.push_back("MAX_FERET_ANGLE");
+            for (auto k : st) v.push_back(std::string("STAT_FERET_DIAM_") + k);
+        }
+        if (mask & NYXHIP_FAM_MARTIN)
+            for (auto k : st) v.push_back(std::string("STAT_MARTIN_DIAM_") + k);
+        if (mask & NYXHIP_FAM_NASSENSTEIN)
+            for (auto k : st) v.push_back(std::string("STAT_NASSENSTEIN_DIAM_") + k);
+    }
     if (mask & NYXHIP_FAM_EULER) v.push_back("EULER_NUMBER");
     if (mask & NYXHIP_FAM_ROI_RADIUS) { v.push_back("ROI_RADIUS_MEAN"); v.push_back("ROI_RADIUS_MAX"); v.push_back("ROI_RADIUS_MEDIAN"); }
     if (mask & NYXHIP_FAM_GLCM) {
@@ -187,6 +198,9 @@ int nyxhip_n_columns(uint32_t family_mask, const nyxhip_settings* s)
     int n = 0;
     if (family_mask & NYXHIP_FAM_INTENSITY) n += kIntensityCols;
     if (family_mask & NYXHIP_FAM_FRACTAL) n += kFractalCols;
+    if (family_mask & NYXHIP_FAM_FERET) n += kFeretCols;
+    if (family_mask & NYXHIP_FAM_MARTIN) n += kMartinCols;
+    if (family_mask & NYXHIP_FAM_NASSENSTEIN) n += kNassensteinCols;
     if (family_mask & NYXHIP_FAM_EULER) n += kEulerCols;
     if (family_mask & NYXHIP_FAM_ROI_RADIUS) n += kRoiRadiusCols;
     if (family_mask & NYXHIP_FAM_GLCM) n += kGlcmAngled * s->glcm_n_angles + kGlcmAve;

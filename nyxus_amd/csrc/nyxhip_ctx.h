@@ -21,6 +21,7 @@
 #include "roi_kernel.h"
 #include "roi_radial.h"
 #include "roi_outline.h"
+#include "roi_caliper.h"
 
 // One hipMalloc allocation, grow-only.  hipFree waits for the device's work by itself; the stream handed to reserve() states which
 // work the site knows to be using the old block.
@@ -143,6 +144,11 @@ struct nyxhip_ctx {
     // outline kernel (roi_outline.hip): list of the ROIs whose bit planes exceed LDS, and their global bit planes
     DevBuf d_outline_list;
     DevBuf d_outline_bits;
+    // caliper kernel (roi_caliper.hip): list of the ROIs whose boxes are wider than the LDS column table, and their global tables
+    DevBuf d_caliper_list;
+    DevBuf d_caliper_ws;
+    const uint32_t* origin_x_next = nullptr;   // set by nyxhip_featurize_batch[_async]_at and the tile path for their next launch_device call:
+    const uint32_t* origin_y_next = nullptr;   // device arrays [n_roi] of the ROIs' box origins (NULL: (0, 0))
     // grow-only workspaces of the fused tile path: scan tables + rows | clouds | two staging slots for host tiles
     DevBuf d_tile;
     DevBuf d_cloud;
@@ -195,6 +201,15 @@ struct nyxhip_ctx {
     hipStream_t stream() const { return use_user_stream ? user_stream : own_stream; }
 };
 
+// Sets the origins of the context's next launch_device call and clears them on every way out of the scope.
+struct OriginScope {
+    nyxhip_ctx* c;
+    OriginScope(nyxhip_ctx* ctx, const uint32_t* ox, const uint32_t* oy) : c(ctx) { c->origin_x_next = ox; c->origin_y_next = oy; }
+    OriginScope(const OriginScope&) = delete;
+    OriginScope& operator=(const OriginScope&) = delete;
+    ~OriginScope() { c->origin_x_next = c->origin_y_next = nullptr; }
+};
+
 // families the kernels cover so far
 constexpr uint32_t kTexture = NYXHIP_FAM_GLRLM | NYXHIP_FAM_GLSZM | NYXHIP_FAM_NGTDM;
 constexpr uint32_t kShape = NYXHIP_FAM_GABOR | NYXHIP_FAM_ZERNIKE;
@@ -203,8 +218,10 @@ constexpr uint32_t kMoments = NYXHIP_FAM_SMOMS | NYXHIP_FAM_IMOMS;
 constexpr uint32_t kOutline = NYXHIP_FAM_FRACTAL | NYXHIP_FAM_EULER | NYXHIP_FAM_ROI_RADIUS;   // roi_outline.hip; their columns follow the intensity block
 // families that read the ROI's ordered contour (launch_contour_families)
 constexpr uint32_t kContourFams = kMoments | NYXHIP_FAM_RADIAL | NYXHIP_FAM_FRACTAL | NYXHIP_FAM_ROI_RADIUS;
-constexpr uint32_t kTailFams = kContourFams | NYXHIP_FAM_EULER;   // ... and everything else launch_contour_families serves (no size classes)
-constexpr uint32_t kImplemented = NYXHIP_FAM_INTENSITY | NYXHIP_FAM_GLCM | kTexture | kShape | kDependence | kMoments | NYXHIP_FAM_RADIAL | kOutline;
+constexpr uint32_t kCaliper = NYXHIP_FAM_FERET | NYXHIP_FAM_MARTIN | NYXHIP_FAM_NASSENSTEIN;   // roi_caliper.hip; their columns follow FRACT_DIM_PERIMETER
+constexpr uint32_t kBehindIntensity = kOutline | kCaliper;   // families whose columns lie between the intensity block and GLCM
+constexpr uint32_t kTailFams = kContourFams | NYXHIP_FAM_EULER | kCaliper;   // ... and everything else launch_contour_families serves (no size classes)
+constexpr uint32_t kImplemented = NYXHIP_FAM_INTENSITY | NYXHIP_FAM_GLCM | kTexture | kShape | kDependence | kMoments | NYXHIP_FAM_RADIAL | kOutline | kCaliper;
 
 namespace nyxhip __attribute__((visibility("hidden"))) {
 

@@ -329,7 +329,7 @@ int build_args(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t mask, const nyxh
     // The outline families (roi_outline.hip) sit between the intensity block and GLCM: every base behind the intensity block moves by
     // their columns.  n_cols1: where the INTENSITY + GLCM span ends.  The feature kernels zero and fill one span of columns from
     // column 0, so a launch with GLCM covers the outline columns as well (launch_device_all enqueues the outline kernel behind it).
-    const int outline_cols = nyxhip_n_columns(mask & kOutline, s);
+    const int outline_cols = nyxhip_n_columns(mask & kBehindIntensity, s);   // (the caliper columns lie among them: roi_caliper.hip)
     const int n_cols1 = nyxhip_n_columns(mask1, s) + outline_cols;
     const int n_cols_feat = (mask1 & NYXHIP_FAM_GLCM) ? n_cols1 : n_cols1 - outline_cols;   // columns the feature kernel owns
     memset(&a, 0, sizeof(a));
@@ -457,6 +457,60 @@ int use_lane(nyxhip_ctx* ctx, int lane, hipStream_t* st)
     return NYXHIP_OK;
 }
 
+// The caliper classes (roi_caliper.hip) on `st`: one workgroup per ROI over the pixel clouds, no contour.  Columns: between
+// FRACT_DIM_PERIMETER and EULER_NUMBER.  The origins are those the entry point left in the context (NULL: (0, 0)).  ROIs whose
+// boxes are wider than the LDS column table go through a classifier and a list launch over global tables, like the outline
+// kernel's deferred ROIs.
+int launch_caliper(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t mask, const nyxhip_settings* s, double* d_out, size_t ld, uint32_t max_side,
+                   hipStream_t st)
+{
+    CalArgs ca;
+    memset(&ca, 0, sizeof(ca));
+    ca.n_roi = b->n_roi;
+    ca.px_offset = b->px_offset; ca.x = b->x; ca.y = b->y; ca.bbox_w = b->bbox_w;
+    ca.origin_x = ctx->origin_x_next; ca.origin_y = ctx->origin_y_next;
+    ca.out = d_out; ca.ld = ld; ca.status = ctx->d_status.as<int>();
+    ca.fams = mask & kCaliper;
+    ca.col_feret = nyxhip_n_columns(mask & (NYXHIP_FAM_INTENSITY | NYXHIP_FAM_FRACTAL), s);
+    ca.col_martin = ca.col_feret + ((mask & NYXHIP_FAM_FERET) ? kFeretCols : 0);
+    ca.col_nassenstein = ca.col_martin + ((mask & NYXHIP_FAM_MARTIN) ? kMartinCols : 0);
+    ca.soft_nan = s->soft_nan;
+    // the reference's expression (rotation.cpp:56-58) on the host's libm, as the reference evaluates it
+    for (int k = 0; k < kCaliperAngles; k++) {
+        const float theta = (float)(10 * k) * float(3.14159265358979323846) / 180.f;
+        ca.sn[k] = std::sin((double)theta); ca.cs[k] = std::cos((double)theta);
+    }
+    const uint32_t side = std::max<uint32_t>(max_side, 1u);
+    ca.cols_cap = std::min<uint32_t>(kCaliperColsLds, (side + 7u) & ~7u);
+    ca.defer_wide = side > kCaliperColsLds ? 1u : 0u;
+    if (launch_roi_caliper(ca, st, (uint32_t)b->n_roi) != 0)
+        return fail(ctx, NYXHIP_ERR_HIP, "caliper kernel: launch failed");
+    if (!ca.defer_wide) return NYXHIP_OK;
+    const size_t list_bytes = 4ull * b->n_roi + 512;
+    HIP_TRY(ctx, ctx->d_caliper_list.reserve(list_bytes, st));
+    uint32_t* d_cnt = ctx->d_caliper_list.as<uint32_t>();
+    uint32_t* d_list = d_cnt + 64;
+    HIP_TRY(ctx, hipMemsetAsync(d_cnt, 0, 4, st));
+    if (launch_caliper_classify(b->n_roi, b->bbox_w, ca.cols_cap, d_list, d_cnt, st) != 0)
+        return fail(ctx, NYXHIP_ERR_HIP, "caliper classifier: launch failed");
+    uint32_t n_wide = 0;
+    HIP_TRY(ctx, hipMemcpyAsync(&n_wide, d_cnt, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    if (!n_wide) return NYXHIP_OK;
+    const uint32_t ws_cols = (std::min<uint32_t>(side, 65535u) + 31u) & ~31u;
+    const uint64_t stride = (uint64_t)kCaliperBytesPerCol * ws_cols;
+    const uint32_t chunk = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(n_wide, ((uint64_t)1 << 30) / stride));
+    HIP_TRY(ctx, ctx->d_caliper_ws.reserve((size_t)(stride * chunk), st));
+    CalArgs cw = ca;
+    cw.defer_wide = 0; cw.ws = ctx->d_caliper_ws.as<unsigned char>(); cw.ws_cols = ws_cols;
+    for (uint32_t o = 0; o < n_wide; o += chunk) {
+        cw.roi_index = d_list + o;
+        if (launch_roi_caliper(cw, st, std::min(chunk, n_wide - o)) != 0)
+            return fail(ctx, NYXHIP_ERR_HIP, "caliper kernel: launch failed");
+    }
+    return NYXHIP_OK;
+}
+
 // Contour (roi_moments.hip) + the families that read it: the 2-D geometric moments (roi_moments.hip) and the radial intensity
 // distribution (roi_radial.hip).  The contour of every ROI goes to a context-owned workspace at the ROI's CSR offset (a contour
 // never has more points than the ROI has pixels) ONCE per call; the moments kernel and / or the radial kernel read it back.
@@ -476,7 +530,7 @@ int launch_contour_families(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t mas
         oa.fams = mask & kOutline;
         oa.has_contour = need_contour ? 1u : 0u;
         oa.col_fractal = nyxhip_n_columns(mask & NYXHIP_FAM_INTENSITY, s);
-        oa.col_euler = oa.col_fractal + ((mask & NYXHIP_FAM_FRACTAL) ? kFractalCols : 0);
+        oa.col_euler = oa.col_fractal + ((mask & NYXHIP_FAM_FRACTAL) ? kFractalCols : 0) + nyxhip_n_columns(mask & kCaliper, s);   // (enum order)
         oa.col_radius = oa.col_euler + ((mask & NYXHIP_FAM_EULER) ? kEulerCols : 0);
         if (mask & (NYXHIP_FAM_FRACTAL | NYXHIP_FAM_EULER)) {
             // bound of outline_bit_words over boxes of at most max_area cells and max_side a side: rows of w / 32 + 1 words, the pyramid
@@ -516,6 +570,10 @@ int launch_contour_families(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t mas
         }
         return NYXHIP_OK;
     };
+    if (mask & kCaliper)
+        if (int crc = launch_caliper(ctx, b, mask, s, d_out, ld, max_side, st)) return crc;
+    if (!need_contour && !do_out)
+        return NYXHIP_OK;                                  // the caliper classes alone
     if (!need_contour) {
         // EULER_NUMBER alone: no contour, no staged pixels -- the bit plane only
         MomArgs& m = oa.m;
@@ -568,7 +626,7 @@ int launch_contour_families(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t mas
     memset(&ra, 0, sizeof(ra));
     if (do_rad) {
         // columns: FRAC_AT_D | GABOR | MEAN_FRAC | RADIAL_CV (enum order)
-        const uint32_t before = NYXHIP_FAM_INTENSITY | kOutline | NYXHIP_FAM_GLCM | kTexture | kDependence;
+        const uint32_t before = NYXHIP_FAM_INTENSITY | kBehindIntensity | NYXHIP_FAM_GLCM | kTexture | kDependence;
         ra.col_frac = nyxhip_n_columns(mask & before, s);
         ra.col_mean = ra.col_frac + kRadialBins + ((mask & NYXHIP_FAM_GABOR) ? s->gabor_n_filters : 0);
         ra.col_cv = ra.col_mean + kRadialBins;
@@ -784,7 +842,7 @@ static int run_large(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t mask, cons
     a.bbox_w = b->bbox_w; a.bbox_h = b->bbox_h; a.min_inten = b->min_inten; a.max_inten = b->max_inten;
     a.slide_min = b->slide_min; a.slide_max = b->slide_max;
     a.out = d_out; a.ld = ld; a.status = ctx->d_status.as<int>();
-    const int outline_cols = nyxhip_n_columns(mask & kOutline, s);   // between the intensity block and GLCM (build_args)
+    const int outline_cols = nyxhip_n_columns(mask & kBehindIntensity, s);   // between the intensity block and GLCM (build_args)
     a.mask = mask1; a.n_cols = nyxhip_n_columns(mask1, s) + ((mask1 & NYXHIP_FAM_GLCM) ? outline_cols : 0);
     a.col_intensity = (mask1 & NYXHIP_FAM_INTENSITY) ? 0 : -1;
     a.col_glcm = (mask1 & NYXHIP_FAM_GLCM) ? ((mask1 & NYXHIP_FAM_INTENSITY) ? kIntensityCols : 0) + outline_cols : -1;
@@ -927,7 +985,7 @@ static int run_large_tex(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t full, 
     a.bbox_w = b->bbox_w; a.bbox_h = b->bbox_h; a.min_inten = b->min_inten; a.max_inten = b->max_inten;
     a.out = d_out; a.ld = ld; a.status = ctx->d_status.as<int>();
     a.mask = mask2; a.n_cols = nyxhip_n_columns(mask2, s);
-    a.col0 = nyxhip_n_columns(full & (NYXHIP_FAM_INTENSITY | NYXHIP_FAM_GLCM | kOutline), s);
+    a.col0 = nyxhip_n_columns(full & (NYXHIP_FAM_INTENSITY | NYXHIP_FAM_GLCM | kBehindIntensity), s);
     a.gap_after_glrlm = (full & NYXHIP_FAM_GLDZM) ? kGldzmCols : 0;
     a.gap_after_glszm = ((full & NYXHIP_FAM_GLDM) ? kGldmCols : 0) + ((full & NYXHIP_FAM_NGLDM) ? kNgldmCols : 0);
     a.soft_nan = s->soft_nan; a.grey_depth = s->grey_depth; a.ibsi = s->ibsi;
@@ -1510,7 +1568,7 @@ int launch_device_all(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t mask, con
     if (mask & kTailFams) {
         // A feature launch with GLCM zeroes and fills its columns from column 0, across the outline columns: the outline kernel goes
         // behind every feature launch of the call -- the lanes join here and the contour chain stays on the call's stream.
-        const bool after_all = (mask & kOutline) && (mask & NYXHIP_FAM_GLCM);
+        const bool after_all = (mask & kBehindIntensity) && (mask & NYXHIP_FAM_GLCM);
         if (after_all) lane_join.join();
         if (int mrc = launch_contour_families(ctx, b, mask, s, d_out, ld, max_px, max_area, max_side, !after_all))
             return mrc;
@@ -1769,7 +1827,7 @@ int validate(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t mask, const nyxhip
 {
     if (!ctx) return NYXHIP_ERR_INVALID_ARG;
     if (!b || !s || !out) return fail(ctx, NYXHIP_ERR_INVALID_ARG, "null batch / settings / out_table");
-    if (mask == 0 || (mask & ~(NYXHIP_FAM_ALL | NYXHIP_FAM_RADIAL | kOutline))) return fail(ctx, NYXHIP_ERR_INVALID_ARG, "bad family mask");
+    if (mask == 0 || (mask & ~(NYXHIP_FAM_ALL | NYXHIP_FAM_RADIAL | kOutline | kCaliper))) return fail(ctx, NYXHIP_ERR_INVALID_ARG, "bad family mask");
     if (mask & ~kImplemented)
         return fail(ctx, NYXHIP_ERR_UNSUPPORTED, "requested feature family is not implemented by the HIP path yet "
                     "(all seven hot-path families are implemented; bad mask?)");

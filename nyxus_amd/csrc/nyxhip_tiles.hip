@@ -146,6 +146,8 @@ static int tiles_chunk(nyxhip_ctx* ctx, const void* d_inten, int dtI, const void
         static const bool no_swz = [] { const char* e = getenv("NYXHIP_NO_XCD_SWIZZLE"); return e && *e && *e != '0'; }();   // A/B
         ctx->win_next = WindowSrc{d_inten, d_label, dtI, dtL, W, H, R.tile, R.label, R.bbox_x0, R.bbox_y0, no_swz ? 0u : 1u};
     }
+    // the box origins inside the tile: one tile is one image, so they are the reference's coordinates (the caliper classes read them)
+    OriginScope origins(ctx, R.bbox_x0, R.bbox_y0);
     int lrc = launch_device(ctx, &b, family_mask, s, d_out, d_ld, meta[3], meta[4], meta[5], meta[6]);
     ctx->win_next = WindowSrc{};
     if (lrc == NYXHIP_INTERNAL_NEEDS_CLOUDS) {

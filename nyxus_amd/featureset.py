@@ -96,6 +96,19 @@ for _n in EULER:
 for _n in ROI_RADIUS:
     FAMILY_OF[_n] = _abi.FAM_ROI_RADIUS
 
+# the three caliper classes (featureset.h:93-114): between FRACT_DIM_PERIMETER and EULER_NUMBER.  No group token: the reference's
+# tokens that cover these codes also cover codes the path does not serve.
+_STAT6 = ["MIN", "MAX", "MEAN", "MEDIAN", "STDDEV", "MODE"]
+FERET = ["MIN_FERET_ANGLE", "MAX_FERET_ANGLE"] + ["STAT_FERET_DIAM_" + k for k in _STAT6]
+MARTIN = ["STAT_MARTIN_DIAM_" + k for k in _STAT6]
+NASSENSTEIN = ["STAT_NASSENSTEIN_DIAM_" + k for k in _STAT6]
+for _n in FERET:
+    FAMILY_OF[_n] = _abi.FAM_FERET
+for _n in MARTIN:
+    FAMILY_OF[_n] = _abi.FAM_MARTIN
+for _n in NASSENSTEIN:
+    FAMILY_OF[_n] = _abi.FAM_NASSENSTEIN
+
 # group tokens (featureset.cpp:650-665) the HIP path can serve completely (the radial distribution has none, featureset.cpp:650-668)
 GROUPS: Dict[str, List[str]] = {
     "*ALL_INTENSITY*": INTENSITY,
@@ -117,6 +130,8 @@ ENUM_ORDER: List[str] = (INTENSITY + GLCM_ANGLED + GLCM_AVE + GLRLM_ANGLED + GLR
 # ... and the order expand() returns codes in: ENUM_ORDER with the shape-block codes at their enum position (ENUM_ORDER itself
 # keeps the codes of the twelve FAM_ALL families and the radial distribution)
 OUTPUT_ORDER: List[str] = INTENSITY + FRACTAL + EULER + ROI_RADIUS + ENUM_ORDER[len(INTENSITY):]
+# every served code in true enum order: OUTPUT_ORDER with the caliper codes behind FRACT_DIM_PERIMETER.  expand() orders by this list.
+SERVED_ORDER: List[str] = INTENSITY + FRACTAL + FERET + MARTIN + NASSENSTEIN + OUTPUT_ORDER[len(INTENSITY) + len(FRACTAL):]
 
 
 def expand(features: List[str]) -> Tuple[int, List[str]]:
@@ -136,10 +151,10 @@ def expand(features: List[str]) -> Tuple[int, List[str]]:
             f"feature(s) {unknown} are not served by the MI355X path. Implemented: groups {sorted(GROUPS)} and the "
             f"individual features of the intensity, GLCM, GLRLM, GLDZM, GLSZM, GLDM, NGLDM and NGTDM families, GABOR, ZERNIKE2D, "
             f"FRAC_AT_D, MEAN_FRAC, RADIAL_CV, FRACT_DIM_BOXCOUNT, FRACT_DIM_PERIMETER, EULER_NUMBER, ROI_RADIUS_MEAN, ROI_RADIUS_MAX, "
-            f"ROI_RADIUS_MEDIAN")
+            f"ROI_RADIUS_MEDIAN, MIN_FERET_ANGLE, MAX_FERET_ANGLE and STAT_{{FERET,MARTIN,NASSENSTEIN}}_DIAM_{{MIN,MAX,MEAN,MEDIAN,STDDEV,MODE}}")
     if not want:
         raise ValueError("no features requested")
-    ordered = [n for n in OUTPUT_ORDER if n in want]
+    ordered = [n for n in SERVED_ORDER if n in want]
     mask = 0
     for n in ordered:
         mask |= FAMILY_OF[n]
