@@ -72,14 +72,21 @@ enum {
     NYXHIP_FAM_EULER     = 1u << 16, /* EulerNumberFeature, 1 column: EULER_NUMBER, mode 8 (features/euler_number.h)                        */
     NYXHIP_FAM_ROI_RADIUS = 1u << 17, /* RoiRadiusFeature, 3 columns: ROI_RADIUS_MEAN, ROI_RADIUS_MAX, ROI_RADIUS_MEDIAN (features/roi_radius.h) */
     /* the three caliper classes (featureset.h:93-114, features/caliper.h): statistics of diameters of the convex hull turned in steps of
-     * 10 degrees.  Not part of NYXHIP_FAM_ALL.  Their columns sit between FRACT_DIM_PERIMETER and EULER_NUMBER (enum order).  These are the
-     * only bits that read the ROI origin of nyxhip_featurize_batch_at(): the reference stores every rotated hull vertex as `float`
+     * 10 degrees.  Not part of NYXHIP_FAM_ALL.  Their columns sit between FRACT_DIM_PERIMETER and EULER_NUMBER (enum order).  These bits
+     * and NYXHIP_FAM_CHORDS are the only ones that read the ROI origin of nyxhip_featurize_batch_at(): the reference stores every rotated hull vertex as `float`
      * (features/rotation.cpp:37-68), so its values depend on where the ROI lies in its image.  Through the entries without an origin
      * the rows are those of an ROI whose bounding box starts at (0, 0).  An ROI of fewer than 2 pixels has no hull: all columns of
      * the requested classes are settings.soft_nan (caliper_feret.cpp:19-32). */
     NYXHIP_FAM_FERET     = 1u << 18, /* CaliperFeretFeature, 8 columns: MIN_FERET_ANGLE, MAX_FERET_ANGLE, STAT_FERET_DIAM_{MIN,MAX,MEAN,MEDIAN,STDDEV,MODE} */
     NYXHIP_FAM_MARTIN    = 1u << 19, /* CaliperMartinFeature, 6 columns: STAT_MARTIN_DIAM_{MIN,MAX,MEAN,MEDIAN,STDDEV,MODE}                                */
     NYXHIP_FAM_NASSENSTEIN = 1u << 20, /* CaliperNassensteinFeature, 6 columns: STAT_NASSENSTEIN_DIAM_{MIN,MAX,MEAN,MEDIAN,STDDEV,MODE}                    */
+    /* ChordsFeature (featureset.h:116-132, features/chords.h): statistics of the chords of the pixel cloud turned in 20 steps of
+     * pi / 20 about the centre of its box.  Not part of NYXHIP_FAM_ALL.  Columns between STAT_NASSENSTEIN_DIAM_MODE and EULER_NUMBER
+     * (enum order).  Reads the ROI origin of nyxhip_featurize_batch_at(), like the caliper bits: the reference rounds every turned pixel
+     * coordinate to float and truncates it toward zero (features/rotation.cpp:70-91), so the chords depend on where the ROI lies.
+     * Reads the intensities only for "zero or not" (a zero-intensity pixel is a hole, image_matrix.cpp:206-237) and relies on
+     * nyxhip_batch::min_inten to tell whether an ROI has any.  An ROI without a closed chord has 16 zeros (chords.cpp:59-60). */
+    NYXHIP_FAM_CHORDS    = 1u << 21, /* 16 columns: MAXCHORDS_{MAX,MAX_ANG,MIN,MIN_ANG,MEDIAN,MEAN,MODE,STDDEV}, then the same eight for ALLCHORDS */
     NYXHIP_FAM_NORTH_STAR = 0x7Fu,  /* the seven families of BASELINE.json's north_star */
     NYXHIP_FAM_ALL       = 0xFFFu
 };
@@ -220,7 +227,7 @@ int nyxhip_sync(nyxhip_ctx* ctx);
 
 /* The two calls above with the ROIs' positions: origin_x[r] / origin_y[r] = aabb.xmin / aabb.ymin of ROI r in its image ([n_roi],
  * in the memory of the batch's other pointers, batch->memory).  Both NULL = every origin (0, 0): exactly nyxhip_featurize_batch
- * [_async].  Only NYXHIP_FAM_FERET / _MARTIN / _NASSENSTEIN read the origin; every other column is the same with and without it. */
+ * [_async].  Only NYXHIP_FAM_FERET / _MARTIN / _NASSENSTEIN / _CHORDS read the origin; every other column is the same with and without it. */
 int nyxhip_featurize_batch_at(nyxhip_ctx* ctx, const nyxhip_batch* batch, const uint32_t* origin_x, const uint32_t* origin_y,
                               uint32_t family_mask, const nyxhip_settings* s, double* out_table, size_t out_ld);
 int nyxhip_featurize_batch_async_at(nyxhip_ctx* ctx, const nyxhip_batch* batch, const uint32_t* origin_x, const uint32_t* origin_y,

@@ -99,6 +99,10 @@ enum class Feature2D : int {
     IMOM_WCM_11, IMOM_WCM_12, IMOM_WCM_20, IMOM_WCM_21, IMOM_WCM_30, IMOM_WNCM_02, IMOM_WNCM_03, IMOM_WNCM_11,
     IMOM_WNCM_12, IMOM_WNCM_20, IMOM_WNCM_21, IMOM_WNCM_30, IMOM_WHU1, IMOM_WHU2, IMOM_WHU3, IMOM_WHU4, IMOM_WHU5,
     IMOM_WHU6, IMOM_WHU7,
+    // ChordsFeature (featureset.h:117-132).  In the reference these sixteen sit between STAT_NASSENSTEIN_DIAM_MODE and EULER_NUMBER, and
+    // that is where their table columns are; this mirror numbers them last, so that the codes it had before keep their neighbours.
+    MAXCHORDS_MAX, MAXCHORDS_MAX_ANG, MAXCHORDS_MIN, MAXCHORDS_MIN_ANG, MAXCHORDS_MEDIAN, MAXCHORDS_MEAN, MAXCHORDS_MODE, MAXCHORDS_STDDEV,
+    ALLCHORDS_MAX, ALLCHORDS_MAX_ANG, ALLCHORDS_MIN, ALLCHORDS_MIN_ANG, ALLCHORDS_MEDIAN, ALLCHORDS_MEAN, ALLCHORDS_MODE, ALLCHORDS_STDDEV,
     _COUNT_
 };
 
@@ -228,7 +232,7 @@ inline void reduce_range(uint32_t mask, size_t start, size_t end, std::vector<in
         LR& r = (*roiData)[(*labels)[start + i]];
         lab[i] = (uint32_t)r.label; bw[i] = (uint32_t)r.aabb.get_width(); bh[i] = (uint32_t)r.aabb.get_height();
         mn[i] = r.aux_min; mx[i] = r.aux_max;
-        ox[i] = (uint32_t)r.aabb.get_xmin(); oy[i] = (uint32_t)r.aabb.get_ymin();   // the ROI's position (read by the caliper classes only)
+        ox[i] = (uint32_t)r.aabb.get_xmin(); oy[i] = (uint32_t)r.aabb.get_ymin();   // the ROI's position (read by the caliper classes and the chords)
         for (const Pixel2& p : r.raw_pixels) { x.push_back((uint16_t)(p.x - r.aabb.get_xmin())); y.push_back((uint16_t)(p.y - r.aabb.get_ymin())); inten.push_back(p.inten); }
         off[i + 1] = inten.size();
         if (r.slide_idx >= 0 && (size_t)r.slide_idx < ds.dataset_props.size()) { smin[i] = ds.dataset_props[r.slide_idx].min_preroi_inten; smax[i] = ds.dataset_props[r.slide_idx].max_preroi_inten; }
@@ -258,6 +262,7 @@ inline void reduce_range(uint32_t mask, size_t start, size_t end, std::vector<in
         if (mask & NYXHIP_FAM_FERET) put(Feature2D::MIN_FERET_ANGLE, Feature2D::STAT_FERET_DIAM_MODE, 1);
         if (mask & NYXHIP_FAM_MARTIN) put(Feature2D::STAT_MARTIN_DIAM_MIN, Feature2D::STAT_MARTIN_DIAM_MODE, 1);
         if (mask & NYXHIP_FAM_NASSENSTEIN) put(Feature2D::STAT_NASSENSTEIN_DIAM_MIN, Feature2D::STAT_NASSENSTEIN_DIAM_MODE, 1);
+        if (mask & NYXHIP_FAM_CHORDS) put(Feature2D::MAXCHORDS_MAX, Feature2D::ALLCHORDS_STDDEV, 1);
         if (mask & NYXHIP_FAM_EULER) put(Feature2D::EULER_NUMBER, Feature2D::EULER_NUMBER, 1);
         if (mask & NYXHIP_FAM_ROI_RADIUS) put(Feature2D::ROI_RADIUS_MEAN, Feature2D::ROI_RADIUS_MEDIAN, 1);
         if (mask & NYXHIP_FAM_GLCM) { put(Feature2D::GLCM_ASM, Feature2D::GLCM_VARIANCE, na); put(Feature2D::GLCM_ASM_AVE, Feature2D::GLCM_SUMVARIANCE_AVE, 1); }
@@ -344,6 +349,8 @@ NYXHIP_FAMILY_CLASS(RoiRadiusFeature, NYXHIP_FAM_ROI_RADIUS, ROI_RADIUS_MEAN, RO
 NYXHIP_FAMILY_CLASS(CaliperFeretFeature, NYXHIP_FAM_FERET, MIN_FERET_ANGLE, STAT_FERET_DIAM_MODE)
 NYXHIP_FAMILY_CLASS(CaliperMartinFeature, NYXHIP_FAM_MARTIN, STAT_MARTIN_DIAM_MIN, STAT_MARTIN_DIAM_MODE)
 NYXHIP_FAMILY_CLASS(CaliperNassensteinFeature, NYXHIP_FAM_NASSENSTEIN, STAT_NASSENSTEIN_DIAM_MIN, STAT_NASSENSTEIN_DIAM_MODE)
+// features/chords.h: reads LR::aabb's origin and the cloud in LR::raw_pixels order
+NYXHIP_FAMILY_CLASS(ChordsFeature, NYXHIP_FAM_CHORDS, MAXCHORDS_MAX, ALLCHORDS_STDDEV)
 
 // RadialDistributionFeature (features/radial_distribution.h): its three codes are not contiguous in the enum (GABOR sits
 // between FRAC_AT_D and MEAN_FRAC), so the class is spelled out.  The contour it depends on is built inside the call.
@@ -389,6 +396,7 @@ inline void reduce_trivial_rois_manual(std::vector<int>& PendingRoisLabels, std:
     if (CaliperFeretFeature::required(fs)) mask |= NYXHIP_FAM_FERET;
     if (CaliperMartinFeature::required(fs)) mask |= NYXHIP_FAM_MARTIN;
     if (CaliperNassensteinFeature::required(fs)) mask |= NYXHIP_FAM_NASSENSTEIN;
+    if (ChordsFeature::required(fs)) mask |= NYXHIP_FAM_CHORDS;
     if (EulerNumberFeature::required(fs)) mask |= NYXHIP_FAM_EULER;
     if (RoiRadiusFeature::required(fs)) mask |= NYXHIP_FAM_ROI_RADIUS;
     if (GLCMFeature::required(fs)) mask |= NYXHIP_FAM_GLCM;

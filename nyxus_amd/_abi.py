@@ -39,6 +39,9 @@ FAM_FERET = 1 << 18           # CaliperFeretFeature (MIN_FERET_ANGLE, MAX_FERET_
 FAM_MARTIN = 1 << 19          # CaliperMartinFeature (STAT_MARTIN_DIAM_*)
 FAM_NASSENSTEIN = 1 << 20     # CaliperNassensteinFeature (STAT_NASSENSTEIN_DIAM_*)
 FAM_CALIPER = FAM_FERET | FAM_MARTIN | FAM_NASSENSTEIN
+FAM_CHORDS = 1 << 21          # ChordsFeature (MAXCHORDS_*, ALLCHORDS_*; columns between the Nassenstein columns and EULER_NUMBER); not part
+                              # of FAM_ALL; reads the ROI origin like the caliper classes
+FAM_NEEDS_ORIGIN = FAM_CALIPER | FAM_CHORDS
 FAM_NORTH_STAR = 0x7F
 FAM_ALL = 0xFFF
 

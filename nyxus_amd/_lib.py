@@ -190,9 +190,9 @@ class Context:
         ncol = self.n_columns(mask, s)
         out = np.empty((batch.n_roi, ncol), np.float64)
         cb = batch.c_struct()
-        if (mask & _abi.FAM_CALIPER) and batch.origin_unrepresentable:
-            raise ValueError("the caliper families need the ROIs' origins, and this batch's lie below 0 or beyond 32 bits")
-        if batch.origin_x is not None:           # the ROIs' positions: read by the caliper families only
+        if (mask & _abi.FAM_NEEDS_ORIGIN) and batch.origin_unrepresentable:
+            raise ValueError("the caliper families and the chords need the ROIs' origins, and this batch's lie below 0 or beyond 32 bits")
+        if batch.origin_x is not None:           # the ROIs' positions: read by the caliper families and the chords
             self._check(self._lib.nyxhip_featurize_batch_at(self._h, C.byref(cb), batch.origin_x.ctypes.data, batch.origin_y.ctypes.data, mask,
                                                             C.byref(s), out.ctypes.data, ncol))
         else:

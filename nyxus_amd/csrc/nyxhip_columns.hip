@@ -103,6 +103,11 @@ std::vector<std::string> column_names(uint32_t mask, const nyxhip_settings* s)
         if (mask & NYXHIP_FAM_NASSENSTEIN)
             for (auto k : st) v.push_back(std::string("STAT_NASSENSTEIN_DIAM_") + k);
     }
+    if (mask & NYXHIP_FAM_CHORDS) {   // ChordsFeature (featureset.h:117-132; names: featureset.cpp:205-220)
+        const char* st[8] = {"MAX", "MAX_ANG", "MIN", "MIN_ANG", "MEDIAN", "MEAN", "MODE", "STDDEV"};
+        for (auto g : {"MAXCHORDS_", "ALLCHORDS_"})
+            for (auto k : st) v.push_back(std::string(g) + k);
+    }
     if (mask & NYXHIP_FAM_EULER) v.push_back("EULER_NUMBER");
     if (mask & NYXHIP_FAM_ROI_RADIUS) { v.push_back("ROI_RADIUS_MEAN"); v.push_back("ROI_RADIUS_MAX"); v.push_back("ROI_RADIUS_MEDIAN"); }
     if (mask & NYXHIP_FAM_GLCM) {
@@ -201,6 +206,7 @@ int nyxhip_n_columns(uint32_t family_mask, const nyxhip_settings* s)
     if (family_mask & NYXHIP_FAM_FERET) n += kFeretCols;
     if (family_mask & NYXHIP_FAM_MARTIN) n += kMartinCols;
     if (family_mask & NYXHIP_FAM_NASSENSTEIN) n += kNassensteinCols;
+    if (family_mask & NYXHIP_FAM_CHORDS) n += kChordsCols;
     if (family_mask & NYXHIP_FAM_EULER) n += kEulerCols;
     if (family_mask & NYXHIP_FAM_ROI_RADIUS) n += kRoiRadiusCols;
     if (family_mask & NYXHIP_FAM_GLCM) n += kGlcmAngled * s->glcm_n_angles + kGlcmAve;

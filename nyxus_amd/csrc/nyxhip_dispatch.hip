@@ -511,6 +511,64 @@ int launch_caliper(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t mask, const 
     return NYXHIP_OK;
 }
 
+// ChordsFeature (roi_chords.hip) on `st`: one workgroup per ROI over the pixel clouds, no contour.  Columns: between the Nassenstein
+// columns and EULER_NUMBER.  The origins are those the entry point left in the context (NULL: (0, 0)).  ROIs whose rotated bit plane
+// may exceed the LDS plane, and ROIs with zero-intensity pixels (min_inten == 0), go through a classifier and a list launch over
+// global planes.  Which ROIs those are is known on the device only: the classifier's three counters are read back on every call
+// (one stream synchronisation, as the caliper and outline kernels have for their wide boxes).
+int launch_chords(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t mask, const nyxhip_settings* s, double* d_out, size_t ld, uint32_t max_side,
+                  hipStream_t st)
+{
+    ChordArgs ca;
+    memset(&ca, 0, sizeof(ca));
+    ca.n_roi = b->n_roi;
+    ca.px_offset = b->px_offset; ca.x = b->x; ca.y = b->y; ca.inten = b->inten; ca.bbox_w = b->bbox_w; ca.bbox_h = b->bbox_h;
+    ca.min_inten = b->min_inten;
+    ca.origin_x = ctx->origin_x_next; ca.origin_y = ctx->origin_y_next;
+    ca.out = d_out; ca.ld = ld; ca.status = ctx->d_status.as<int>();
+    ca.col0 = nyxhip_n_columns(mask & (NYXHIP_FAM_INTENSITY | NYXHIP_FAM_FRACTAL | kCaliper), s);
+    // the reference's loop (chords.cpp:22-23) and its expressions (rotation.cpp:70-82: the angle is passed as float) on the host's libm
+    {
+        const double step = M_PI / double(kChordsAngles);
+        int k = 0;
+        for (double ang = 0; ang < M_PI && k < kChordsAngles; ang += step, k++) {
+            const float theta = (float)ang;
+            ca.ang[k] = ang; ca.sn[k] = std::sin((double)theta); ca.cs[k] = std::cos((double)theta);
+        }
+        if (k != kChordsAngles)
+            return fail(ctx, NYXHIP_ERR_HIP, "chords: the angle loop did not give 20 angles");
+    }
+    const uint32_t side = std::min<uint32_t>(std::max<uint32_t>(max_side, 1u), 65535u);
+    ca.lds_words = (uint32_t)std::min<uint64_t>(kChordsLdsWords, chords_plane_words(side, side));
+    const size_t list_bytes = 4ull * b->n_roi + 512;
+    HIP_TRY(ctx, ctx->d_chords_list.reserve(list_bytes, st));
+    uint32_t* d_hdr = ctx->d_chords_list.as<uint32_t>();
+    uint32_t* d_list = d_hdr + 64;
+    HIP_TRY(ctx, hipMemsetAsync(d_hdr, 0, 12, st));
+    if (launch_chords_classify(b->n_roi, b->bbox_w, b->bbox_h, b->min_inten, ca.lds_words, d_list, d_hdr, st) != 0)
+        return fail(ctx, NYXHIP_ERR_HIP, "chords classifier: launch failed");
+    if (launch_roi_chords(ca, st, (uint32_t)b->n_roi) != 0)
+        return fail(ctx, NYXHIP_ERR_HIP, "chords kernel: launch failed");
+    uint32_t hdr[3] = {0, 0, 0};
+    HIP_TRY(ctx, hipMemcpyAsync(hdr, d_hdr, 12, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    const uint32_t n_list = hdr[0];
+    if (!n_list) return NYXHIP_OK;
+    ChordArgs cw = ca;
+    cw.ws_words = ((uint64_t)hdr[1] + 63) & ~63ull;
+    cw.ws_cells = ((uint64_t)hdr[2] * hdr[2] + 63) & ~63ull;
+    const uint64_t stride = 4ull * (cw.ws_words + cw.ws_cells);
+    const uint32_t chunk = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(n_list, ((uint64_t)1 << 30) / stride));
+    HIP_TRY(ctx, ctx->d_chords_ws.reserve((size_t)(stride * chunk), st));
+    cw.ws = ctx->d_chords_ws.as<uint32_t>();
+    for (uint32_t o = 0; o < n_list; o += chunk) {
+        cw.roi_index = d_list + o;
+        if (launch_roi_chords(cw, st, std::min(chunk, n_list - o)) != 0)
+            return fail(ctx, NYXHIP_ERR_HIP, "chords kernel: launch failed");
+    }
+    return NYXHIP_OK;
+}
+
 // Contour (roi_moments.hip) + the families that read it: the 2-D geometric moments (roi_moments.hip) and the radial intensity
 // distribution (roi_radial.hip).  The contour of every ROI goes to a context-owned workspace at the ROI's CSR offset (a contour
 // never has more points than the ROI has pixels) ONCE per call; the moments kernel and / or the radial kernel read it back.
@@ -530,7 +588,7 @@ int launch_contour_families(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t mas
         oa.fams = mask & kOutline;
         oa.has_contour = need_contour ? 1u : 0u;
         oa.col_fractal = nyxhip_n_columns(mask & NYXHIP_FAM_INTENSITY, s);
-        oa.col_euler = oa.col_fractal + ((mask & NYXHIP_FAM_FRACTAL) ? kFractalCols : 0) + nyxhip_n_columns(mask & kCaliper, s);   // (enum order)
+        oa.col_euler = oa.col_fractal + ((mask & NYXHIP_FAM_FRACTAL) ? kFractalCols : 0) + nyxhip_n_columns(mask & (kCaliper | NYXHIP_FAM_CHORDS), s);   // (enum order)
         oa.col_radius = oa.col_euler + ((mask & NYXHIP_FAM_EULER) ? kEulerCols : 0);
         if (mask & (NYXHIP_FAM_FRACTAL | NYXHIP_FAM_EULER)) {
             // bound of outline_bit_words over boxes of at most max_area cells and max_side a side: rows of w / 32 + 1 words, the pyramid
@@ -572,8 +630,10 @@ int launch_contour_families(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t mas
     };
     if (mask & kCaliper)
         if (int crc = launch_caliper(ctx, b, mask, s, d_out, ld, max_side, st)) return crc;
+    if (mask & NYXHIP_FAM_CHORDS)
+        if (int crc = launch_chords(ctx, b, mask, s, d_out, ld, max_side, st)) return crc;
     if (!need_contour && !do_out)
-        return NYXHIP_OK;                                  // the caliper classes alone
+        return NYXHIP_OK;                                  // the caliper classes / the chords alone
     if (!need_contour) {
         // EULER_NUMBER alone: no contour, no staged pixels -- the bit plane only
         MomArgs& m = oa.m;
@@ -1827,7 +1887,7 @@ int validate(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t mask, const nyxhip
 {
     if (!ctx) return NYXHIP_ERR_INVALID_ARG;
     if (!b || !s || !out) return fail(ctx, NYXHIP_ERR_INVALID_ARG, "null batch / settings / out_table");
-    if (mask == 0 || (mask & ~(NYXHIP_FAM_ALL | NYXHIP_FAM_RADIAL | kOutline | kCaliper))) return fail(ctx, NYXHIP_ERR_INVALID_ARG, "bad family mask");
+    if (mask == 0 || (mask & ~(NYXHIP_FAM_ALL | NYXHIP_FAM_RADIAL | kOutline | kCaliper | NYXHIP_FAM_CHORDS))) return fail(ctx, NYXHIP_ERR_INVALID_ARG, "bad family mask");
     if (mask & ~kImplemented)
         return fail(ctx, NYXHIP_ERR_UNSUPPORTED, "requested feature family is not implemented by the HIP path yet "
                     "(all seven hot-path families are implemented; bad mask?)");

@@ -109,6 +109,12 @@ for _n in MARTIN:
 for _n in NASSENSTEIN:
     FAMILY_OF[_n] = _abi.FAM_NASSENSTEIN
 
+# ChordsFeature (featureset.h:117-132): between STAT_NASSENSTEIN_DIAM_MODE and EULER_NUMBER.  No group token, for the same reason.
+_STAT8 = ["MAX", "MAX_ANG", "MIN", "MIN_ANG", "MEDIAN", "MEAN", "MODE", "STDDEV"]
+CHORDS = ["MAXCHORDS_" + k for k in _STAT8] + ["ALLCHORDS_" + k for k in _STAT8]
+for _n in CHORDS:
+    FAMILY_OF[_n] = _abi.FAM_CHORDS
+
 # group tokens (featureset.cpp:650-665) the HIP path can serve completely (the radial distribution has none, featureset.cpp:650-668)
 GROUPS: Dict[str, List[str]] = {
     "*ALL_INTENSITY*": INTENSITY,
@@ -130,8 +136,12 @@ ENUM_ORDER: List[str] = (INTENSITY + GLCM_ANGLED + GLCM_AVE + GLRLM_ANGLED + GLR
 # ... and the order expand() returns codes in: ENUM_ORDER with the shape-block codes at their enum position (ENUM_ORDER itself
 # keeps the codes of the twelve FAM_ALL families and the radial distribution)
 OUTPUT_ORDER: List[str] = INTENSITY + FRACTAL + EULER + ROI_RADIUS + ENUM_ORDER[len(INTENSITY):]
-# every served code in true enum order: OUTPUT_ORDER with the caliper codes behind FRACT_DIM_PERIMETER.  expand() orders by this list.
+# every served code in true enum order: OUTPUT_ORDER with the caliper codes behind FRACT_DIM_PERIMETER.
 SERVED_ORDER: List[str] = INTENSITY + FRACTAL + FERET + MARTIN + NASSENSTEIN + OUTPUT_ORDER[len(INTENSITY) + len(FRACTAL):]
+# ... and SERVED_ORDER with the chords codes behind STAT_NASSENSTEIN_DIAM_MODE (SERVED_ORDER keeps the codes it was introduced with,
+# like ENUM_ORDER and OUTPUT_ORDER before it).  expand() orders by this list.
+_K = len(INTENSITY) + len(FRACTAL) + len(FERET) + len(MARTIN) + len(NASSENSTEIN)
+CATALOGUE_ORDER: List[str] = SERVED_ORDER[:_K] + CHORDS + SERVED_ORDER[_K:]
 
 
 def expand(features: List[str]) -> Tuple[int, List[str]]:
@@ -151,10 +161,11 @@ def expand(features: List[str]) -> Tuple[int, List[str]]:
             f"feature(s) {unknown} are not served by the MI355X path. Implemented: groups {sorted(GROUPS)} and the "
             f"individual features of the intensity, GLCM, GLRLM, GLDZM, GLSZM, GLDM, NGLDM and NGTDM families, GABOR, ZERNIKE2D, "
             f"FRAC_AT_D, MEAN_FRAC, RADIAL_CV, FRACT_DIM_BOXCOUNT, FRACT_DIM_PERIMETER, EULER_NUMBER, ROI_RADIUS_MEAN, ROI_RADIUS_MAX, "
-            f"ROI_RADIUS_MEDIAN, MIN_FERET_ANGLE, MAX_FERET_ANGLE and STAT_{{FERET,MARTIN,NASSENSTEIN}}_DIAM_{{MIN,MAX,MEAN,MEDIAN,STDDEV,MODE}}")
+            f"ROI_RADIUS_MEDIAN, MIN_FERET_ANGLE, MAX_FERET_ANGLE and STAT_{{FERET,MARTIN,NASSENSTEIN}}_DIAM_{{MIN,MAX,MEAN,MEDIAN,STDDEV,MODE}}, "
+            f"{{MAXCHORDS,ALLCHORDS}}_{{MAX,MAX_ANG,MIN,MIN_ANG,MEDIAN,MEAN,MODE,STDDEV}}")
     if not want:
         raise ValueError("no features requested")
-    ordered = [n for n in SERVED_ORDER if n in want]
+    ordered = [n for n in CATALOGUE_ORDER if n in want]
     mask = 0
     for n in ordered:
         mask |= FAMILY_OF[n]
