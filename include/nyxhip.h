@@ -87,6 +87,14 @@ enum {
      * Reads the intensities only for "zero or not" (a zero-intensity pixel is a hole, image_matrix.cpp:206-237) and relies on
      * nyxhip_batch::min_inten to tell whether an ROI has any.  An ROI without a closed chord has 16 zeros (chords.cpp:59-60). */
     NYXHIP_FAM_CHORDS    = 1u << 21, /* 16 columns: MAXCHORDS_{MAX,MAX_ANG,MIN,MIN_ANG,MEDIAN,MEAN,MODE,STDDEV}, then the same eight for ALLCHORDS */
+    /* EllipseFittingFeature (featureset.h:62-68, features/ellipse_fitting.h): Legendre's ellipse of inertia of the pixel cloud.  Not part of
+     * NYXHIP_FAM_ALL.  Columns directly behind the intensity block, in front of EROSIONS_2_VANISH / FRACT_DIM_BOXCOUNT (enum order).
+     * Reads coordinates only (no intensities, no origin: central moments do not move with the box); no column can be NaN. */
+    NYXHIP_FAM_ELLIPSE   = 1u << 22, /* 6 columns: MAJOR_AXIS_LENGTH, MINOR_AXIS_LENGTH, ELONGATION, ECCENTRICITY, ORIENTATION, ROUNDNESS */
+    /* ErosionPixelsFeature (featureset.h:85-86, features/erosion.h): erosions of the box mask by the 3 x 3 cross until nothing is left
+     * (at most 1000).  Not part of NYXHIP_FAM_ALL.  Columns behind ROUNDNESS, in front of FRACT_DIM_BOXCOUNT.  Relies on
+     * nyxhip_batch::min_inten / max_inten: an ROI with min_inten == max_inten is skipped, as the reference's driver does, and has 0. */
+    NYXHIP_FAM_EROSION   = 1u << 23, /* 2 columns: EROSIONS_2_VANISH, EROSIONS_2_VANISH_COMPLEMENT (never assigned by the class: 0) */
     NYXHIP_FAM_NORTH_STAR = 0x7Fu,  /* the seven families of BASELINE.json's north_star */
     NYXHIP_FAM_ALL       = 0xFFFu
 };

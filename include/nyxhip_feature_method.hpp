@@ -103,6 +103,10 @@ enum class Feature2D : int {
     // that is where their table columns are; this mirror numbers them last, so that the codes it had before keep their neighbours.
     MAXCHORDS_MAX, MAXCHORDS_MAX_ANG, MAXCHORDS_MIN, MAXCHORDS_MIN_ANG, MAXCHORDS_MEDIAN, MAXCHORDS_MEAN, MAXCHORDS_MODE, MAXCHORDS_STDDEV,
     ALLCHORDS_MAX, ALLCHORDS_MAX_ANG, ALLCHORDS_MIN, ALLCHORDS_MIN_ANG, ALLCHORDS_MEDIAN, ALLCHORDS_MEAN, ALLCHORDS_MODE, ALLCHORDS_STDDEV,
+    // EllipseFittingFeature (featureset.h:62-68) and ErosionPixelsFeature (:85-86).  In the reference these eight sit behind the intensity
+    // block, in front of FRACT_DIM_BOXCOUNT, and that is where their table columns are; numbered last here for the same reason.
+    MAJOR_AXIS_LENGTH, MINOR_AXIS_LENGTH, ELONGATION, ECCENTRICITY, ORIENTATION, ROUNDNESS,
+    EROSIONS_2_VANISH, EROSIONS_2_VANISH_COMPLEMENT,
     _COUNT_
 };
 
@@ -258,6 +262,8 @@ inline void reduce_range(uint32_t mask, size_t start, size_t end, std::vector<in
             for (int f = (int)first; f <= (int)last; f++) { r.fvals[f].assign(p, p + width); p += width; }
         };
         if (mask & NYXHIP_FAM_INTENSITY) put(Feature2D::COV, Feature2D::UNIFORMITY_PIU, 1);
+        if (mask & NYXHIP_FAM_ELLIPSE) put(Feature2D::MAJOR_AXIS_LENGTH, Feature2D::ROUNDNESS, 1);
+        if (mask & NYXHIP_FAM_EROSION) put(Feature2D::EROSIONS_2_VANISH, Feature2D::EROSIONS_2_VANISH_COMPLEMENT, 1);
         if (mask & NYXHIP_FAM_FRACTAL) put(Feature2D::FRACT_DIM_BOXCOUNT, Feature2D::FRACT_DIM_PERIMETER, 1);
         if (mask & NYXHIP_FAM_FERET) put(Feature2D::MIN_FERET_ANGLE, Feature2D::STAT_FERET_DIAM_MODE, 1);
         if (mask & NYXHIP_FAM_MARTIN) put(Feature2D::STAT_MARTIN_DIAM_MIN, Feature2D::STAT_MARTIN_DIAM_MODE, 1);
@@ -351,6 +357,9 @@ NYXHIP_FAMILY_CLASS(CaliperMartinFeature, NYXHIP_FAM_MARTIN, STAT_MARTIN_DIAM_MI
 NYXHIP_FAMILY_CLASS(CaliperNassensteinFeature, NYXHIP_FAM_NASSENSTEIN, STAT_NASSENSTEIN_DIAM_MIN, STAT_NASSENSTEIN_DIAM_MODE)
 // features/chords.h: reads LR::aabb's origin and the cloud in LR::raw_pixels order
 NYXHIP_FAMILY_CLASS(ChordsFeature, NYXHIP_FAM_CHORDS, MAXCHORDS_MAX, ALLCHORDS_STDDEV)
+// features/ellipse_fitting.h, features/erosion.h: the pixel cloud only; the erosion's skip reads LR::aux_min / aux_max
+NYXHIP_FAMILY_CLASS(EllipseFittingFeature, NYXHIP_FAM_ELLIPSE, MAJOR_AXIS_LENGTH, ROUNDNESS)
+NYXHIP_FAMILY_CLASS(ErosionPixelsFeature, NYXHIP_FAM_EROSION, EROSIONS_2_VANISH, EROSIONS_2_VANISH_COMPLEMENT)
 
 // RadialDistributionFeature (features/radial_distribution.h): its three codes are not contiguous in the enum (GABOR sits
 // between FRAC_AT_D and MEAN_FRAC), so the class is spelled out.  The contour it depends on is built inside the call.
@@ -397,6 +406,8 @@ inline void reduce_trivial_rois_manual(std::vector<int>& PendingRoisLabels, std:
     if (CaliperMartinFeature::required(fs)) mask |= NYXHIP_FAM_MARTIN;
     if (CaliperNassensteinFeature::required(fs)) mask |= NYXHIP_FAM_NASSENSTEIN;
     if (ChordsFeature::required(fs)) mask |= NYXHIP_FAM_CHORDS;
+    if (EllipseFittingFeature::required(fs)) mask |= NYXHIP_FAM_ELLIPSE;
+    if (ErosionPixelsFeature::required(fs)) mask |= NYXHIP_FAM_EROSION;
     if (EulerNumberFeature::required(fs)) mask |= NYXHIP_FAM_EULER;
     if (RoiRadiusFeature::required(fs)) mask |= NYXHIP_FAM_ROI_RADIUS;
     if (GLCMFeature::required(fs)) mask |= NYXHIP_FAM_GLCM;

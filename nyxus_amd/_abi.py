@@ -42,6 +42,8 @@ FAM_CALIPER = FAM_FERET | FAM_MARTIN | FAM_NASSENSTEIN
 FAM_CHORDS = 1 << 21          # ChordsFeature (MAXCHORDS_*, ALLCHORDS_*; columns between the Nassenstein columns and EULER_NUMBER); not part
                               # of FAM_ALL; reads the ROI origin like the caliper classes
 FAM_NEEDS_ORIGIN = FAM_CALIPER | FAM_CHORDS
+FAM_ELLIPSE = 1 << 22         # EllipseFittingFeature (MAJOR_AXIS_LENGTH .. ROUNDNESS; columns directly behind the intensity block); not part of FAM_ALL
+FAM_EROSION = 1 << 23         # ErosionPixelsFeature (EROSIONS_2_VANISH, EROSIONS_2_VANISH_COMPLEMENT; behind ROUNDNESS); not part of FAM_ALL
 FAM_NORTH_STAR = 0x7F
 FAM_ALL = 0xFFF
 

@@ -91,6 +91,9 @@ std::vector<std::string> column_names(uint32_t mask, const nyxhip_settings* s)
     if (mask & NYXHIP_FAM_INTENSITY)
         for (auto n : kIntensityNames) v.push_back(n);
     // the shape block follows the intensity block (featureset.h:46-160)
+    if (mask & NYXHIP_FAM_ELLIPSE)    // EllipseFittingFeature (featureset.h:62-68)
+        for (auto n : {"MAJOR_AXIS_LENGTH", "MINOR_AXIS_LENGTH", "ELONGATION", "ECCENTRICITY", "ORIENTATION", "ROUNDNESS"}) v.push_back(n);
+    if (mask & NYXHIP_FAM_EROSION) { v.push_back("EROSIONS_2_VANISH"); v.push_back("EROSIONS_2_VANISH_COMPLEMENT"); }   // featureset.h:85-86
     if (mask & NYXHIP_FAM_FRACTAL) { v.push_back("FRACT_DIM_BOXCOUNT"); v.push_back("FRACT_DIM_PERIMETER"); }
     {   // the caliper classes (featureset.h:93-114; names: featureset.cpp:181-203)
         const char* st[6] = {"MIN", "MAX", "MEAN", "MEDIAN", "STDDEV", "MODE"};
@@ -202,6 +205,8 @@ int nyxhip_n_columns(uint32_t family_mask, const nyxhip_settings* s)
     if (!s) return 0;
     int n = 0;
     if (family_mask & NYXHIP_FAM_INTENSITY) n += kIntensityCols;
+    if (family_mask & NYXHIP_FAM_ELLIPSE) n += kEllipseCols;
+    if (family_mask & NYXHIP_FAM_EROSION) n += kErosionCols;
     if (family_mask & NYXHIP_FAM_FRACTAL) n += kFractalCols;
     if (family_mask & NYXHIP_FAM_FERET) n += kFeretCols;
     if (family_mask & NYXHIP_FAM_MARTIN) n += kMartinCols;

@@ -23,6 +23,7 @@
 #include "roi_outline.h"
 #include "roi_caliper.h"
 #include "roi_chords.h"
+#include "roi_erosion.h"
 
 // One hipMalloc allocation, grow-only.  hipFree waits for the device's work by itself; the stream handed to reserve() states which
 // work the site knows to be using the old block.
@@ -151,6 +152,9 @@ struct nyxhip_ctx {
     // chords kernel (roi_chords.hip): list of the ROIs served on global planes (plane beyond LDS, or zero-intensity pixels), and the planes
     DevBuf d_chords_list;
     DevBuf d_chords_ws;
+    // erosion kernel (roi_erosion.hip): list of the ROIs whose two bit planes exceed the LDS planes, and their global planes
+    DevBuf d_erosion_list;
+    DevBuf d_erosion_ws;
     const uint32_t* origin_x_next = nullptr;   // set by nyxhip_featurize_batch[_async]_at and the tile path for their next launch_device call:
     const uint32_t* origin_y_next = nullptr;   // device arrays [n_roi] of the ROIs' box origins (NULL: (0, 0))
     // grow-only workspaces of the fused tile path: scan tables + rows | clouds | two staging slots for host tiles
@@ -223,9 +227,10 @@ constexpr uint32_t kOutline = NYXHIP_FAM_FRACTAL | NYXHIP_FAM_EULER | NYXHIP_FAM
 // families that read the ROI's ordered contour (launch_contour_families)
 constexpr uint32_t kContourFams = kMoments | NYXHIP_FAM_RADIAL | NYXHIP_FAM_FRACTAL | NYXHIP_FAM_ROI_RADIUS;
 constexpr uint32_t kCaliper = NYXHIP_FAM_FERET | NYXHIP_FAM_MARTIN | NYXHIP_FAM_NASSENSTEIN;   // roi_caliper.hip; their columns follow FRACT_DIM_PERIMETER
-constexpr uint32_t kBehindIntensity = kOutline | kCaliper | NYXHIP_FAM_CHORDS;   // families whose columns lie between the intensity block and GLCM
-constexpr uint32_t kTailFams = kContourFams | NYXHIP_FAM_EULER | kCaliper | NYXHIP_FAM_CHORDS;   // ... and everything else launch_contour_families serves (no size classes)
-constexpr uint32_t kImplemented = NYXHIP_FAM_INTENSITY | NYXHIP_FAM_GLCM | kTexture | kShape | kDependence | kMoments | NYXHIP_FAM_RADIAL | kOutline | kCaliper | NYXHIP_FAM_CHORDS;
+constexpr uint32_t kEllipseErosion = NYXHIP_FAM_ELLIPSE | NYXHIP_FAM_EROSION;   // roi_erosion.hip; their columns follow the intensity block, in front of kOutline's
+constexpr uint32_t kBehindIntensity = kOutline | kCaliper | NYXHIP_FAM_CHORDS | kEllipseErosion;   // families whose columns lie between the intensity block and GLCM
+constexpr uint32_t kTailFams = kContourFams | NYXHIP_FAM_EULER | kCaliper | NYXHIP_FAM_CHORDS | kEllipseErosion;   // ... and everything else launch_contour_families serves (no size classes)
+constexpr uint32_t kImplemented = NYXHIP_FAM_INTENSITY | NYXHIP_FAM_GLCM | kTexture | kShape | kDependence | kMoments | NYXHIP_FAM_RADIAL | kOutline | kCaliper | NYXHIP_FAM_CHORDS | kEllipseErosion;
 
 namespace nyxhip __attribute__((visibility("hidden"))) {
 

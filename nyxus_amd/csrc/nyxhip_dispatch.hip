@@ -471,7 +471,7 @@ int launch_caliper(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t mask, const 
     ca.origin_x = ctx->origin_x_next; ca.origin_y = ctx->origin_y_next;
     ca.out = d_out; ca.ld = ld; ca.status = ctx->d_status.as<int>();
     ca.fams = mask & kCaliper;
-    ca.col_feret = nyxhip_n_columns(mask & (NYXHIP_FAM_INTENSITY | NYXHIP_FAM_FRACTAL), s);
+    ca.col_feret = nyxhip_n_columns(mask & (NYXHIP_FAM_INTENSITY | kEllipseErosion | NYXHIP_FAM_FRACTAL), s);
     ca.col_martin = ca.col_feret + ((mask & NYXHIP_FAM_FERET) ? kFeretCols : 0);
     ca.col_nassenstein = ca.col_martin + ((mask & NYXHIP_FAM_MARTIN) ? kMartinCols : 0);
     ca.soft_nan = s->soft_nan;
@@ -526,7 +526,7 @@ int launch_chords(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t mask, const n
     ca.min_inten = b->min_inten;
     ca.origin_x = ctx->origin_x_next; ca.origin_y = ctx->origin_y_next;
     ca.out = d_out; ca.ld = ld; ca.status = ctx->d_status.as<int>();
-    ca.col0 = nyxhip_n_columns(mask & (NYXHIP_FAM_INTENSITY | NYXHIP_FAM_FRACTAL | kCaliper), s);
+    ca.col0 = nyxhip_n_columns(mask & (NYXHIP_FAM_INTENSITY | kEllipseErosion | NYXHIP_FAM_FRACTAL | kCaliper), s);
     // the reference's loop (chords.cpp:22-23) and its expressions (rotation.cpp:70-82: the angle is passed as float) on the host's libm
     {
         const double step = M_PI / double(kChordsAngles);
@@ -569,6 +569,61 @@ int launch_chords(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t mask, const n
     return NYXHIP_OK;
 }
 
+// EllipseFittingFeature and ErosionPixelsFeature (roi_erosion.hip) on `st`, over the pixel clouds: no contour, no origin.  Columns:
+// directly behind the intensity block.  The ellipse sums take a wave per ROI, and a workgroup per ROI of more than kEllipseWavePx
+// pixels when the batch can hold one.  The erosion takes a workgroup per ROI with its two bit planes in LDS; when the batch's extrema
+// allow a box beyond kErosionLdsWords, those ROIs go through a classifier and a list launch over global planes (the pattern of
+// launch_caliper: one read-back, and only then).
+int launch_ellipse_erosion(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t mask, const nyxhip_settings* s, double* d_out, size_t ld, uint32_t max_px,
+                           uint32_t max_area, uint32_t max_side, hipStream_t st)
+{
+    EroArgs ea;
+    memset(&ea, 0, sizeof(ea));
+    ea.n_roi = b->n_roi;
+    ea.px_offset = b->px_offset; ea.x = b->x; ea.y = b->y; ea.bbox_w = b->bbox_w; ea.bbox_h = b->bbox_h;
+    ea.min_inten = b->min_inten; ea.max_inten = b->max_inten;
+    ea.out = d_out; ea.ld = ld; ea.status = ctx->d_status.as<int>();
+    ea.col_ellipse = nyxhip_n_columns(mask & NYXHIP_FAM_INTENSITY, s);
+    ea.col_erosion = ea.col_ellipse + ((mask & NYXHIP_FAM_ELLIPSE) ? kEllipseCols : 0);
+    if (mask & NYXHIP_FAM_ELLIPSE) {
+        const uint32_t most = max_px ? max_px : max_area;                      // (a batch without a stated pixel maximum: no ROI has more than its box)
+        if (launch_roi_ellipse(ea, st, most > kEllipseWavePx) != 0)
+            return fail(ctx, NYXHIP_ERR_HIP, "ellipse kernel: launch failed");
+    }
+    if (!(mask & NYXHIP_FAM_EROSION)) return NYXHIP_OK;
+    // bound of two planes over boxes of at most max_area cells and max_side a side: (w / 32 + 1) * h <= area / 32 + side
+    const uint64_t bound = std::max<uint64_t>(2ull * ((uint64_t)max_area / 32u + max_side), 2u);
+    ea.lds_words = (uint32_t)std::min<uint64_t>(kErosionLdsWords, bound);
+    ea.defer_large = bound > kErosionLdsWords ? 1u : 0u;
+    if (launch_roi_erosion(ea, st, (uint32_t)b->n_roi) != 0)
+        return fail(ctx, NYXHIP_ERR_HIP, "erosion kernel: launch failed");
+    if (!ea.defer_large) return NYXHIP_OK;
+    const size_t list_bytes = 4ull * b->n_roi + 512;
+    HIP_TRY(ctx, ctx->d_erosion_list.reserve(list_bytes, st));
+    uint32_t* d_hdr = ctx->d_erosion_list.as<uint32_t>();
+    uint32_t* d_list = d_hdr + 64;
+    HIP_TRY(ctx, hipMemsetAsync(d_hdr, 0, 8, st));
+    if (launch_erosion_classify(b->n_roi, b->bbox_w, b->bbox_h, ea.lds_words, d_list, d_hdr, st) != 0)
+        return fail(ctx, NYXHIP_ERR_HIP, "erosion classifier: launch failed");
+    uint32_t hdr[2] = {0, 0};
+    HIP_TRY(ctx, hipMemcpyAsync(hdr, d_hdr, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    const uint32_t n_list = hdr[0];
+    if (!n_list) return NYXHIP_OK;
+    EroArgs ew = ea;
+    ew.defer_large = 0;
+    ew.ws_stride = (2ull * hdr[1] + 63) & ~63ull;
+    const uint32_t chunk = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(n_list, ((uint64_t)1 << 30) / (4 * ew.ws_stride)));
+    HIP_TRY(ctx, ctx->d_erosion_ws.reserve((size_t)(4 * ew.ws_stride * chunk), st));
+    ew.ws = ctx->d_erosion_ws.as<uint32_t>();
+    for (uint32_t o = 0; o < n_list; o += chunk) {
+        ew.roi_index = d_list + o;
+        if (launch_roi_erosion(ew, st, std::min(chunk, n_list - o)) != 0)
+            return fail(ctx, NYXHIP_ERR_HIP, "erosion kernel: launch failed");
+    }
+    return NYXHIP_OK;
+}
+
 // Contour (roi_moments.hip) + the families that read it: the 2-D geometric moments (roi_moments.hip) and the radial intensity
 // distribution (roi_radial.hip).  The contour of every ROI goes to a context-owned workspace at the ROI's CSR offset (a contour
 // never has more points than the ROI has pixels) ONCE per call; the moments kernel and / or the radial kernel read it back.
@@ -587,7 +642,7 @@ int launch_contour_families(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t mas
     if (do_out) {
         oa.fams = mask & kOutline;
         oa.has_contour = need_contour ? 1u : 0u;
-        oa.col_fractal = nyxhip_n_columns(mask & NYXHIP_FAM_INTENSITY, s);
+        oa.col_fractal = nyxhip_n_columns(mask & (NYXHIP_FAM_INTENSITY | kEllipseErosion), s);   // (the ellipse and erosion columns precede it)
         oa.col_euler = oa.col_fractal + ((mask & NYXHIP_FAM_FRACTAL) ? kFractalCols : 0) + nyxhip_n_columns(mask & (kCaliper | NYXHIP_FAM_CHORDS), s);   // (enum order)
         oa.col_radius = oa.col_euler + ((mask & NYXHIP_FAM_EULER) ? kEulerCols : 0);
         if (mask & (NYXHIP_FAM_FRACTAL | NYXHIP_FAM_EULER)) {
@@ -632,8 +687,10 @@ int launch_contour_families(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t mas
         if (int crc = launch_caliper(ctx, b, mask, s, d_out, ld, max_side, st)) return crc;
     if (mask & NYXHIP_FAM_CHORDS)
         if (int crc = launch_chords(ctx, b, mask, s, d_out, ld, max_side, st)) return crc;
+    if (mask & kEllipseErosion)
+        if (int crc = launch_ellipse_erosion(ctx, b, mask, s, d_out, ld, max_px, max_area, max_side, st)) return crc;
     if (!need_contour && !do_out)
-        return NYXHIP_OK;                                  // the caliper classes / the chords alone
+        return NYXHIP_OK;                                  // the caliper classes / the chords / the ellipse and erosion classes alone
     if (!need_contour) {
         // EULER_NUMBER alone: no contour, no staged pixels -- the bit plane only
         MomArgs& m = oa.m;
@@ -1887,7 +1944,7 @@ int validate(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t mask, const nyxhip
 {
     if (!ctx) return NYXHIP_ERR_INVALID_ARG;
     if (!b || !s || !out) return fail(ctx, NYXHIP_ERR_INVALID_ARG, "null batch / settings / out_table");
-    if (mask == 0 || (mask & ~(NYXHIP_FAM_ALL | NYXHIP_FAM_RADIAL | kOutline | kCaliper | NYXHIP_FAM_CHORDS))) return fail(ctx, NYXHIP_ERR_INVALID_ARG, "bad family mask");
+    if (mask == 0 || (mask & ~(NYXHIP_FAM_ALL | NYXHIP_FAM_RADIAL | kOutline | kCaliper | NYXHIP_FAM_CHORDS | kEllipseErosion))) return fail(ctx, NYXHIP_ERR_INVALID_ARG, "bad family mask");
     if (mask & ~kImplemented)
         return fail(ctx, NYXHIP_ERR_UNSUPPORTED, "requested feature family is not implemented by the HIP path yet "
                     "(all seven hot-path families are implemented; bad mask?)");

@@ -115,6 +115,15 @@ CHORDS = ["MAXCHORDS_" + k for k in _STAT8] + ["ALLCHORDS_" + k for k in _STAT8]
 for _n in CHORDS:
     FAMILY_OF[_n] = _abi.FAM_CHORDS
 
+# EllipseFittingFeature and ErosionPixelsFeature (featureset.h:62-68, :85-86): directly behind the intensity block, in front of
+# FRACT_DIM_BOXCOUNT.  No group token, for the same reason.
+ELLIPSE = ["MAJOR_AXIS_LENGTH", "MINOR_AXIS_LENGTH", "ELONGATION", "ECCENTRICITY", "ORIENTATION", "ROUNDNESS"]
+EROSION = ["EROSIONS_2_VANISH", "EROSIONS_2_VANISH_COMPLEMENT"]
+for _n in ELLIPSE:
+    FAMILY_OF[_n] = _abi.FAM_ELLIPSE
+for _n in EROSION:
+    FAMILY_OF[_n] = _abi.FAM_EROSION
+
 # group tokens (featureset.cpp:650-665) the HIP path can serve completely (the radial distribution has none, featureset.cpp:650-668)
 GROUPS: Dict[str, List[str]] = {
     "*ALL_INTENSITY*": INTENSITY,
@@ -139,9 +148,12 @@ OUTPUT_ORDER: List[str] = INTENSITY + FRACTAL + EULER + ROI_RADIUS + ENUM_ORDER[
 # every served code in true enum order: OUTPUT_ORDER with the caliper codes behind FRACT_DIM_PERIMETER.
 SERVED_ORDER: List[str] = INTENSITY + FRACTAL + FERET + MARTIN + NASSENSTEIN + OUTPUT_ORDER[len(INTENSITY) + len(FRACTAL):]
 # ... and SERVED_ORDER with the chords codes behind STAT_NASSENSTEIN_DIAM_MODE (SERVED_ORDER keeps the codes it was introduced with,
-# like ENUM_ORDER and OUTPUT_ORDER before it).  expand() orders by this list.
+# like ENUM_ORDER and OUTPUT_ORDER before it).
 _K = len(INTENSITY) + len(FRACTAL) + len(FERET) + len(MARTIN) + len(NASSENSTEIN)
 CATALOGUE_ORDER: List[str] = SERVED_ORDER[:_K] + CHORDS + SERVED_ORDER[_K:]
+# ... and CATALOGUE_ORDER with the ellipse and erosion codes behind the intensity codes (CATALOGUE_ORDER keeps the codes it was
+# introduced with, like the three lists before it).  expand() orders by this list.
+FULL_ORDER: List[str] = INTENSITY + ELLIPSE + EROSION + CATALOGUE_ORDER[len(INTENSITY):]
 
 
 def expand(features: List[str]) -> Tuple[int, List[str]]:
@@ -162,10 +174,11 @@ def expand(features: List[str]) -> Tuple[int, List[str]]:
             f"individual features of the intensity, GLCM, GLRLM, GLDZM, GLSZM, GLDM, NGLDM and NGTDM families, GABOR, ZERNIKE2D, "
             f"FRAC_AT_D, MEAN_FRAC, RADIAL_CV, FRACT_DIM_BOXCOUNT, FRACT_DIM_PERIMETER, EULER_NUMBER, ROI_RADIUS_MEAN, ROI_RADIUS_MAX, "
             f"ROI_RADIUS_MEDIAN, MIN_FERET_ANGLE, MAX_FERET_ANGLE and STAT_{{FERET,MARTIN,NASSENSTEIN}}_DIAM_{{MIN,MAX,MEAN,MEDIAN,STDDEV,MODE}}, "
-            f"{{MAXCHORDS,ALLCHORDS}}_{{MAX,MAX_ANG,MIN,MIN_ANG,MEDIAN,MEAN,MODE,STDDEV}}")
+            f"{{MAXCHORDS,ALLCHORDS}}_{{MAX,MAX_ANG,MIN,MIN_ANG,MEDIAN,MEAN,MODE,STDDEV}}, MAJOR_AXIS_LENGTH, MINOR_AXIS_LENGTH, ELONGATION, "
+            f"ECCENTRICITY, ORIENTATION, ROUNDNESS, EROSIONS_2_VANISH, EROSIONS_2_VANISH_COMPLEMENT")
     if not want:
         raise ValueError("no features requested")
-    ordered = [n for n in CATALOGUE_ORDER if n in want]
+    ordered = [n for n in FULL_ORDER if n in want]
     mask = 0
     for n in ordered:
         mask |= FAMILY_OF[n]

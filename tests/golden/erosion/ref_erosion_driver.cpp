@@ -1,0 +1,112 @@
+/*
+ * ref_erosion_driver.cpp -- TEST INFRASTRUCTURE, NOT PRODUCT CODE.
+ *
+ * A thin driver (own code, in the manner of oracle/ref_driver.cpp and tests/golden/chords/ref_chords_driver.cpp) around the
+ * reference's own EllipseFittingFeature and ErosionPixelsFeature classes.  make_erosion_golden.py compiles it OUTSIDE the repository
+ * against the reference sources where they lie and records what it returns into the fixtures next to this file; nothing compiled
+ * from it is kept.
+ *
+ * Per ROI of a host nyxhip_batch placed at (origin_x[r], origin_y[r]): an LR with ABSOLUTE pixel coordinates in the batch's cloud
+ * order; BasicMorphologyFeatures first (the reference's dependency order: it leaves CENTROID_X / _Y and AREA_PIXELS_COUNT in fvals),
+ * then EllipseFittingFeature::extract(), then -- unless aux_min == aux_max, the skip of ErosionPixelsFeature::parallel_process_1_batch
+ * -- ErosionPixelsFeature::extract():
+ *   out[r * 8 ..]   MAJOR_AXIS_LENGTH, MINOR_AXIS_LENGTH, ELONGATION, ECCENTRICITY, ORIENTATION, ROUNDNESS, EROSIONS_2_VANISH,
+ *                   EROSIONS_2_VANISH_COMPLEMENT (enum order), each passed through the output stage's "not finite -> soft_nan"
+ * seconds[0] = EllipseFittingFeature::reduce, seconds[1] = ErosionPixelsFeature::parallel_process_1_batch (wall, n_threads workers),
+ * when seconds != NULL.
+ */
+#define _USE_MATH_DEFINES
+#include <chrono>
+#include <cmath>
+#include <cstring>
+#include <vector>
+#include <unordered_map>
+
+#include "roi_cache.h"
+#include "dataset.h"
+#include "parallel.h"
+#include "helpers/helpers.h"
+#include "features/basic_morphology.h"
+#include "features/ellipse_fitting.h"
+#include "features/erosion.h"
+
+#include "nyxhip.h"
+
+using namespace Nyxus;
+
+extern "C" int erosionref_batch(const nyxhip_batch* b, const uint32_t* origin_x, const uint32_t* origin_y, double soft_nan, int n_threads,
+                                double* out, double* seconds)
+{
+    if (!b || !out || b->memory != NYXHIP_MEM_HOST || n_threads < 1)
+        return 1;
+    try {
+        Fsettings fst;
+        fst.resize((int)NyxSetting::__COUNT__);
+        fst[(int)NyxSetting::SOFTNAN].rval = soft_nan;
+        fst[(int)NyxSetting::TINY].rval = 1e-10;
+        fst[(int)NyxSetting::SINGLEROI].bval = false;
+        fst[(int)NyxSetting::GREYDEPTH].ival = 64;
+        fst[(int)NyxSetting::PIXELSIZEUM].rval = 1.0;
+        fst[(int)NyxSetting::PIXELDISTANCE].ival = 5;
+        fst[(int)NyxSetting::XYRES].rval = 0.0;
+        fst[(int)NyxSetting::USEGPU].bval = false;
+        fst[(int)NyxSetting::VERBOSLVL].ival = 0;
+        fst[(int)NyxSetting::IBSI].bval = false;
+        Dataset ds;
+        std::vector<int> L;
+        std::unordered_map<int, LR> roiData;
+        L.reserve(b->n_roi);
+        roiData.reserve(b->n_roi);
+        for (uint64_t r = 0; r < b->n_roi; r++) {
+            int lab = (int)r + 1;
+            L.push_back(lab);
+            LR& lr = roiData[lab];
+            lr.label = lab;
+            const StatsInt ox = origin_x ? (StatsInt)origin_x[r] : 0, oy = origin_y ? (StatsInt)origin_y[r] : 0;
+            uint64_t o = b->px_offset[r], n = b->px_offset[r + 1] - o;
+            lr.raw_pixels.reserve(n);
+            for (uint64_t i = 0; i < n; i++)
+                lr.raw_pixels.push_back(Pixel2((StatsInt)b->x[o + i] + ox, (StatsInt)b->y[o + i] + oy, (PixIntens)b->inten[o + i]));
+            lr.aux_area = (unsigned int)n;
+            lr.aux_min = b->min_inten[r];
+            lr.aux_max = b->max_inten[r];
+            lr.ph_aabb.init_x(ox); lr.ph_aabb.update_x(ox + (StatsInt)b->bbox_w[r] - 1);
+            lr.ph_aabb.init_y(oy); lr.ph_aabb.update_y(oy + (StatsInt)b->bbox_h[r] - 1);
+            lr.make_nonanisotropic_aabb();
+            lr.slide_idx = -1;
+            lr.initialize_fvals();
+            BasicMorphologyFeatures bm;
+            bm.calculate(lr, fst);
+            bm.save_value(lr.fvals);
+        }
+        if (seconds) {
+            size_t jobSize = L.size(), workPerThread = jobSize / (size_t)n_threads;
+            auto a0 = std::chrono::steady_clock::now();
+            runParallel(EllipseFittingFeature::reduce, n_threads, workPerThread, jobSize, &L, &roiData, fst, ds);
+            auto a1 = std::chrono::steady_clock::now();
+            runParallel(ErosionPixelsFeature::parallel_process_1_batch, n_threads, workPerThread, jobSize, &L, &roiData, fst, ds);
+            auto a2 = std::chrono::steady_clock::now();
+            seconds[0] = std::chrono::duration<double>(a1 - a0).count();
+            seconds[1] = std::chrono::duration<double>(a2 - a1).count();
+            for (uint64_t r = 0; r < b->n_roi; r++) roiData[(int)r + 1].fvals[(int)Feature2D::EROSIONS_2_VANISH][0] = 0;
+        }
+        static const Feature2D codes[8] = {Feature2D::MAJOR_AXIS_LENGTH, Feature2D::MINOR_AXIS_LENGTH, Feature2D::ELONGATION, Feature2D::ECCENTRICITY,
+                                           Feature2D::ORIENTATION, Feature2D::ROUNDNESS, Feature2D::EROSIONS_2_VANISH,
+                                           Feature2D::EROSIONS_2_VANISH_COMPLEMENT};
+        for (uint64_t r = 0; r < b->n_roi; r++) {
+            LR& lr = roiData[(int)r + 1];
+            EllipseFittingFeature::extract(lr, fst);
+            if (lr.aux_min != lr.aux_max)
+                ErosionPixelsFeature::extract(lr, fst);
+            double* o = out + r * 8;
+            for (int i = 0; i < 8; i++) {
+                const double v = lr.fvals[(int)codes[i]][0];
+                o[i] = std::isfinite(v) ? v : soft_nan;
+            }
+        }
+    } catch (const std::exception& e) {
+        fprintf(stderr, "erosionref_batch: %s\n", e.what());
+        return 2;
+    }
+    return 0;
+}
