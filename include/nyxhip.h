@@ -72,8 +72,8 @@ enum {
     NYXHIP_FAM_EULER     = 1u << 16, /* EulerNumberFeature, 1 column: EULER_NUMBER, mode 8 (features/euler_number.h)                        */
     NYXHIP_FAM_ROI_RADIUS = 1u << 17, /* RoiRadiusFeature, 3 columns: ROI_RADIUS_MEAN, ROI_RADIUS_MAX, ROI_RADIUS_MEDIAN (features/roi_radius.h) */
     /* the three caliper classes (featureset.h:93-114, features/caliper.h): statistics of diameters of the convex hull turned in steps of
-     * 10 degrees.  Not part of NYXHIP_FAM_ALL.  Their columns sit between FRACT_DIM_PERIMETER and EULER_NUMBER (enum order).  These bits
-     * and NYXHIP_FAM_CHORDS are the only ones that read the ROI origin of nyxhip_featurize_batch_at(): the reference stores every rotated hull vertex as `float`
+     * 10 degrees.  Not part of NYXHIP_FAM_ALL.  Their columns sit between FRACT_DIM_PERIMETER and EULER_NUMBER (enum order).  These bits,
+     * NYXHIP_FAM_CHORDS and NYXHIP_FAM_CIRCLES are the only ones that read the ROI origin of nyxhip_featurize_batch_at(): the reference stores every rotated hull vertex as `float`
      * (features/rotation.cpp:37-68), so its values depend on where the ROI lies in its image.  Through the entries without an origin
      * the rows are those of an ROI whose bounding box starts at (0, 0).  An ROI of fewer than 2 pixels has no hull: all columns of
      * the requested classes are settings.soft_nan (caliper_feret.cpp:19-32). */
@@ -95,6 +95,16 @@ enum {
      * (at most 1000).  Not part of NYXHIP_FAM_ALL.  Columns behind ROUNDNESS, in front of FRACT_DIM_BOXCOUNT.  Relies on
      * nyxhip_batch::min_inten / max_inten: an ROI with min_inten == max_inten is skipped, as the reference's driver does, and has 0. */
     NYXHIP_FAM_EROSION   = 1u << 23, /* 2 columns: EROSIONS_2_VANISH, EROSIONS_2_VANISH_COMPLEMENT (never assigned by the class: 0) */
+    /* EnclosingInscribingCircumscribingCircleFeature (featureset.h:150-152, features/circle.h) over the ROI's merged contour.  Not part
+     * of NYXHIP_FAM_ALL.  Columns directly behind EULER_NUMBER, in front of GEODETIC_LENGTH / ROI_RADIUS_MEAN (enum order).  The third
+     * reader of the ROI origin of nyxhip_featurize_batch_at(): the reference searches the enclosing circle in `float` over ABSOLUTE
+     * contour points and truncates midpoints to integers, so its values depend on where the ROI lies.  An ROI without a contour
+     * (one pixel, two pixels, an anti-diagonal) is skipped by the class and has three zeros (circle.cpp:257). */
+    NYXHIP_FAM_CIRCLES   = 1u << 24, /* 3 columns: DIAMETER_MIN_ENCLOSING_CIRCLE, DIAMETER_CIRCUMSCRIBING_CIRCLE, DIAMETER_INSCRIBING_CIRCLE */
+    /* GeodeticLengthThicknessFeature (featureset.h:154-155, features/geodetic_len_thickness.h): the rectangle model over the contour's
+     * perimeter and the pixel count.  Not part of NYXHIP_FAM_ALL.  Columns behind DIAMETER_INSCRIBING_CIRCLE, in front of
+     * ROI_RADIUS_MEAN.  Coordinate differences only: does not read the origin.  Bits 26-31 stay unassigned (NYXHIP_ERR_INVALID_ARG). */
+    NYXHIP_FAM_GEODETIC  = 1u << 25, /* 2 columns: GEODETIC_LENGTH, THICKNESS */
     NYXHIP_FAM_NORTH_STAR = 0x7Fu,  /* the seven families of BASELINE.json's north_star */
     NYXHIP_FAM_ALL       = 0xFFFu
 };
@@ -235,7 +245,7 @@ int nyxhip_sync(nyxhip_ctx* ctx);
 
 /* The two calls above with the ROIs' positions: origin_x[r] / origin_y[r] = aabb.xmin / aabb.ymin of ROI r in its image ([n_roi],
  * in the memory of the batch's other pointers, batch->memory).  Both NULL = every origin (0, 0): exactly nyxhip_featurize_batch
- * [_async].  Only NYXHIP_FAM_FERET / _MARTIN / _NASSENSTEIN / _CHORDS read the origin; every other column is the same with and without it. */
+ * [_async].  Only NYXHIP_FAM_FERET / _MARTIN / _NASSENSTEIN / _CHORDS / _CIRCLES read the origin; every other column is the same with and without it. */
 int nyxhip_featurize_batch_at(nyxhip_ctx* ctx, const nyxhip_batch* batch, const uint32_t* origin_x, const uint32_t* origin_y,
                               uint32_t family_mask, const nyxhip_settings* s, double* out_table, size_t out_ld);
 int nyxhip_featurize_batch_async_at(nyxhip_ctx* ctx, const nyxhip_batch* batch, const uint32_t* origin_x, const uint32_t* origin_y,

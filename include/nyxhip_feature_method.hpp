@@ -107,6 +107,11 @@ enum class Feature2D : int {
     // block, in front of FRACT_DIM_BOXCOUNT, and that is where their table columns are; numbered last here for the same reason.
     MAJOR_AXIS_LENGTH, MINOR_AXIS_LENGTH, ELONGATION, ECCENTRICITY, ORIENTATION, ROUNDNESS,
     EROSIONS_2_VANISH, EROSIONS_2_VANISH_COMPLEMENT,
+    // EnclosingInscribingCircumscribingCircleFeature (featureset.h:150-152) and GeodeticLengthThicknessFeature (:154-155).  In the
+    // reference these five sit behind EULER_NUMBER, in front of ROI_RADIUS_MEAN, and that is where their table columns are; numbered
+    // last here for the same reason.
+    DIAMETER_MIN_ENCLOSING_CIRCLE, DIAMETER_CIRCUMSCRIBING_CIRCLE, DIAMETER_INSCRIBING_CIRCLE,
+    GEODETIC_LENGTH, THICKNESS,
     _COUNT_
 };
 
@@ -236,7 +241,7 @@ inline void reduce_range(uint32_t mask, size_t start, size_t end, std::vector<in
         LR& r = (*roiData)[(*labels)[start + i]];
         lab[i] = (uint32_t)r.label; bw[i] = (uint32_t)r.aabb.get_width(); bh[i] = (uint32_t)r.aabb.get_height();
         mn[i] = r.aux_min; mx[i] = r.aux_max;
-        ox[i] = (uint32_t)r.aabb.get_xmin(); oy[i] = (uint32_t)r.aabb.get_ymin();   // the ROI's position (read by the caliper classes and the chords)
+        ox[i] = (uint32_t)r.aabb.get_xmin(); oy[i] = (uint32_t)r.aabb.get_ymin();   // the ROI's position (read by the caliper classes, the chords and the circle class)
         for (const Pixel2& p : r.raw_pixels) { x.push_back((uint16_t)(p.x - r.aabb.get_xmin())); y.push_back((uint16_t)(p.y - r.aabb.get_ymin())); inten.push_back(p.inten); }
         off[i + 1] = inten.size();
         if (r.slide_idx >= 0 && (size_t)r.slide_idx < ds.dataset_props.size()) { smin[i] = ds.dataset_props[r.slide_idx].min_preroi_inten; smax[i] = ds.dataset_props[r.slide_idx].max_preroi_inten; }
@@ -270,6 +275,8 @@ inline void reduce_range(uint32_t mask, size_t start, size_t end, std::vector<in
         if (mask & NYXHIP_FAM_NASSENSTEIN) put(Feature2D::STAT_NASSENSTEIN_DIAM_MIN, Feature2D::STAT_NASSENSTEIN_DIAM_MODE, 1);
         if (mask & NYXHIP_FAM_CHORDS) put(Feature2D::MAXCHORDS_MAX, Feature2D::ALLCHORDS_STDDEV, 1);
         if (mask & NYXHIP_FAM_EULER) put(Feature2D::EULER_NUMBER, Feature2D::EULER_NUMBER, 1);
+        if (mask & NYXHIP_FAM_CIRCLES) put(Feature2D::DIAMETER_MIN_ENCLOSING_CIRCLE, Feature2D::DIAMETER_INSCRIBING_CIRCLE, 1);
+        if (mask & NYXHIP_FAM_GEODETIC) put(Feature2D::GEODETIC_LENGTH, Feature2D::THICKNESS, 1);
         if (mask & NYXHIP_FAM_ROI_RADIUS) put(Feature2D::ROI_RADIUS_MEAN, Feature2D::ROI_RADIUS_MEDIAN, 1);
         if (mask & NYXHIP_FAM_GLCM) { put(Feature2D::GLCM_ASM, Feature2D::GLCM_VARIANCE, na); put(Feature2D::GLCM_ASM_AVE, Feature2D::GLCM_SUMVARIANCE_AVE, 1); }
         if (mask & NYXHIP_FAM_GLRLM) { put(Feature2D::GLRLM_SRE, Feature2D::GLRLM_LRHGLE, 4); put(Feature2D::GLRLM_SRE_AVE, Feature2D::GLRLM_LRHGLE_AVE, 1); }
@@ -360,6 +367,10 @@ NYXHIP_FAMILY_CLASS(ChordsFeature, NYXHIP_FAM_CHORDS, MAXCHORDS_MAX, ALLCHORDS_S
 // features/ellipse_fitting.h, features/erosion.h: the pixel cloud only; the erosion's skip reads LR::aux_min / aux_max
 NYXHIP_FAMILY_CLASS(EllipseFittingFeature, NYXHIP_FAM_ELLIPSE, MAJOR_AXIS_LENGTH, ROUNDNESS)
 NYXHIP_FAMILY_CLASS(ErosionPixelsFeature, NYXHIP_FAM_EROSION, EROSIONS_2_VANISH, EROSIONS_2_VANISH_COMPLEMENT)
+// features/circle.h, features/geodetic_len_thickness.h: the contour they depend on is built inside the call; the circle class reads
+// LR::aabb's origin (absolute contour points), the geodetic class coordinate differences and the pixel count only
+NYXHIP_FAMILY_CLASS(EnclosingInscribingCircumscribingCircleFeature, NYXHIP_FAM_CIRCLES, DIAMETER_MIN_ENCLOSING_CIRCLE, DIAMETER_INSCRIBING_CIRCLE)
+NYXHIP_FAMILY_CLASS(GeodeticLengthThicknessFeature, NYXHIP_FAM_GEODETIC, GEODETIC_LENGTH, THICKNESS)
 
 // RadialDistributionFeature (features/radial_distribution.h): its three codes are not contiguous in the enum (GABOR sits
 // between FRAC_AT_D and MEAN_FRAC), so the class is spelled out.  The contour it depends on is built inside the call.
@@ -409,6 +420,8 @@ inline void reduce_trivial_rois_manual(std::vector<int>& PendingRoisLabels, std:
     if (EllipseFittingFeature::required(fs)) mask |= NYXHIP_FAM_ELLIPSE;
     if (ErosionPixelsFeature::required(fs)) mask |= NYXHIP_FAM_EROSION;
     if (EulerNumberFeature::required(fs)) mask |= NYXHIP_FAM_EULER;
+    if (EnclosingInscribingCircumscribingCircleFeature::required(fs)) mask |= NYXHIP_FAM_CIRCLES;
+    if (GeodeticLengthThicknessFeature::required(fs)) mask |= NYXHIP_FAM_GEODETIC;
     if (RoiRadiusFeature::required(fs)) mask |= NYXHIP_FAM_ROI_RADIUS;
     if (GLCMFeature::required(fs)) mask |= NYXHIP_FAM_GLCM;
     if (GLRLMFeature::required(fs)) mask |= NYXHIP_FAM_GLRLM;

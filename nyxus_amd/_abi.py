@@ -33,17 +33,20 @@ FAM_RADIAL = 1 << 13          # (bit 12 stays unassigned) RadialDistributionFeat
 FAM_FRACTAL = 1 << 15         # FractalDimensionFeature (FRACT_DIM_BOXCOUNT, FRACT_DIM_PERIMETER)
 FAM_EULER = 1 << 16           # EulerNumberFeature (EULER_NUMBER)
 FAM_ROI_RADIUS = 1 << 17      # RoiRadiusFeature (ROI_RADIUS_MEAN, ROI_RADIUS_MAX, ROI_RADIUS_MEDIAN)
-# the three caliper classes (columns between FRACT_DIM_PERIMETER and EULER_NUMBER); not part of FAM_ALL.  The only families that read
-# the ROI origin (HostBatch.origin_x / origin_y, nyxhip_featurize_batch_at)
+# the three caliper classes (columns between FRACT_DIM_PERIMETER and EULER_NUMBER); not part of FAM_ALL.  They, the chords and the circle
+# diameters read the ROI origin (HostBatch.origin_x / origin_y, nyxhip_featurize_batch_at)
 FAM_FERET = 1 << 18           # CaliperFeretFeature (MIN_FERET_ANGLE, MAX_FERET_ANGLE, STAT_FERET_DIAM_*)
 FAM_MARTIN = 1 << 19          # CaliperMartinFeature (STAT_MARTIN_DIAM_*)
 FAM_NASSENSTEIN = 1 << 20     # CaliperNassensteinFeature (STAT_NASSENSTEIN_DIAM_*)
 FAM_CALIPER = FAM_FERET | FAM_MARTIN | FAM_NASSENSTEIN
 FAM_CHORDS = 1 << 21          # ChordsFeature (MAXCHORDS_*, ALLCHORDS_*; columns between the Nassenstein columns and EULER_NUMBER); not part
                               # of FAM_ALL; reads the ROI origin like the caliper classes
-FAM_NEEDS_ORIGIN = FAM_CALIPER | FAM_CHORDS
 FAM_ELLIPSE = 1 << 22         # EllipseFittingFeature (MAJOR_AXIS_LENGTH .. ROUNDNESS; columns directly behind the intensity block); not part of FAM_ALL
 FAM_EROSION = 1 << 23         # ErosionPixelsFeature (EROSIONS_2_VANISH, EROSIONS_2_VANISH_COMPLEMENT; behind ROUNDNESS); not part of FAM_ALL
+FAM_CIRCLES = 1 << 24         # EnclosingInscribingCircumscribingCircleFeature (DIAMETER_MIN_ENCLOSING_CIRCLE, _CIRCUMSCRIBING_, _INSCRIBING_; columns
+                              # directly behind EULER_NUMBER); not part of FAM_ALL; reads the ROI origin (nyxhip_featurize_batch_at)
+FAM_GEODETIC = 1 << 25        # GeodeticLengthThicknessFeature (GEODETIC_LENGTH, THICKNESS; behind DIAMETER_INSCRIBING_CIRCLE); not part of FAM_ALL
+FAM_NEEDS_ORIGIN = FAM_CALIPER | FAM_CHORDS | FAM_CIRCLES
 FAM_NORTH_STAR = 0x7F
 FAM_ALL = 0xFFF
 

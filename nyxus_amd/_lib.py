@@ -191,8 +191,8 @@ class Context:
         out = np.empty((batch.n_roi, ncol), np.float64)
         cb = batch.c_struct()
         if (mask & _abi.FAM_NEEDS_ORIGIN) and batch.origin_unrepresentable:
-            raise ValueError("the caliper families and the chords need the ROIs' origins, and this batch's lie below 0 or beyond 32 bits")
-        if batch.origin_x is not None:           # the ROIs' positions: read by the caliper families and the chords
+            raise ValueError("the caliper families, the chords and the circle diameters need the ROIs' origins, and this batch's lie below 0 or beyond 32 bits")
+        if batch.origin_x is not None:           # the ROIs' positions: read by the caliper families, the chords and the circle diameters
             self._check(self._lib.nyxhip_featurize_batch_at(self._h, C.byref(cb), batch.origin_x.ctypes.data, batch.origin_y.ctypes.data, mask,
                                                             C.byref(s), out.ctypes.data, ncol))
         else:

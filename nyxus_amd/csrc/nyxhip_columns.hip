@@ -112,6 +112,9 @@ std::vector<std::string> column_names(uint32_t mask, const nyxhip_settings* s)
             for (auto k : st) v.push_back(std::string(g) + k);
     }
     if (mask & NYXHIP_FAM_EULER) v.push_back("EULER_NUMBER");
+    if (mask & NYXHIP_FAM_CIRCLES)    // EnclosingInscribingCircumscribingCircleFeature (featureset.h:150-152)
+        for (auto n : {"DIAMETER_MIN_ENCLOSING_CIRCLE", "DIAMETER_CIRCUMSCRIBING_CIRCLE", "DIAMETER_INSCRIBING_CIRCLE"}) v.push_back(n);
+    if (mask & NYXHIP_FAM_GEODETIC) { v.push_back("GEODETIC_LENGTH"); v.push_back("THICKNESS"); }   // featureset.h:154-155
     if (mask & NYXHIP_FAM_ROI_RADIUS) { v.push_back("ROI_RADIUS_MEAN"); v.push_back("ROI_RADIUS_MAX"); v.push_back("ROI_RADIUS_MEDIAN"); }
     if (mask & NYXHIP_FAM_GLCM) {
         for (auto n : kGlcmNames)
@@ -213,6 +216,8 @@ int nyxhip_n_columns(uint32_t family_mask, const nyxhip_settings* s)
     if (family_mask & NYXHIP_FAM_NASSENSTEIN) n += kNassensteinCols;
     if (family_mask & NYXHIP_FAM_CHORDS) n += kChordsCols;
     if (family_mask & NYXHIP_FAM_EULER) n += kEulerCols;
+    if (family_mask & NYXHIP_FAM_CIRCLES) n += kCirclesCols;
+    if (family_mask & NYXHIP_FAM_GEODETIC) n += kGeodeticCols;
     if (family_mask & NYXHIP_FAM_ROI_RADIUS) n += kRoiRadiusCols;
     if (family_mask & NYXHIP_FAM_GLCM) n += kGlcmAngled * s->glcm_n_angles + kGlcmAve;
     if (family_mask & NYXHIP_FAM_GLRLM) n += kGlrlmCols;

@@ -24,6 +24,7 @@
 #include "roi_caliper.h"
 #include "roi_chords.h"
 #include "roi_erosion.h"
+#include "roi_circle.h"
 
 // One hipMalloc allocation, grow-only.  hipFree waits for the device's work by itself; the stream handed to reserve() states which
 // work the site knows to be using the old block.
@@ -225,12 +226,13 @@ constexpr uint32_t kDependence = NYXHIP_FAM_GLDZM | NYXHIP_FAM_GLDM | NYXHIP_FAM
 constexpr uint32_t kMoments = NYXHIP_FAM_SMOMS | NYXHIP_FAM_IMOMS;
 constexpr uint32_t kOutline = NYXHIP_FAM_FRACTAL | NYXHIP_FAM_EULER | NYXHIP_FAM_ROI_RADIUS;   // roi_outline.hip; their columns follow the intensity block
 // families that read the ROI's ordered contour (launch_contour_families)
-constexpr uint32_t kContourFams = kMoments | NYXHIP_FAM_RADIAL | NYXHIP_FAM_FRACTAL | NYXHIP_FAM_ROI_RADIUS;
+constexpr uint32_t kCircleGeodetic = NYXHIP_FAM_CIRCLES | NYXHIP_FAM_GEODETIC;   // roi_circle.hip; their columns follow EULER_NUMBER, in front of ROI_RADIUS_MEAN
+constexpr uint32_t kContourFams = kMoments | NYXHIP_FAM_RADIAL | NYXHIP_FAM_FRACTAL | NYXHIP_FAM_ROI_RADIUS | kCircleGeodetic;
 constexpr uint32_t kCaliper = NYXHIP_FAM_FERET | NYXHIP_FAM_MARTIN | NYXHIP_FAM_NASSENSTEIN;   // roi_caliper.hip; their columns follow FRACT_DIM_PERIMETER
 constexpr uint32_t kEllipseErosion = NYXHIP_FAM_ELLIPSE | NYXHIP_FAM_EROSION;   // roi_erosion.hip; their columns follow the intensity block, in front of kOutline's
-constexpr uint32_t kBehindIntensity = kOutline | kCaliper | NYXHIP_FAM_CHORDS | kEllipseErosion;   // families whose columns lie between the intensity block and GLCM
-constexpr uint32_t kTailFams = kContourFams | NYXHIP_FAM_EULER | kCaliper | NYXHIP_FAM_CHORDS | kEllipseErosion;   // ... and everything else launch_contour_families serves (no size classes)
-constexpr uint32_t kImplemented = NYXHIP_FAM_INTENSITY | NYXHIP_FAM_GLCM | kTexture | kShape | kDependence | kMoments | NYXHIP_FAM_RADIAL | kOutline | kCaliper | NYXHIP_FAM_CHORDS | kEllipseErosion;
+constexpr uint32_t kBehindIntensity = kOutline | kCaliper | NYXHIP_FAM_CHORDS | kEllipseErosion | kCircleGeodetic;   // families whose columns lie between the intensity block and GLCM
+constexpr uint32_t kTailFams = kContourFams | NYXHIP_FAM_EULER | kCaliper | NYXHIP_FAM_CHORDS | kEllipseErosion | kCircleGeodetic;   // ... and everything else launch_contour_families serves (no size classes)
+constexpr uint32_t kImplemented = NYXHIP_FAM_INTENSITY | NYXHIP_FAM_GLCM | kTexture | kShape | kDependence | kMoments | NYXHIP_FAM_RADIAL | kOutline | kCaliper | NYXHIP_FAM_CHORDS | kEllipseErosion | kCircleGeodetic;
 
 namespace nyxhip __attribute__((visibility("hidden"))) {
 

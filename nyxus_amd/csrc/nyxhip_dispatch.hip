@@ -628,7 +628,7 @@ int launch_ellipse_erosion(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t mask
 // distribution (roi_radial.hip).  The contour of every ROI goes to a context-owned workspace at the ROI's CSR offset (a contour
 // never has more points than the ROI has pixels) ONCE per call; the moments kernel and / or the radial kernel read it back.
 // (The workspace keeps its per-pixel double plane for a radial-only call too: the contour kernel's walk stack lives there.)
-// The outline kernel (roi_outline.hip) is the third reader; a mask that holds none of the contour families (EULER_NUMBER alone) skips
+// The outline kernel (roi_outline.hip) is the third reader, the circle kernel (roi_circle.hip) the fourth; a mask that holds none of the contour families (EULER_NUMBER alone) skips
 // the contour chain and launches it by itself.  allow_lane = false: everything stays on the call's stream (the caller has joined the
 // lanes: the feature kernels of a GLCM launch zero the outline columns, so the outline kernel must follow all of them).
 int launch_contour_families(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t mask, const nyxhip_settings* s, double* d_out, size_t ld,
@@ -644,7 +644,7 @@ int launch_contour_families(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t mas
         oa.has_contour = need_contour ? 1u : 0u;
         oa.col_fractal = nyxhip_n_columns(mask & (NYXHIP_FAM_INTENSITY | kEllipseErosion), s);   // (the ellipse and erosion columns precede it)
         oa.col_euler = oa.col_fractal + ((mask & NYXHIP_FAM_FRACTAL) ? kFractalCols : 0) + nyxhip_n_columns(mask & (kCaliper | NYXHIP_FAM_CHORDS), s);   // (enum order)
-        oa.col_radius = oa.col_euler + ((mask & NYXHIP_FAM_EULER) ? kEulerCols : 0);
+        oa.col_radius = oa.col_euler + ((mask & NYXHIP_FAM_EULER) ? kEulerCols : 0) + nyxhip_n_columns(mask & kCircleGeodetic, s);   // (the circle and geodetic columns precede it)
         if (mask & (NYXHIP_FAM_FRACTAL | NYXHIP_FAM_EULER)) {
             // bound of outline_bit_words over boxes of at most max_area cells and max_side a side: rows of w / 32 + 1 words, the pyramid
             // at most as much again plus a word and a row per level
@@ -683,6 +683,16 @@ int launch_contour_families(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t mas
         }
         return NYXHIP_OK;
     };
+    // the circle / geodetic classes (roi_circle.hip): the fourth reader of the contour, columns directly behind EULER_NUMBER
+    const bool do_circ = (mask & kCircleGeodetic) != 0;
+    CircArgs cg;
+    memset(&cg, 0, sizeof(cg));
+    if (do_circ) {
+        cg.fams = mask & kCircleGeodetic;
+        cg.col_circles = nyxhip_n_columns(mask & (NYXHIP_FAM_INTENSITY | kEllipseErosion | NYXHIP_FAM_FRACTAL | kCaliper | NYXHIP_FAM_CHORDS | NYXHIP_FAM_EULER), s);
+        cg.col_geodetic = cg.col_circles + ((mask & NYXHIP_FAM_CIRCLES) ? kCirclesCols : 0);
+        cg.origin_x = ctx->origin_x_next; cg.origin_y = ctx->origin_y_next;
+    }
     if (mask & kCaliper)
         if (int crc = launch_caliper(ctx, b, mask, s, d_out, ld, max_side, st)) return crc;
     if (mask & NYXHIP_FAM_CHORDS)
@@ -770,6 +780,10 @@ int launch_contour_families(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t mas
             oa.m = mm;
             r = launch_roi_outline(oa, s_, g);
         }
+        if (r == 0 && do_circ) {
+            cg.m = mm;
+            r = launch_roi_circle(cg, s_, g);
+        }
         return r;
     };
     const uint64_t full_plane = (uint64_t)max_area + 4ull * max_side + 4;      // (w + 2)(h + 2) <= area + 2(w + h) + 4
@@ -829,7 +843,7 @@ int launch_contour_families(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t mas
         }
     }
     if (rc != 0)
-        return fail(ctx, NYXHIP_ERR_HIP, std::string("contour / moments / radial / outline kernel launch failed: ") + hipGetErrorString((hipError_t)rc));
+        return fail(ctx, NYXHIP_ERR_HIP, std::string("contour / moments / radial / outline / circle kernel launch failed: ") + hipGetErrorString((hipError_t)rc));
     if (out_deferred) {
         if (st_join) {                                     // the deferred ROIs' contours may come from the big boxes' lane
             HIP_TRY(ctx, hipEventRecord(ctx->lane_done[nyxhip_ctx::kMomLaneBig], st_join));
@@ -1944,7 +1958,7 @@ int validate(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t mask, const nyxhip
 {
     if (!ctx) return NYXHIP_ERR_INVALID_ARG;
     if (!b || !s || !out) return fail(ctx, NYXHIP_ERR_INVALID_ARG, "null batch / settings / out_table");
-    if (mask == 0 || (mask & ~(NYXHIP_FAM_ALL | NYXHIP_FAM_RADIAL | kOutline | kCaliper | NYXHIP_FAM_CHORDS | kEllipseErosion))) return fail(ctx, NYXHIP_ERR_INVALID_ARG, "bad family mask");
+    if (mask == 0 || (mask & ~(NYXHIP_FAM_ALL | NYXHIP_FAM_RADIAL | kOutline | kCaliper | NYXHIP_FAM_CHORDS | kEllipseErosion | kCircleGeodetic))) return fail(ctx, NYXHIP_ERR_INVALID_ARG, "bad family mask");
     if (mask & ~kImplemented)
         return fail(ctx, NYXHIP_ERR_UNSUPPORTED, "requested feature family is not implemented by the HIP path yet "
                     "(all seven hot-path families are implemented; bad mask?)");

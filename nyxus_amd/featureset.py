@@ -124,6 +124,15 @@ for _n in ELLIPSE:
 for _n in EROSION:
     FAMILY_OF[_n] = _abi.FAM_EROSION
 
+# EnclosingInscribingCircumscribingCircleFeature and GeodeticLengthThicknessFeature (featureset.h:150-155): directly behind
+# EULER_NUMBER, in front of ROI_RADIUS_MEAN.  No group token, for the same reason.
+CIRCLES = ["DIAMETER_MIN_ENCLOSING_CIRCLE", "DIAMETER_CIRCUMSCRIBING_CIRCLE", "DIAMETER_INSCRIBING_CIRCLE"]
+GEODETIC = ["GEODETIC_LENGTH", "THICKNESS"]
+for _n in CIRCLES:
+    FAMILY_OF[_n] = _abi.FAM_CIRCLES
+for _n in GEODETIC:
+    FAMILY_OF[_n] = _abi.FAM_GEODETIC
+
 # group tokens (featureset.cpp:650-665) the HIP path can serve completely (the radial distribution has none, featureset.cpp:650-668)
 GROUPS: Dict[str, List[str]] = {
     "*ALL_INTENSITY*": INTENSITY,
@@ -152,8 +161,12 @@ SERVED_ORDER: List[str] = INTENSITY + FRACTAL + FERET + MARTIN + NASSENSTEIN + O
 _K = len(INTENSITY) + len(FRACTAL) + len(FERET) + len(MARTIN) + len(NASSENSTEIN)
 CATALOGUE_ORDER: List[str] = SERVED_ORDER[:_K] + CHORDS + SERVED_ORDER[_K:]
 # ... and CATALOGUE_ORDER with the ellipse and erosion codes behind the intensity codes (CATALOGUE_ORDER keeps the codes it was
-# introduced with, like the three lists before it).  expand() orders by this list.
+# introduced with, like the three lists before it).
 FULL_ORDER: List[str] = INTENSITY + ELLIPSE + EROSION + CATALOGUE_ORDER[len(INTENSITY):]
+# ... and FULL_ORDER with the circle and geodetic codes behind EULER_NUMBER (FULL_ORDER keeps the codes it was introduced with, like
+# the four lists before it).  expand() orders by this list.
+_E = FULL_ORDER.index("EULER_NUMBER") + 1
+EXPAND_ORDER: List[str] = FULL_ORDER[:_E] + CIRCLES + GEODETIC + FULL_ORDER[_E:]
 
 
 def expand(features: List[str]) -> Tuple[int, List[str]]:
@@ -175,10 +188,11 @@ def expand(features: List[str]) -> Tuple[int, List[str]]:
             f"FRAC_AT_D, MEAN_FRAC, RADIAL_CV, FRACT_DIM_BOXCOUNT, FRACT_DIM_PERIMETER, EULER_NUMBER, ROI_RADIUS_MEAN, ROI_RADIUS_MAX, "
             f"ROI_RADIUS_MEDIAN, MIN_FERET_ANGLE, MAX_FERET_ANGLE and STAT_{{FERET,MARTIN,NASSENSTEIN}}_DIAM_{{MIN,MAX,MEAN,MEDIAN,STDDEV,MODE}}, "
             f"{{MAXCHORDS,ALLCHORDS}}_{{MAX,MAX_ANG,MIN,MIN_ANG,MEDIAN,MEAN,MODE,STDDEV}}, MAJOR_AXIS_LENGTH, MINOR_AXIS_LENGTH, ELONGATION, "
-            f"ECCENTRICITY, ORIENTATION, ROUNDNESS, EROSIONS_2_VANISH, EROSIONS_2_VANISH_COMPLEMENT")
+            f"ECCENTRICITY, ORIENTATION, ROUNDNESS, EROSIONS_2_VANISH, EROSIONS_2_VANISH_COMPLEMENT, DIAMETER_MIN_ENCLOSING_CIRCLE, "
+            f"DIAMETER_CIRCUMSCRIBING_CIRCLE, DIAMETER_INSCRIBING_CIRCLE, GEODETIC_LENGTH, THICKNESS")
     if not want:
         raise ValueError("no features requested")
-    ordered = [n for n in FULL_ORDER if n in want]
+    ordered = [n for n in EXPAND_ORDER if n in want]
     mask = 0
     for n in ordered:
         mask |= FAMILY_OF[n]
