@@ -342,6 +342,30 @@ int nyxhip_featurize_tiles(nyxhip_ctx* ctx, const uint32_t* inten, const uint32_
                            uint32_t* out_labels, uint32_t* out_tile_index, uint64_t max_rows,
                            double* out_table, size_t out_ld, uint64_t* n_roi_out);
 
+/* ---- the neighbor class -------------------------------------------------------
+ * NeighborsFeature (features/neighbors.cpp:125-536, featureset.h:162-171): NUM_NEIGHBORS, PERCENT_TOUCHING, CLOSEST_NEIGHBOR1_DIST,
+ * CLOSEST_NEIGHBOR1_ANG, CLOSEST_NEIGHBOR2_DIST, CLOSEST_NEIGHBOR2_ANG, ANG_BW_NEIGHBORS_MEAN, ANG_BW_NEIGHBORS_STDDEV,
+ * ANG_BW_NEIGHBORS_MODE.  No per-ROI reduction: it relates the ROIs of ONE image to each other (boxes that overlap at pixel_distance,
+ * then exact distances between the merged contours), so it claims no family bit and has entries and an output table
+ * [n_roi x NYXHIP_NEIGHBOR_COLS] of its own; nyxhip_n_columns / nyxhip_column_name do not know it.  ROIs of different images are never
+ * neighbors.  Every value is finite (soft_nan never shows): an ROI without a neighbor has zeros.
+ * pixel_distance <= 0 is NYXHIP_ERR_INVALID_ARG; beyond 46340 its square overflows the reference's int: NYXHIP_ERR_UNSUPPORTED. */
+#define NYXHIP_NEIGHBOR_COLS 9
+int nyxhip_neighbor_column_name(int col, char* buf, size_t buf_len);
+
+/* A batch of ROIs of n_images images: image k owns rows [image_offset[k], image_offset[k + 1]) (CSR, [n_images + 1], in batch->memory
+ * like the origins; NULL: one image).  The rows of an image must be strictly ascending in roi_label (the reference walks its labels
+ * sorted, and the order decides ties): anything else is NYXHIP_ERR_INVALID_ARG.  origin_x / origin_y as in nyxhip_featurize_batch_at
+ * (both NULL: every origin (0, 0)).  Reads roi_label, px_offset, x, y, inten, bbox_w, bbox_h of the batch.  Synchronous. */
+int nyxhip_neighbors_batch(nyxhip_ctx* ctx, const nyxhip_batch* batch, const uint32_t* origin_x, const uint32_t* origin_y,
+                           const uint64_t* image_offset, uint64_t n_images, int32_t pixel_distance,
+                           const nyxhip_settings* s, double* out_table /* [n_roi x 9] */, size_t out_ld);
+/* The tile path (label scan, ROI assembly, chunks under max_device_bytes) with one image per tile; rows in the (tile, label) order of
+ * nyxhip_featurize_tiles_v2, outputs as there. */
+int nyxhip_neighbors_tiles(nyxhip_ctx* ctx, const nyxhip_tiles* tiles, int32_t pixel_distance, const nyxhip_settings* s,
+                           uint32_t* out_labels, uint32_t* out_tile_index, uint64_t max_rows,
+                           double* out_table, size_t out_ld, uint64_t* n_roi_out);
+
 /* ---- measurement hooks -------------------------------------------------------
  * Average device time (ms) per featurize call since the last nyxhip_timing_reset(),
  * measured with hipEvents recorded on the launch stream around EVERYTHING the call

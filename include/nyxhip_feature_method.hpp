@@ -25,6 +25,7 @@
 #include <stdexcept>
 #include <string>
 #include <unordered_map>
+#include <unordered_set>
 #include <vector>
 
 #include "nyxhip.h"
@@ -112,6 +113,10 @@ enum class Feature2D : int {
     // last here for the same reason.
     DIAMETER_MIN_ENCLOSING_CIRCLE, DIAMETER_CIRCUMSCRIBING_CIRCLE, DIAMETER_INSCRIBING_CIRCLE,
     GEODETIC_LENGTH, THICKNESS,
+    // NeighborsFeature (featureset.h:162-171).  In the reference these nine sit behind ROI_RADIUS_MEDIAN, in front of GLCM_ASM, and that is
+    // where the Python face puts their columns; numbered last here for the same reason.
+    NUM_NEIGHBORS, PERCENT_TOUCHING, CLOSEST_NEIGHBOR1_DIST, CLOSEST_NEIGHBOR1_ANG, CLOSEST_NEIGHBOR2_DIST, CLOSEST_NEIGHBOR2_ANG,
+    ANG_BW_NEIGHBORS_MEAN, ANG_BW_NEIGHBORS_STDDEV, ANG_BW_NEIGHBORS_MODE,
     _COUNT_
 };
 
@@ -395,6 +400,54 @@ public:
                        const Dataset& ds) { reduce_range(NYXHIP_FAM_RADIAL, start, end, labels, roiData, s, ds); }
     static void parallel_process_1_batch(size_t start, size_t end, std::vector<int>* labels, std::unordered_map<int, LR>* roiData,
                                          const Fsettings& s, const Dataset& ds) { reduce_range(NYXHIP_FAM_RADIAL, start, end, labels, roiData, s, ds); }
+};
+
+// NeighborsFeature (features/neighbors.h): no per-ROI class -- calculate() is empty in the reference too (neighbors.cpp:40-41) -- but a
+// reduction over the ROIs of one image: manual_reduce(roiData, settings, uniqueLabels) relates them to each other (boxes that overlap at
+// PIXELDISTANCE, then exact contour distances).  Served by nyxhip_neighbors_batch over the labels in ascending order (the order the
+// reference sorts them into, neighbors.cpp:149-152) with LR::aabb's origin; the contours are built inside the call.
+using Roidata = std::unordered_map<int, LR>;
+class NeighborsFeature : public FeatureMethod {
+public:
+    NeighborsFeature() : FeatureMethod("NeighborsFeature") { provide_features(Feature2D::NUM_NEIGHBORS, Feature2D::ANG_BW_NEIGHBORS_MODE); }
+    static bool required(const FeatureSet& fs) { return fs.anyEnabledInRange(Feature2D::NUM_NEIGHBORS, Feature2D::ANG_BW_NEIGHBORS_MODE); }
+    void calculate(LR&, const Fsettings&) override {}
+    void save_value(std::vector<std::vector<double>>&) override {}
+    static void manual_reduce(Roidata& roiData, const Fsettings& fst, const std::unordered_set<int>& uniqueLabels)
+    {
+        if (uniqueLabels.empty()) return;
+        nyxhip_settings s = make_settings(fst);
+        const int radius = NYXHIP_STNGS_MISSING(fst) ? 5 : fst[(int)NyxSetting::PIXELDISTANCE].ival;   // (the reference's default neighbor distance)
+        std::vector<int> L(uniqueLabels.begin(), uniqueLabels.end());
+        std::sort(L.begin(), L.end());
+        const size_t n = L.size();
+        std::vector<uint32_t> lab(n), bw(n), bh(n), mn(n), mx(n), ox(n), oy(n), inten;
+        std::vector<uint64_t> off(n + 1, 0);
+        std::vector<uint16_t> x, y;
+        for (size_t i = 0; i < n; i++) {
+            LR& r = roiData.at(L[i]);
+            if (L[i] < 0 || r.aabb.get_xmin() < 0 || r.aabb.get_ymin() < 0) throw std::runtime_error("NeighborsFeature: negative label or origin");
+            lab[i] = (uint32_t)L[i]; bw[i] = (uint32_t)r.aabb.get_width(); bh[i] = (uint32_t)r.aabb.get_height();
+            mn[i] = r.aux_min; mx[i] = r.aux_max;
+            ox[i] = (uint32_t)r.aabb.get_xmin(); oy[i] = (uint32_t)r.aabb.get_ymin();
+            for (const Pixel2& p : r.raw_pixels) { x.push_back((uint16_t)(p.x - r.aabb.get_xmin())); y.push_back((uint16_t)(p.y - r.aabb.get_ymin())); inten.push_back(p.inten); }
+            off[i + 1] = inten.size();
+            if (r.fvals.empty()) r.initialize_fvals();
+        }
+        nyxhip_batch b{};
+        b.n_roi = n; b.roi_label = lab.data(); b.px_offset = off.data(); b.x = x.data(); b.y = y.data(); b.inten = inten.data();
+        b.bbox_w = bw.data(); b.bbox_h = bh.data(); b.min_inten = mn.data(); b.max_inten = mx.data();
+        b.memory = NYXHIP_MEM_HOST;
+        std::vector<double> table(n * (size_t)NYXHIP_NEIGHBOR_COLS);
+        nyxhip_ctx* ctx = context();
+        if (nyxhip_neighbors_batch(ctx, &b, ox.data(), oy.data(), nullptr, 0, radius, &s, table.data(), (size_t)NYXHIP_NEIGHBOR_COLS) != NYXHIP_OK)
+            throw std::runtime_error(std::string("nyxhip_neighbors_batch: ") + nyxhip_last_error(ctx));
+        for (size_t i = 0; i < n; i++) {
+            LR& r = roiData.at(L[i]);
+            for (int c = 0; c < NYXHIP_NEIGHBOR_COLS; c++)
+                r.fvals[(int)Feature2D::NUM_NEIGHBORS + c].assign(1, table[i * (size_t)NYXHIP_NEIGHBOR_COLS + (size_t)c]);
+        }
+    }
 };
 
 // runParallel (parallel.h:23-42): the GPU batch is the parallel unit, so the slices run back to back on the

@@ -58,6 +58,7 @@ U8, U16, U32 = 1, 2, 4                       # tile element types (bytes per ele
 SLIDE_MONTAGE, SLIDE_PER_TILE, SLIDE_GIVEN = 0, 1, 2
 
 MAX_GLCM_ANGLES = 4
+NEIGHBOR_COLS = 9            # NYXHIP_NEIGHBOR_COLS: the table of nyxhip_neighbors_batch / _tiles (no family bit: the class relates the ROIs of an image)
 MAX_GABOR_FILTERS = 16
 
 
@@ -174,6 +175,7 @@ class HostBatch:
     origin_x: Optional[np.ndarray] = None    # [n_roi] aabb.xmin / aabb.ymin of the ROIs in their image, or None: (0, 0)
     origin_y: Optional[np.ndarray] = None
     origin_unrepresentable: bool = False     # built from ROIs whose origins do not fit uint32 (batch_from_rois)
+    image_offset: Optional[np.ndarray] = None   # [n_images + 1] CSR over the rows (nyxhip_neighbors_batch), or None: one image
 
     def __post_init__(self):
         self.roi_label = np.ascontiguousarray(self.roi_label, np.uint32)
@@ -196,6 +198,10 @@ class HostBatch:
             self.origin_y = np.ascontiguousarray(self.origin_y, np.uint32)
             if len(self.origin_x) != n or len(self.origin_y) != n:
                 raise ValueError("origin_x / origin_y must have n_roi entries")
+        if self.image_offset is not None:
+            self.image_offset = np.ascontiguousarray(self.image_offset, np.uint64)
+            if len(self.image_offset) < 2 or int(self.image_offset[0]) != 0 or int(self.image_offset[-1]) != n:
+                raise ValueError("image_offset must run from 0 to n_roi")
         if len(self.px_offset) != n + 1:
             raise ValueError("px_offset must have n_roi+1 entries")
         if int(self.px_offset[-1]) != len(self.inten) or len(self.x) != len(self.inten) or len(self.y) != len(self.inten):

@@ -28,6 +28,7 @@ ABI_SYMBOLS = [
     "nyxhip_timing_enable", "nyxhip_timing_reset", "nyxhip_timing_get",
     "nyxhip_featurize_tiles_v2", "nyxhip_fetch_result", "nyxhip_featurize_tiles_sharded", "nyxhip_fetch_result_sharded",
     "nyxhip_launch_report", "nyxhip_featurize_batch_at", "nyxhip_featurize_batch_async_at",
+    "nyxhip_neighbor_column_name", "nyxhip_neighbors_batch", "nyxhip_neighbors_tiles",
 ]
 
 
@@ -110,6 +111,15 @@ def load() -> C.CDLL:
     lib.nyxhip_timing_reset.restype = C.c_int
     lib.nyxhip_timing_get.argtypes = [C.c_void_p, P(C.c_double), P(C.c_uint64)]
     lib.nyxhip_timing_get.restype = C.c_int
+    if hasattr(lib, "nyxhip_neighbors_batch"):   # (absent from older builds of the ABI selected through NYXHIP_LIB for A/B runs)
+        lib.nyxhip_neighbor_column_name.argtypes = [C.c_int, C.c_char_p, C.c_size_t]
+        lib.nyxhip_neighbor_column_name.restype = C.c_int
+        lib.nyxhip_neighbors_batch.argtypes = [C.c_void_p, P(_abi.Batch), C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int32, P(_abi.Settings),
+                                               C.c_void_p, C.c_size_t]
+        lib.nyxhip_neighbors_batch.restype = C.c_int
+        lib.nyxhip_neighbors_tiles.argtypes = [C.c_void_p, P(_abi.Tiles), C.c_int32, P(_abi.Settings), C.c_void_p, C.c_void_p, C.c_uint64,
+                                               C.c_void_p, C.c_size_t, P(C.c_uint64)]
+        lib.nyxhip_neighbors_tiles.restype = C.c_int
     if hasattr(lib, "nyxhip_launch_report"):     # (absent from older builds of the ABI selected through NYXHIP_LIB for A/B runs)
         lib.nyxhip_launch_report.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
         lib.nyxhip_launch_report.restype = C.c_int
@@ -126,6 +136,19 @@ def column_names(mask: int, s: _abi.Settings) -> List[str]:
         rc = lib.nyxhip_column_name(mask, C.byref(s), i, buf, 128)
         if rc != 0:
             raise NyxHipError(rc, f"column {i}")
+        out.append(buf.value.decode())
+    return out
+
+
+def neighbor_column_names() -> List[str]:
+    """The nine columns of nyxhip_neighbors_batch / _tiles, enum order."""
+    lib = load()
+    buf = C.create_string_buffer(128)
+    out = []
+    for i in range(_abi.NEIGHBOR_COLS):
+        rc = lib.nyxhip_neighbor_column_name(i, buf, 128)
+        if rc != 0:
+            raise NyxHipError(rc, f"neighbor column {i}")
         out.append(buf.value.decode())
     return out
 
@@ -198,6 +221,43 @@ class Context:
         else:
             self._check(self._lib.nyxhip_featurize_batch(self._h, C.byref(cb), mask, C.byref(s), out.ctypes.data, ncol))
         return out
+
+    def neighbors_host(self, batch: _abi.HostBatch, distance: int, s: _abi.Settings) -> np.ndarray:
+        """The neighbor columns [n_roi x 9] of a host batch (nyxhip_neighbors_batch).  batch.image_offset: the rows of every image (None:
+        one image); inside an image the rows ascend in roi_label.  batch.origin_x / origin_y: the boxes' places in their image."""
+        if batch.origin_unrepresentable:
+            raise ValueError("the neighbor class needs the ROIs' origins, and this batch's lie below 0 or beyond 32 bits")
+        out = np.empty((batch.n_roi, _abi.NEIGHBOR_COLS), np.float64)
+        cb = batch.c_struct()
+        io = batch.image_offset
+        self._check(self._lib.nyxhip_neighbors_batch(
+            self._h, C.byref(cb), batch.origin_x.ctypes.data if batch.origin_x is not None else None,
+            batch.origin_y.ctypes.data if batch.origin_y is not None else None, io.ctypes.data if io is not None else None,
+            len(io) - 1 if io is not None else 0, int(distance), C.byref(s), out.ctypes.data, _abi.NEIGHBOR_COLS))
+        return out
+
+    def neighbors_tiles_host(self, inten: np.ndarray, label: np.ndarray, distance: int, s: _abi.Settings, max_device_bytes: int = 0):
+        """The neighbor columns of a stack [n_tiles, H, W] of host tiles, one image per tile (nyxhip_neighbors_tiles).  Returns
+        (tile_index, labels, table [n_roi x 9]) in the (tile, label) row order of featurize_tiles_host."""
+        if inten.shape != label.shape or inten.ndim != 3:
+            raise ValueError("stacks must be 3-D arrays [n_tiles, H, W] of the same shape")
+        dt = {np.dtype(np.uint8): _abi.U8, np.dtype(np.uint16): _abi.U16, np.dtype(np.uint32): _abi.U32}
+        inten = np.ascontiguousarray(inten if inten.dtype in dt else inten.astype(np.uint32))
+        label = np.ascontiguousarray(label if label.dtype in dt else label.astype(np.uint32))
+        nt, h, w = inten.shape
+        ncol = _abi.NEIGHBOR_COLS
+        if nt == 0:
+            return np.zeros(0, np.uint32), np.zeros(0, np.uint32), np.zeros((0, ncol))
+        t = _abi.Tiles()
+        t.inten = inten.ctypes.data; t.label = label.ctypes.data
+        t.inten_dtype = dt[inten.dtype]; t.label_dtype = dt[label.dtype]
+        t.width = w; t.height = h; t.n_tiles = nt; t.memory = _abi.MEM_HOST; t.slide_mode = _abi.SLIDE_MONTAGE
+        t.max_device_bytes = int(max_device_bytes)
+        n = C.c_uint64(0)
+        self._check(self._lib.nyxhip_neighbors_tiles(self._h, C.byref(t), int(distance), C.byref(s), None, None, 0, None, 0, C.byref(n)))
+        labels = np.zeros(n.value, np.uint32); tiles = np.zeros(n.value, np.uint32); table = np.empty((n.value, ncol), np.float64)
+        self._check(self._lib.nyxhip_fetch_result(self._h, labels.ctypes.data, tiles.ctypes.data, table.ctypes.data, ncol))
+        return tiles, labels, table
 
     def featurize_device_async(self, cb: _abi.Batch, mask: int, s: _abi.Settings, out_ptr: int, ld: int, origin_x_ptr: Optional[int] = None,
                                origin_y_ptr: Optional[int] = None):

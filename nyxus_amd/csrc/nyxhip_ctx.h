@@ -4,6 +4,7 @@
 //   nyxhip_dispatch.hip  layouts, argument blocks, size classes: a device-resident batch -> kernel launches
 //   nyxhip_tiles.hip     the fused tile path and its host staging
 //   nyxhip_api.hip       context life cycle, the batch entry points, timing, launch report
+//   nyxhip_neighbors.hip the neighbor entries: column names, the launches over a device-resident batch, nyxhip_neighbors_batch
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -25,6 +26,7 @@
 #include "roi_chords.h"
 #include "roi_erosion.h"
 #include "roi_circle.h"
+#include "roi_neighbors.h"
 
 // One hipMalloc allocation, grow-only.  hipFree waits for the device's work by itself; the stream handed to reserve() states which
 // work the site knows to be using the old block.
@@ -156,6 +158,9 @@ struct nyxhip_ctx {
     // erosion kernel (roi_erosion.hip): list of the ROIs whose two bit planes exceed the LDS planes, and their global planes
     DevBuf d_erosion_list;
     DevBuf d_erosion_ws;
+    // neighbor entries (roi_neighbors.hip): geometry table + candidate counts and offsets | candidate lists, minima, flags
+    DevBuf d_nb_geo;
+    DevBuf d_nb_cand;
     const uint32_t* origin_x_next = nullptr;   // set by nyxhip_featurize_batch[_async]_at and the tile path for their next launch_device call:
     const uint32_t* origin_y_next = nullptr;   // device arrays [n_roi] of the ROIs' box origins (NULL: (0, 0))
     // grow-only workspaces of the fused tile path: scan tables + rows | clouds | two staging slots for host tiles
@@ -260,5 +265,12 @@ void clear_runs(nyxhip_ctx* ctx);
 int launch_device(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t mask, const nyxhip_settings* s, double* d_out, size_t ld, uint32_t max_px,
                   uint32_t max_area, uint32_t max_range, uint32_t max_side, bool hinted = true);
 int validate(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t mask, const nyxhip_settings* s, double* out, size_t ld);
+int launch_contour_families(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t mask, const nyxhip_settings* s, double* d_out, size_t ld, uint32_t max_px,
+                            uint32_t max_area, uint32_t max_side, bool allow_lane, MomArgs* contour_out = nullptr);
+// nyxhip_neighbors.hip: the neighbor columns of a device-resident batch -> d_out [n_roi x ld] (enqueued on the context's stream).  The rows of
+// an image are given by image_offset (CSR, device) or image_id (ascending per row, device); both NULL: one image.
+int neighbors_device(nyxhip_ctx* ctx, const nyxhip_batch* b, const uint32_t* d_ox, const uint32_t* d_oy, const uint64_t* d_image_offset, uint64_t n_images,
+                     const uint32_t* d_image_id, int32_t pixel_distance, const nyxhip_settings* s, double* d_out, size_t ld, uint32_t max_px,
+                     uint32_t max_area, uint32_t max_side);
 
 } // namespace nyxhip

@@ -631,11 +631,13 @@ int launch_ellipse_erosion(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t mask
 // The outline kernel (roi_outline.hip) is the third reader, the circle kernel (roi_circle.hip) the fourth; a mask that holds none of the contour families (EULER_NUMBER alone) skips
 // the contour chain and launches it by itself.  allow_lane = false: everything stays on the call's stream (the caller has joined the
 // lanes: the feature kernels of a GLCM launch zero the outline columns, so the outline kernel must follow all of them).
-int launch_contour_families(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t mask, const nyxhip_settings* s, double* d_out, size_t ld,
-                   uint32_t max_px, uint32_t max_area, uint32_t max_side, bool allow_lane)
+// contour_out != NULL: the contour chain runs whatever the mask holds (0: the chain alone, no reader, d_out unused) and the argument
+// block that names its workspace (ws_contour / n_contour) is handed back -- the neighbor entries read the contours themselves.
+int contour_families(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t mask, const nyxhip_settings* s, double* d_out, size_t ld,
+                   uint32_t max_px, uint32_t max_area, uint32_t max_side, bool allow_lane, MomArgs* contour_out = nullptr)
 {
     hipStream_t st = ctx->stream();
-    const bool do_out = (mask & kOutline) != 0, need_contour = (mask & kContourFams) != 0;
+    const bool do_out = (mask & kOutline) != 0, need_contour = (mask & kContourFams) != 0 || contour_out != nullptr;
     OutArgs oa;
     memset(&oa, 0, sizeof(oa));
     bool out_deferred = false;                             // some ROI's bit planes may exceed LDS: a list launch follows the readers
@@ -844,6 +846,7 @@ int launch_contour_families(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t mas
     }
     if (rc != 0)
         return fail(ctx, NYXHIP_ERR_HIP, std::string("contour / moments / radial / outline / circle kernel launch failed: ") + hipGetErrorString((hipError_t)rc));
+    if (contour_out) *contour_out = m;
     if (out_deferred) {
         if (st_join) {                                     // the deferred ROIs' contours may come from the big boxes' lane
             HIP_TRY(ctx, hipEventRecord(ctx->lane_done[nyxhip_ctx::kMomLaneBig], st_join));
@@ -1701,7 +1704,7 @@ int launch_device_all(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t mask, con
         // behind every feature launch of the call -- the lanes join here and the contour chain stays on the call's stream.
         const bool after_all = (mask & kBehindIntensity) && (mask & NYXHIP_FAM_GLCM);
         if (after_all) lane_join.join();
-        if (int mrc = launch_contour_families(ctx, b, mask, s, d_out, ld, max_px, max_area, max_side, !after_all))
+        if (int mrc = contour_families(ctx, b, mask, s, d_out, ld, max_px, max_area, max_side, !after_all))
             return mrc;
     }
     return NYXHIP_OK;
@@ -1711,6 +1714,12 @@ int launch_device_all(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t mask, con
 
 // ---- what the other host units call (declared in nyxhip_ctx.h) ----
 namespace nyxhip {
+
+int launch_contour_families(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t mask, const nyxhip_settings* s, double* d_out, size_t ld, uint32_t max_px,
+                            uint32_t max_area, uint32_t max_side, bool allow_lane, MomArgs* contour_out)
+{
+    return contour_families(ctx, b, mask, s, d_out, ld, max_px, max_area, max_side, allow_lane, contour_out);
+}
 
 uint32_t pow2ceil(uint32_t v)
 {

@@ -33,10 +33,12 @@ static size_t chunk_table_bytes(uint32_t nt, uint32_t cap)
 
 // One chunk of tiles resident on the device -> rows in d_lab / d_til / d_out (device).  *n_roi_out rows are produced; more than
 // rows_cap -> nothing is written beyond rows_cap and the caller reports the shortage.
+// neighbor_distance > 0: the rows are the kNeighborCols neighbor columns (neighbors_device over the chunk's clouds, one image per tile;
+// family_mask is not read) instead of the family columns -- label scan, ROI assembly and row order are the same piece of code.
 static int tiles_chunk(nyxhip_ctx* ctx, const void* d_inten, int dtI, const void* d_label, int dtL, uint32_t W, uint32_t H, uint32_t nt,
                        int slide_mode, const double* h_smin, const double* h_smax, uint32_t family_mask, const nyxhip_settings* s,
                        uint64_t rows_cap, uint32_t* d_lab, uint32_t* d_til, uint32_t tile_base, double* d_out, size_t d_ld, uint32_t label_limit,
-                       uint64_t* n_roi_out, hipStream_t st)
+                       uint64_t* n_roi_out, hipStream_t st, int32_t neighbor_distance = 0)
 {
     auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
     uint32_t cap = ctx->tile_cap_hint ? ctx->tile_cap_hint : first_tile_cap((uint64_t)W * H);
@@ -110,7 +112,7 @@ static int tiles_chunk(nyxhip_ctx* ctx, const void* d_inten, int dtI, const void
     // INTENSITY / GLCM alone, every ROI LDS-sized: the feature kernel reads the ROIs' windows of the tiles itself and no cloud is
     // materialised (8 B per ROI pixel written and read back otherwise).  Any other family, or ROIs beyond LDS: clouds.
     static const bool no_window = [] { const char* e = getenv("NYXHIP_NO_WINDOW"); return e && *e && *e != '0'; }();   // A/B and tests
-    bool window = !no_window && (family_mask & ~(uint32_t)(NYXHIP_FAM_INTENSITY | NYXHIP_FAM_GLCM)) == 0;
+    bool window = !no_window && !neighbor_distance && (family_mask & ~(uint32_t)(NYXHIP_FAM_INTENSITY | NYXHIP_FAM_GLCM)) == 0;
     if (window) {
         LdsLayout Lt; std::string why_t;
         window = make_layout(family_mask, s, nyxhip_n_columns(family_mask, s), meta[3], meta[4], meta[5], Lt, why_t) == NYXHIP_OK;
@@ -147,6 +149,8 @@ static int tiles_chunk(nyxhip_ctx* ctx, const void* d_inten, int dtI, const void
         ctx->win_next = WindowSrc{d_inten, d_label, dtI, dtL, W, H, R.tile, R.label, R.bbox_x0, R.bbox_y0, no_swz ? 0u : 1u};
     }
     // the box origins inside the tile: one tile is one image, so they are the reference's coordinates (the caliper classes read them)
+    if (neighbor_distance)
+        return neighbors_device(ctx, &b, R.bbox_x0, R.bbox_y0, nullptr, 0, R.tile, neighbor_distance, s, d_out, d_ld, meta[3], meta[4], meta[6]);
     OriginScope origins(ctx, R.bbox_x0, R.bbox_y0);
     int lrc = launch_device(ctx, &b, family_mask, s, d_out, d_ld, meta[3], meta[4], meta[5], meta[6]);
     ctx->win_next = WindowSrc{};
@@ -159,7 +163,7 @@ static int tiles_chunk(nyxhip_ctx* ctx, const void* d_inten, int dtI, const void
     return lrc;
 }
 
-static int tiles_validate(nyxhip_ctx* ctx, const nyxhip_tiles* t, uint32_t family_mask, const nyxhip_settings* s, uint64_t* n_roi_out)
+static int tiles_validate(nyxhip_ctx* ctx, const nyxhip_tiles* t, uint32_t family_mask, const nyxhip_settings* s, uint64_t* n_roi_out, bool neighbors)
 {
     if (!ctx) return NYXHIP_ERR_INVALID_ARG;
     if (!t || !s || !n_roi_out) return fail(ctx, NYXHIP_ERR_INVALID_ARG, "null tiles / settings / n_roi_out");
@@ -167,7 +171,7 @@ static int tiles_validate(nyxhip_ctx* ctx, const nyxhip_tiles* t, uint32_t famil
     if (!t->inten || !t->label || t->width == 0 || t->height == 0) return fail(ctx, NYXHIP_ERR_INVALID_ARG, "null pointer or empty tile");
     auto dt_ok = [](int d) { return d == NYXHIP_U8 || d == NYXHIP_U16 || d == NYXHIP_U32; };
     if (!dt_ok(t->inten_dtype) || !dt_ok(t->label_dtype)) return fail(ctx, NYXHIP_ERR_INVALID_ARG, "tile element types must be NYXHIP_U8 / U16 / U32");
-    if (family_mask == 0 || (family_mask & ~kImplemented)) return fail(ctx, NYXHIP_ERR_INVALID_ARG, "bad family mask");
+    if (!neighbors && (family_mask == 0 || (family_mask & ~kImplemented))) return fail(ctx, NYXHIP_ERR_INVALID_ARG, "bad family mask");
     if (t->memory != NYXHIP_MEM_HOST && t->memory != NYXHIP_MEM_DEVICE && t->memory != NYXHIP_MEM_HOST_OWN_MAPPING) return fail(ctx, NYXHIP_ERR_INVALID_ARG, "bad memory kind");
     if (t->slide_mode < NYXHIP_SLIDE_MONTAGE || t->slide_mode > NYXHIP_SLIDE_GIVEN) return fail(ctx, NYXHIP_ERR_INVALID_ARG, "bad slide_mode");
     if (t->slide_mode == NYXHIP_SLIDE_GIVEN && (!t->slide_min || !t->slide_max)) return fail(ctx, NYXHIP_ERR_INVALID_ARG, "NYXHIP_SLIDE_GIVEN needs slide_min and slide_max");
@@ -293,10 +297,10 @@ struct HostPin {
 // The whole stack in chunks.  label_limit: v1's max_label (validated only).  prepinned: the caller has pinned the arrays.
 static int tiles_run(nyxhip_ctx* ctx, const nyxhip_tiles* t, uint32_t family_mask, const nyxhip_settings* s, uint32_t* out_labels, uint32_t* out_tile_index,
                      uint64_t max_rows, double* out_table, size_t out_ld, uint64_t* n_roi_out, uint32_t label_limit, uint32_t tile_index_base = 0,
-                     const HostPin* prepinned = nullptr)
+                     const HostPin* prepinned = nullptr, int32_t neighbor_distance = 0)
 {
-    if (int vrc = tiles_validate(ctx, t, family_mask, s, n_roi_out)) return vrc;
-    const int n_cols = nyxhip_n_columns(family_mask, s);
+    if (int vrc = tiles_validate(ctx, t, family_mask, s, n_roi_out, neighbor_distance != 0)) return vrc;
+    const int n_cols = neighbor_distance ? kNeighborCols : nyxhip_n_columns(family_mask, s);
     const bool host = t->memory == NYXHIP_MEM_HOST || t->memory == NYXHIP_MEM_HOST_OWN_MAPPING;
     const bool keep = host && out_table == nullptr;                  // result stays in the context (nyxhip_fetch_result)
     if (!keep && (!out_labels || !out_table)) return fail(ctx, NYXHIP_ERR_INVALID_ARG, "null output pointers");
@@ -350,7 +354,8 @@ static int tiles_run(nyxhip_ctx* ctx, const nyxhip_tiles* t, uint32_t family_mas
             uint64_t n = 0;
             int rc = tiles_chunk(ctx, di, t->inten_dtype, dl, t->label_dtype, W, H, nt, t->slide_mode, t->slide_min ? t->slide_min + t0 : nullptr,
                                  t->slide_max ? t->slide_max + t0 : nullptr, family_mask, s, short_out ? 0 : room, out_labels + rows_done,
-                                 out_tile_index ? out_tile_index + rows_done : nullptr, (uint32_t)t0, out_table + rows_done * out_ld, out_ld, label_limit, &n, st);
+                                 out_tile_index ? out_tile_index + rows_done : nullptr, (uint32_t)t0, out_table + rows_done * out_ld, out_ld, label_limit, &n, st,
+                                 neighbor_distance);
             if (rc) return rc;
             if (n > room) short_out = true;
             rows_done += n;
@@ -425,7 +430,7 @@ static int tiles_run(nyxhip_ctx* ctx, const nyxhip_tiles* t, uint32_t family_mas
             }
             rc = tiles_chunk(ctx, slot_inten(k), t->inten_dtype, slot_label(k, nt), t->label_dtype, W, H, nt, t->slide_mode,
                              t->slide_min ? t->slide_min + t0 : nullptr, t->slide_max ? t->slide_max + t0 : nullptr, family_mask, s, cap_rows, d_lab, d_til,
-                             tile_index_base + (uint32_t)t0, d_out, (size_t)n_cols, label_limit, &n, st);
+                             tile_index_base + (uint32_t)t0, d_out, (size_t)n_cols, label_limit, &n, st, neighbor_distance);
             if (rc) return rc;
             if (n > cap_rows) { HIP_TRY(ctx, hipStreamSynchronize(st)); need = (size_t)n * (8 * (size_t)n_cols + 8) + 4096; continue; }
             HIP_TRY(ctx, hipEventRecord(ctx->slot_free[k], st));
@@ -461,6 +466,16 @@ int nyxhip_featurize_tiles_v2(nyxhip_ctx* ctx, const nyxhip_tiles* tiles, uint32
                               uint32_t* out_tile_index, uint64_t max_rows, double* out_table, size_t out_ld, uint64_t* n_roi_out)
 {
     return tiles_run(ctx, tiles, family_mask, s, out_labels, out_tile_index, max_rows, out_table, out_ld, n_roi_out, 0xFFFFFFFFu);
+}
+
+int nyxhip_neighbors_tiles(nyxhip_ctx* ctx, const nyxhip_tiles* tiles, int32_t pixel_distance, const nyxhip_settings* s, uint32_t* out_labels,
+                           uint32_t* out_tile_index, uint64_t max_rows, double* out_table, size_t out_ld, uint64_t* n_roi_out)
+{
+    if (!ctx) return NYXHIP_ERR_INVALID_ARG;
+    if (pixel_distance <= 0) return fail(ctx, NYXHIP_ERR_INVALID_ARG, "pixel_distance must be greater than zero");
+    if (pixel_distance > kNbMaxDistance)
+        return fail(ctx, NYXHIP_ERR_UNSUPPORTED, "pixel_distance beyond 46340: its square overflows the reference's int (neighbors.cpp:242)");
+    return tiles_run(ctx, tiles, 0, s, out_labels, out_tile_index, max_rows, out_table, out_ld, n_roi_out, 0xFFFFFFFFu, 0, nullptr, pixel_distance);
 }
 
 int nyxhip_fetch_result(nyxhip_ctx* ctx, uint32_t* out_labels, uint32_t* out_tile_index, double* out_table, size_t out_ld)

@@ -133,6 +133,21 @@ for _n in CIRCLES:
 for _n in GEODETIC:
     FAMILY_OF[_n] = _abi.FAM_GEODETIC
 
+# NeighborsFeature (featureset.h:162-171): behind ROI_RADIUS_MEDIAN, in front of GLCM_ASM.  The class relates the ROIs of an image to each
+# other, so it is no family of the C ABI's mask: FAM_NEIGHBORS is a marker of this module alone (bit 32: beyond the 32-bit mask, it never
+# crosses the ABI -- split_neighbors() takes it off) that sends a call to the neighbor entries (nyxhip_neighbors_tiles).
+NEIGHBORS = ["NUM_NEIGHBORS", "PERCENT_TOUCHING", "CLOSEST_NEIGHBOR1_DIST", "CLOSEST_NEIGHBOR1_ANG", "CLOSEST_NEIGHBOR2_DIST",
+             "CLOSEST_NEIGHBOR2_ANG", "ANG_BW_NEIGHBORS_MEAN", "ANG_BW_NEIGHBORS_STDDEV", "ANG_BW_NEIGHBORS_MODE"]
+FAM_NEIGHBORS = 1 << 32
+for _n in NEIGHBORS:
+    FAMILY_OF[_n] = FAM_NEIGHBORS
+
+
+def split_neighbors(mask: int) -> Tuple[int, bool]:
+    """(the family mask of the C ABI, whether the neighbor marker was set)."""
+    return mask & 0xFFFFFFFF, bool(mask & FAM_NEIGHBORS)
+
+
 # group tokens (featureset.cpp:650-665) the HIP path can serve completely (the radial distribution has none, featureset.cpp:650-668)
 GROUPS: Dict[str, List[str]] = {
     "*ALL_INTENSITY*": INTENSITY,
@@ -146,6 +161,7 @@ GROUPS: Dict[str, List[str]] = {
     "*GEOMOMS*": SMOMS + IMOMS,      # env_features.cpp:316-333
     "*SGEOMOMS*": SMOMS,
     "*IGEOMOMS*": IMOMS,
+    "*ALL_NEIGHBOR*": NEIGHBORS,
 }
 
 # enum order of every feature code the path covers (one entry per Feature2D code)
@@ -167,10 +183,15 @@ FULL_ORDER: List[str] = INTENSITY + ELLIPSE + EROSION + CATALOGUE_ORDER[len(INTE
 # the four lists before it).  expand() orders by this list.
 _E = FULL_ORDER.index("EULER_NUMBER") + 1
 EXPAND_ORDER: List[str] = FULL_ORDER[:_E] + CIRCLES + GEODETIC + FULL_ORDER[_E:]
+# ... and EXPAND_ORDER with the neighbor codes behind ROI_RADIUS_MEDIAN (EXPAND_ORDER keeps the codes it was introduced with, like the
+# five lists before it).  expand() orders by this list.
+_R = EXPAND_ORDER.index("ROI_RADIUS_MEDIAN") + 1
+REQUEST_ORDER: List[str] = EXPAND_ORDER[:_R] + NEIGHBORS + EXPAND_ORDER[_R:]
 
 
 def expand(features: List[str]) -> Tuple[int, List[str]]:
-    """Expands group tokens, validates names, returns (family mask, requested feature codes in enum order)."""
+    """Expands group tokens, validates names, returns (family mask, requested feature codes in enum order).  The mask holds
+    FAM_NEIGHBORS (bit 32, not a bit of the C ABI: split_neighbors) when a neighbor code is among them."""
     want = set()
     unknown = []
     for f in features:
@@ -189,10 +210,10 @@ def expand(features: List[str]) -> Tuple[int, List[str]]:
             f"ROI_RADIUS_MEDIAN, MIN_FERET_ANGLE, MAX_FERET_ANGLE and STAT_{{FERET,MARTIN,NASSENSTEIN}}_DIAM_{{MIN,MAX,MEAN,MEDIAN,STDDEV,MODE}}, "
             f"{{MAXCHORDS,ALLCHORDS}}_{{MAX,MAX_ANG,MIN,MIN_ANG,MEDIAN,MEAN,MODE,STDDEV}}, MAJOR_AXIS_LENGTH, MINOR_AXIS_LENGTH, ELONGATION, "
             f"ECCENTRICITY, ORIENTATION, ROUNDNESS, EROSIONS_2_VANISH, EROSIONS_2_VANISH_COMPLEMENT, DIAMETER_MIN_ENCLOSING_CIRCLE, "
-            f"DIAMETER_CIRCUMSCRIBING_CIRCLE, DIAMETER_INSCRIBING_CIRCLE, GEODETIC_LENGTH, THICKNESS")
+            f"DIAMETER_CIRCUMSCRIBING_CIRCLE, DIAMETER_INSCRIBING_CIRCLE, GEODETIC_LENGTH, THICKNESS, {', '.join(NEIGHBORS)}")
     if not want:
         raise ValueError("no features requested")
-    ordered = [n for n in EXPAND_ORDER if n in want]
+    ordered = [n for n in REQUEST_ORDER if n in want]
     mask = 0
     for n in ordered:
         mask |= FAMILY_OF[n]

@@ -62,7 +62,7 @@ class Nyxus:
             raise ValueError("anisotropy is outside the MI355X hot path (SURVEY.md section 8)")
 
         self._features = list(features)
-        self._mask, self._requested = featureset.expand(self._features)
+        self._set_features(self._features)
         self._settings = _abi.default_settings(int(coarse_gray_depth), bool(kwargs.get("ibsi", False)))
         self._env = {"neighbor_distance": neighbor_distance, "pixels_per_micron": pixels_per_micron, "n_feature_calc_threads": n_threads,
                      "dynamic_range": kwargs.get("dynamic_range", 10000), "min_intensity": kwargs.get("min_intensity", 0.0),
@@ -83,6 +83,13 @@ class Nyxus:
         self._extra_ctx: List[_lib.Context] = []
         self._valid_output_types = ["pandas", "arrowipc", "parquet"]
         self.error_message = ""
+
+    def _set_features(self, features: List[str]):
+        """self._mask: the family mask of the C ABI; self._neighbors: a neighbor code is requested (featureset.FAM_NEIGHBORS) -- served
+        by the neighbor entry (nyxhip_neighbors_tiles) with `neighbor_distance`, its nine columns to the right of the family table."""
+        self._features = list(features)
+        full, self._requested = featureset.expand(self._features)
+        self._mask, self._neighbors = featureset.split_neighbors(full)
 
     # -- Gabor bank: customize_gabor_feature_imp -> parse_gabor_options_raw_inputs (cli_gabor_options.cpp:14-120)
     def set_gabor_feature_params(self, **kw):
@@ -127,15 +134,31 @@ class Nyxus:
         return int(rl) << 20 if rl is not None and rl > 0 else 0
 
     def _featurize_stack(self, I: np.ndarray, M: np.ndarray, slide_mode: int):
+        """The family table of the stack and, when a neighbor code is requested, the nine neighbor columns to its right (one image per
+        tile; neighbor codes alone: no family call).  With `gpu_devices` the family call is shared by the listed devices; the neighbor
+        call runs on the first context only."""
         ctx = self._context()
-        tiles, labels, table = ctx.featurize_tiles_host(I, M, self._mask, self._settings, slide_mode=slide_mode,
-                                                        max_device_bytes=self._device_budget(), contexts=self._extra_ctx)
+        tiles = labels = table = None
+        if self._mask:
+            tiles, labels, table = ctx.featurize_tiles_host(I, M, self._mask, self._settings, slide_mode=slide_mode,
+                                                            max_device_bytes=self._device_budget(), contexts=self._extra_ctx)
+        if self._neighbors:
+            nt, nl, ntab = ctx.neighbors_tiles_host(I, M, int(self._env["neighbor_distance"]), self._settings,
+                                                    max_device_bytes=self._device_budget())
+            if table is None:
+                tiles, labels, table = nt, nl, ntab
+            else:
+                if not (np.array_equal(nt, tiles) and np.array_equal(nl, labels)):
+                    raise RuntimeError("the neighbor call and the family call disagree about the ROIs of the stack")
+                table = np.ascontiguousarray(np.hstack([table, ntab]))
         _lib.load().nyxhip_finalize_table(table.ctypes.data, table.shape[0], table.shape[1], table.shape[1],
                                           C.c_double(self._settings.soft_nan))
         return tiles, labels, table
 
     def _columns(self):
-        names = _lib.column_names(self._mask, self._settings)
+        names = _lib.column_names(self._mask, self._settings) if self._mask else []
+        if self._neighbors:
+            names = names + _lib.neighbor_column_names()
         angles = [self._settings.glcm_angles[i] for i in range(self._settings.glcm_n_angles)]
         sel = featureset.column_selector(self._requested, names, angles)
         return [names[i] for i in sel], sel
@@ -346,8 +369,7 @@ class Nyxus:
             if key not in valid_params:
                 raise ValueError(f"Invalid environment parameter {key}. Value parameters are {params}")
         if params.get("features"):
-            self._features = list(params["features"])
-            self._mask, self._requested = featureset.expand(self._features)
+            self._set_features(list(params["features"]))
         if params.get("coarse_gray_depth", 0) != 0:      # 0 = "leave as is" (new_bindings_py.cpp set_environment_params_imp)
             gd = int(params["coarse_gray_depth"])
             self._settings.grey_depth = gd
