@@ -469,6 +469,12 @@ __device__ __forceinline__ uint32_t mul_u24_su(uint32_t a, uint32_t b_uniform)
     asm("v_mul_u32_u24 %0, %1, %2" : "=v"(r) : "s"(b_uniform), "v"(a));
     return r;
 }
+__device__ __forceinline__ uint32_t mad_u24_su(uint32_t a, uint32_t b_uniform, uint32_t c)
+{
+    uint32_t r;
+    asm("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(r) : "s"(b_uniform), "v"(a), "v"(c));
+    return r;
+}
 
 __device__ __forceinline__ int mul_i24(int a, int b)      // signed 24-bit factors, full rate
 {

@@ -790,6 +790,10 @@ __device__ __forceinline__ void glcm_features_wave64_v2(const uint16_t* P, int N
 #define STAMP(i) do { } while (0)
 #endif
 
+// fractions of the six percentiles (histogram.h:218-223), indexed by the lane group that holds the percentile (roi_features_body);
+// entries 6 and 7 belong to the groups of the median's two ranks and are not used as fractions
+__constant__ const double kPctFrac[8] = {0.01, 0.1, 0.25, 0.75, 0.9, 0.99, 0.5, 0.5};
+
 // ---- the fused kernel --------------------------------------------------------------
 // GS: per-workgroup scratch in the global workspace instead of LDS (large-ROI launches).
 // C16: the counting table holds 16-bit entries and the value buffer 16-bit offsets from the ROI minimum (every ROI of the
@@ -1460,11 +1464,11 @@ __device__ __forceinline__ void roi_features_body(const RoiArgs& A, const uint64
         STAMP(4);
 
         if (!blank) {
-            // histogram bin boundaries: lower bounds found by binary search, over the value
-            // domain (counting engine) or over the sorted array (sort engine)
-            for (uint32_t t = tid; t < 100 + nb; t += BS) {
-                const bool is100 = t < 100;
-                const uint32_t b = is100 ? t : t - 100;
+            // histogram bin boundaries: the lower bound of bin b (the number of values whose bin index is below b), found over the
+            // value domain (counting engine) or by binary search over the sorted array (sort engine).  is100: the percentile
+            // histogram (100 bins), else the n_hist-bin histogram of entropy / uniformity.
+            auto bin_bound = [&](auto is100_t, const uint32_t b) -> uint32_t {
+                constexpr bool is100 = decltype(is100_t)::value;
                 uint32_t lo;
                 if (use_count) {
                     // smallest offset d in [0, range+1] whose bin index reaches b
@@ -1504,8 +1508,8 @@ __device__ __forceinline__ void roi_features_body(const RoiArgs& A, const uint64
                         if (idx < b) lo = mid + 1; else hi = mid;
                     }
                 }
-                if (is100) s_lb100[b] = lo; else s_lbc[b] = lo;
-            }
+                return lo;
+            };
             STAMP(5);
             if (!use_count) {
                 // mode on the sorted array: longest run, smallest value on ties; every thread
@@ -1545,56 +1549,71 @@ __device__ __forceinline__ void roi_features_body(const RoiArgs& A, const uint64
                     s_stat[S_MODE] = (double)mv;
                 }
             }
-            grp_sync<GS, NW>();
-            STAMP(6);
+            STAMP(6);   // (no barrier here: wave 0 reads the mode it wrote itself or that lies behind the engine's barrier, wave 1 its own bounds)
 
-            // three independent reductions run on three different waves
+            // two independent reductions run on two different waves
             if (NW == 1 || wave == 0) {
-                // percentiles P01,P10,P25,P75,P90,P99 (histogram.h:214-243): the LAST bin i with
-                // runSum_i <= cnt <= runSum_i + bins_i wins (every matching bin overwrites);
-                // runSum_i is exactly the lower bound of bin i.  Lanes test bins i and i+64.
-                const int i0 = lane, i1 = lane + 64;
-                const uint32_t r0 = s_lb100[i0], e0 = (i0 < 99 ? s_lb100[i0 + 1] : n);
-                const uint32_t r1 = i1 < 100 ? s_lb100[i1] : 0u, e1 = i1 < 100 ? (i1 < 99 ? s_lb100[i1 + 1] : n) : 0u;
-                // the six winners are found with the whole wave (two ballots each); lane q then interpolates percentile q -- one
-                // division per lane instead of six per wave -- and lane 0 collects the values
-                int mywin = -1;
-                double mycnt = 0;
-#pragma unroll
-                for (int q = 0; q < 6; q++) {
-                    const double frac = q == 0 ? 0.01 : q == 1 ? 0.1 : q == 2 ? 0.25 : q == 3 ? 0.75 : q == 4 ? 0.9 : 0.99;
-                    const double cnt_p = dn * frac;
-                    bool m0 = (double)r0 <= cnt_p && cnt_p <= (double)e0;
-                    bool m1 = i1 < 100 && (double)r1 <= cnt_p && cnt_p <= (double)e1;
-                    unsigned long long b0 = __ballot(m0), b1 = __ballot(m1);
-                    int win = b1 ? 64 + (63 - __clzll((long long)b1)) : (b0 ? 63 - __clzll((long long)b0) : -1);
-                    if (lane == q) { mywin = win; mycnt = cnt_p; }
-                }
-                double pv = 0;
-                if (mywin >= 0) {
-                    uint32_t rs = s_lb100[mywin], bi = (mywin < 99 ? s_lb100[mywin + 1] : n) - rs;
-                    pv = (mycnt - (double)rs) * binW100 / (double)bi + (double)vmin + binW100 * (double)mywin;
-                }
-                double pq[6];
-#pragma unroll
-                for (int q = 0; q < 6; q++) {
-                    pq[q] = readlane_f64(pv, q);
-                }
+                // percentiles P01,P10,P25,P75,P90,P99 (histogram.h:214-243): the LAST bin i with runSum_i <= cnt <= runSum_i + bins_i
+                // wins (every matching bin overwrites); runSum_i is exactly the lower bound of bin i.  runSum is non-decreasing and
+                // cnt < n, so the winner is the largest i with runSum_i <= c, c = floor(cnt); runSum_i counts the values whose bin
+                // index is below i and the bin index is monotone in the value, so runSum_i <= c holds exactly when the c-th smallest
+                // value x_c (0-based) has a bin index >= i: winner = min(99, idx100(x_c)) -- 99 is the folded last bin
+                // (histogram.h:65-66).  Six order statistics and twelve bounds instead of a hundred bounds; the two order
+                // statistics of the median (histogram.h:268-287: ranks n/2 and n/2 - 1) ride along.
+                // Eight lanes per rank: group g = lane / 8 holds percentile g (g < 6), rank n/2 (g = 6) or rank n/2 - 1 (g = 7).
+                const int g = lane >> 3, sub = lane & 7;
+                const double mycnt = dn * kPctFrac[g];           // (a table read: the six-way choice compiled to a tree of branches)
+                const uint32_t k = g < 6 ? (uint32_t)mycnt : (g == 6 || n / 2 == 0) ? n / 2 : n / 2 - 1;
+                uint32_t xv;                                     // the group's order statistic (a value, not an offset)
+                if (use_count) {
+                    // smallest i with C(i) > k, all eight ranks at once: the lanes of a group probe the ends of the eight parts of the
+                    // group's interval [lo, lo + span), the group's byte of the ballot finds the first hit (C is non-decreasing and
+                    // C(range) = n > k: the last lane of a group always hits) -- four rounds for ranges up to 4095, five for the rest of the 16-bit tables (up to 16383)
+                    uint32_t lom1 = 0xFFFFFFFFu, span = range + 1;   // lom1 = lo - 1 (mod 2^32); span is the same for every group: the loop is wave-uniform
+                    while (span > 1) {
+                        const uint32_t B = (span + 7) >> 3;
+                        uint32_t i = mad_u24_su((uint32_t)sub + 1, B, lom1);   // last position of this lane's part: lo + (sub + 1) B - 1
+                        if (i > range) i = range;
+                        const unsigned long long hit = __ballot(cum(i) > k);
+                        const uint32_t half = lane < 32 ? (uint32_t)hit : (uint32_t)(hit >> 32);
+                        const uint32_t first = (uint32_t)__builtin_ctz(((half >> (lane & 24)) & 0xFFu) | 0x80u);
+                        lom1 = mad_u24_su(first, B, lom1);
+                        span = B;
+                    }
+                    xv = vmin + lom1 + 1;
+                } else
+                    xv = SV(k);
+                // lanes 0 and 1 of a percentile's group: the bounds of the winning bin and of the bin after it (bin 100: n)
+                const uint32_t win = min((uint32_t)idx100(xv), 99u);
+                const uint32_t bb = win + (uint32_t)sub;
+                uint32_t bnd = 0;
+                if (g < 6 && sub < 2)
+                    bnd = bb < 100u ? bin_bound(std::true_type{}, bb) : n;
+                const uint32_t rs = bnd, bi = wave_rol1(bnd) - rs;
+                // (lane 8 q interpolates percentile q -- one division per lane instead of six per wave -- and stores it: the six columns
+                //  lie side by side.  On these lanes bi > 0: the winner is the largest bin whose runSum is <= c, so the next bound
+                //  exceeds c >= rs, and bin 99 ends at n > c.  The other lanes divide by whatever they hold; their values are not read.)
+                const double pv = (mycnt - (double)rs) * binW100 / (double)bi + (double)vmin + binW100 * (double)win;
+                static_assert(I_P10 == I_P01 + 1 && I_P25 == I_P01 + 2 && I_P75 == I_P01 + 3 && I_P90 == I_P01 + 4 && I_P99 == I_P01 + 5, "P01 .. P99 are adjacent columns");
+                if (g < 6 && sub == 0)
+                    o[I_P01 + g] = pv;
+                // (P10 and P90 feed the robust statistics; P25 and P75 the quartile columns, where those are not deferred)
+                const double p10 = readlane_f64(pv, 8), p90 = readlane_f64(pv, 32);
+                const double p25 = DEFER ? 0.0 : readlane_f64(pv, 16), p75 = DEFER ? 0.0 : readlane_f64(pv, 24);
+                const uint32_t hi_v = (uint32_t)__builtin_amdgcn_readlane((int)xv, 48), lo_v = (uint32_t)__builtin_amdgcn_readlane((int)xv, 56);
                 if (lane == 0) {
-                    o[I_P01] = pq[0]; o[I_P10] = pq[1]; o[I_P25] = pq[2]; o[I_P75] = pq[3]; o[I_P90] = pq[4]; o[I_P99] = pq[5];
                     if (!DEFER)                        // (deferred: derived from the P25 and P75 of the row)
-                        close_quartiles(RowColumns{o}, pq[2], pq[3]);
-                    s_stat[S_P10] = pq[1];
-                    s_stat[S_P90] = pq[4];
+                        close_quartiles(RowColumns{o}, p25, p75);
+                    s_stat[S_P10] = p10;
+                    s_stat[S_P90] = p90;
                     if (FUSED) {
                         // bounds of the robust statistics in the offset domain and the populations around them (see the fused sweep):
                         // derived once, here, instead of by every thread of the workgroup
-                        const double p10 = pq[1], p90 = pq[4];
                         uint32_t lox = 0x80000000u, span = 0;                   // empty range unless the bounds say otherwise (NaN: empty)
                         if (p10 <= p90 && p90 >= (double)vmin && p10 <= (double)vmax) {
                             const double cl = ceil(p10), fl = floor(p90);
-                            const uint32_t lo_v = cl <= (double)vmin ? vmin : (uint32_t)cl, hi_v = fl >= (double)vmax ? vmax : (uint32_t)fl;
-                            if (lo_v <= hi_v) { lox = lo_v - vmin; span = hi_v - lo_v; }
+                            const uint32_t lo_b = cl <= (double)vmin ? vmin : (uint32_t)cl, hi_b = fl >= (double)vmax ? vmax : (uint32_t)fl;
+                            if (lo_b <= hi_b) { lox = lo_b - vmin; span = hi_b - lo_b; }
                         }
                         const bool empty = span == 0 && lox == 0x80000000u;
                         uint32_t* const s_rob = (uint32_t*)(s_stat + 6);
@@ -1603,9 +1622,24 @@ __device__ __forceinline__ void roi_features_body(const RoiArgs& A, const uint64
                         s_rob[2] = (empty || lox == 0) ? 0u : cum(lox - 1);       // values below the range
                         s_rob[3] = empty ? 0u : cum(lox + span);                  // values up to its upper end
                     }
+                    // median (histogram.h:268-287)
+                    double median = (n & 1) ? (double)hi_v : (double)(uint32_t)(hi_v + lo_v) / 2.0;
+                    o[I_MEDIAN] = median;
+                    o[I_MODE] = s_stat[S_MODE];
+                    s_stat[S_MEDIAN] = median;
+                    if (FUSED) {   // 2 (median - vmin) as an integer, and #(x <= floor(median)) for the half-integer correction of the MAD
+                        const uint32_t m2x = (uint32_t)((median - (double)vmin) * 2.0);
+                        uint32_t* const s_med = (uint32_t*)(s_stat + 10);
+                        s_med[0] = m2x;
+                        s_med[1] = (m2x & 1u) ? cum(m2x >> 1) : 0u;
+                    }
                 }
             }
             if (NW == 1 || wave == 1) {
+                // the bounds of the nb-bin histogram, filled by the wave that reads them
+                for (uint32_t b = lane; b < nb; b += 64)
+                    s_lbc[b] = bin_bound(std::false_type{}, b);
+                wav_sync<GS>();
                 // entropy / uniformity over the n+1 slots (histogram.h:145-151): slot n is empty
                 double e = 0, u = 0;
                 for (uint32_t k = lane; k < nb; k += 64) {
@@ -1619,44 +1653,6 @@ __device__ __forceinline__ void roi_features_body(const RoiArgs& A, const uint64
                 if (lane == 0) {
                     o[I_ENTROPY] = -e;
                     o[I_UNIFORMITY] = u;
-                }
-            }
-            if (NW == 1 || wave == 2) {
-                // median (histogram.h:268-287): order statistics n/2 and n/2-1
-                uint32_t hi_v, lo_v;
-                if (use_count) {
-                    // smallest i with C(i) > k, for k = n/2 and n/2 - 1: a 64-way search -- every lane probes one position of the
-                    // current interval, a ballot finds the first hit -- two rounds for ranges up to 4096, three up to 2^18
-                    auto kth = [&](uint32_t k) -> uint32_t {
-                        uint32_t lo = 0, span = range + 1;                  // the answer lies in [lo, lo + span)
-                        while (span > 1) {
-                            const uint32_t B = (span + 63) >> 6;
-                            uint32_t i = lo + mul24((uint32_t)lane + 1, B) - 1;   // last position of this lane's block
-                            if (i > range) i = range;
-                            const unsigned long long hit = __ballot(cum(i) > k);
-                            const uint32_t first = hit ? (uint32_t)__builtin_ctzll(hit) : 63u;
-                            lo += first * B;
-                            span = lo + B > range + 1 ? range + 1 - lo : B;
-                        }
-                        return lo;
-                    };
-                    hi_v = vmin + kth(n / 2);
-                    lo_v = vmin + kth(n / 2 ? n / 2 - 1 : 0);
-                } else {
-                    hi_v = SV(n / 2);
-                    lo_v = SV(n / 2 ? n / 2 - 1 : 0);
-                }
-                if (lane == 0) {
-                    double median = (n & 1) ? (double)hi_v : (double)(uint32_t)(hi_v + lo_v) / 2.0;
-                    o[I_MEDIAN] = median;
-                    o[I_MODE] = s_stat[S_MODE];
-                    s_stat[S_MEDIAN] = median;
-                    if (FUSED) {   // 2 (median - vmin) as an integer, and #(x <= floor(median)) for the half-integer correction of the MAD
-                        const uint32_t m2x = (uint32_t)((median - (double)vmin) * 2.0);
-                        uint32_t* const s_med = (uint32_t*)(s_stat + 10);
-                        s_med[0] = m2x;
-                        s_med[1] = (m2x & 1u) ? cum(m2x >> 1) : 0u;
-                    }
                 }
             }
             grp_sync<GS, NW>();
