@@ -366,6 +366,29 @@ int nyxhip_neighbors_tiles(nyxhip_ctx* ctx, const nyxhip_tiles* tiles, int32_t p
                            uint32_t* out_labels, uint32_t* out_tile_index, uint64_t max_rows,
                            double* out_table, size_t out_ld, uint64_t* n_roi_out);
 
+/* ---- the IBSI intensity-histogram class ------------------------------------------
+ * IntensityHistogramFeatures (features/intensity_histogram.cpp:29-325, featureset.h:584-637): the 46 codes IH_MEAN_VAL .. IH_BIN_SIZE, all
+ * derived from one N-bin histogram over the ROI's [min_inten, max_inten], N = settings.grey_depth.  The codes lie at the very end of
+ * Feature2D and every bit of the family mask is spoken for, so the class has entries and an output table [n_roi x NYXHIP_IH_COLS] of its
+ * own, like the neighbor class; nyxhip_n_columns / nyxhip_column_name do not know it.  The class gates itself: with settings.ibsi == 0,
+ * grey_depth < 2 (a negative, i.e. radiomics, grey depth lands here), max_inten <= min_inten or an empty ROI, all 46 values of the row
+ * are settings.soft_nan.  Every column has the reference's bits except IH_ENTROPY_VAL / IH_ENTROPY_IDX, which go through log() and
+ * agree to rounding.  NaN / inf are not replaced (nyxhip_finalize_table), as in every other table.  Integer images only: the reference's
+ * float_domain_map is the identity unless the slide is a float image or HU mode is on, and neither exists behind this ABI.
+ * ibsi != 0 with grey_depth > 4096 is NYXHIP_ERR_UNSUPPORTED: the bin counters live in LDS. */
+#define NYXHIP_IH_COLS 46
+int nyxhip_ih_column_name(int col, char* buf, size_t buf_len);
+
+/* Reads px_offset, inten, min_inten, max_inten of the batch and nothing else (host or device memory, like nyxhip_neighbors_batch;
+ * batch->max_px is a hint as everywhere).  Synchronous. */
+int nyxhip_ih_batch(nyxhip_ctx* ctx, const nyxhip_batch* batch, const nyxhip_settings* s,
+                    double* out_table /* [n_roi x 46] */, size_t out_ld);
+/* The tile path (label scan, ROI assembly, chunks under max_device_bytes) with this class as the reducer; rows in the (tile, label)
+ * order of nyxhip_featurize_tiles_v2, outputs as there. */
+int nyxhip_ih_tiles(nyxhip_ctx* ctx, const nyxhip_tiles* tiles, const nyxhip_settings* s,
+                    uint32_t* out_labels, uint32_t* out_tile_index, uint64_t max_rows,
+                    double* out_table, size_t out_ld, uint64_t* n_roi_out);
+
 /* ---- measurement hooks -------------------------------------------------------
  * Average device time (ms) per featurize call since the last nyxhip_timing_reset(),
  * measured with hipEvents recorded on the launch stream around EVERYTHING the call

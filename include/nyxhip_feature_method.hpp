@@ -117,6 +117,17 @@ enum class Feature2D : int {
     // where the Python face puts their columns; numbered last here for the same reason.
     NUM_NEIGHBORS, PERCENT_TOUCHING, CLOSEST_NEIGHBOR1_DIST, CLOSEST_NEIGHBOR1_ANG, CLOSEST_NEIGHBOR2_DIST, CLOSEST_NEIGHBOR2_ANG,
     ANG_BW_NEIGHBORS_MEAN, ANG_BW_NEIGHBORS_STDDEV, ANG_BW_NEIGHBORS_MODE,
+    // IntensityHistogramFeatures (featureset.h:584-637): the 46 IBSI intensity-histogram codes.  Numbered last here -- which, for once, is
+    // also their true position: the reference appended them to Feature2D so that no existing code shifts.
+    IH_MEAN_VAL, IH_VARIANCE_VAL, IH_SKEWNESS_VAL, IH_EXCESS_KURTOSIS_VAL, IH_MEDIAN_VAL, IH_MINIMUM_VAL, IH_P10_VAL, IH_P90_VAL, IH_MAXIMUM_VAL,
+    IH_MODE_VAL, IH_INTERQUANTILE_RANGE_VAL, IH_RANGE_VAL, IH_MEAN_ABSOLUTE_DEVIATION_VAL, IH_ROBUST_MEAN_ABSOLUTE_DEVIATION_VAL,
+    IH_MEDIAN_ABSOLUTE_DEVIATION_VAL, IH_COEFFICIENT_OF_VARIATION_VAL, IH_QUANTILE_COEFFICIENT_OF_DISPERSION_VAL, IH_ENTROPY_VAL,
+    IH_UNIFORMITY_VAL, IH_ROBUST_MEAN_VAL,
+    IH_MEAN_IDX, IH_VARIANCE_IDX, IH_SKEWNESS_IDX, IH_EXCESS_KURTOSIS_IDX, IH_MEDIAN_IDX, IH_MINIMUM_IDX, IH_P10_IDX, IH_P90_IDX, IH_MAXIMUM_IDX,
+    IH_MODE_IDX, IH_INTERQUANTILE_RANGE_IDX, IH_RANGE_IDX, IH_MEAN_ABSOLUTE_DEVIATION_IDX, IH_ROBUST_MEAN_ABSOLUTE_DEVIATION_IDX,
+    IH_MEDIAN_ABSOLUTE_DEVIATION_IDX, IH_COEFFICIENT_OF_VARIATION_IDX, IH_QUANTILE_COEFFICIENT_OF_DISPERSION_IDX, IH_ENTROPY_IDX,
+    IH_UNIFORMITY_IDX,
+    IH_MAX_GRADIENT, IH_MAX_GRADIENT_IDX, IH_MIN_GRADIENT, IH_MIN_GRADIENT_IDX, IH_ROBUST_MEAN_IDX, IH_NUM_BINS, IH_BIN_SIZE,
     _COUNT_
 };
 
@@ -450,6 +461,54 @@ public:
     }
 };
 
+// IntensityHistogramFeatures (features/intensity_histogram.h): a per-ROI class like the family classes above, but without a bit of the family
+// mask -- served by nyxhip_ih_batch, which reads the intensities and LR::aux_min / aux_max only.  The class gates itself (IBSI off, fewer
+// than 2 bins, a single intensity: 46 times SOFTNAN, intensity_histogram.cpp:304-320), so reduce() may be called under any settings.
+// Integer images: the reference's float / HU domain map is the identity here.
+class IntensityHistogramFeatures : public FeatureMethod {
+public:
+    IntensityHistogramFeatures() : FeatureMethod("IntensityHistogramFeatures") { provide_features(Feature2D::IH_MEAN_VAL, Feature2D::IH_BIN_SIZE); }
+    static bool required(const FeatureSet& fs) { return fs.anyEnabledInRange(Feature2D::IH_MEAN_VAL, Feature2D::IH_BIN_SIZE); }
+    void calculate(LR& r, const Fsettings& s) override { calculate(r, s, Dataset()); }
+    void calculate(LR& r, const Fsettings& s, const Dataset& ds)
+    {
+        std::vector<int> L{r.label};
+        std::unordered_map<int, LR> data;
+        data[r.label] = r;
+        reduce(0, 1, &L, &data, s, ds);
+        held = data[r.label].fvals;
+    }
+    void save_value(std::vector<std::vector<double>>& fv) override { save_range(fv, Feature2D::IH_MEAN_VAL, Feature2D::IH_BIN_SIZE); }
+    static void extract(LR& r, const Fsettings& s, const Dataset& ds = Dataset()) { IntensityHistogramFeatures f; f.calculate(r, s, ds); f.save_value(r.fvals); }
+    static void reduce(size_t start, size_t end, std::vector<int>* labels, std::unordered_map<int, LR>* roiData, const Fsettings& fst, const Dataset&)
+    {
+        if (end <= start) return;
+        nyxhip_settings s = make_settings(fst);
+        const size_t n = end - start;
+        std::vector<uint32_t> mn(n), mx(n), inten;
+        std::vector<uint64_t> off(n + 1, 0);
+        for (size_t i = 0; i < n; i++) {
+            LR& r = (*roiData)[(*labels)[start + i]];
+            mn[i] = r.aux_min; mx[i] = r.aux_max;
+            for (const Pixel2& p : r.raw_pixels) inten.push_back(p.inten);
+            off[i + 1] = inten.size();
+            if (r.fvals.empty()) r.initialize_fvals();
+        }
+        nyxhip_batch b{};
+        b.n_roi = n; b.px_offset = off.data(); b.inten = inten.data(); b.min_inten = mn.data(); b.max_inten = mx.data();
+        b.memory = NYXHIP_MEM_HOST;
+        std::vector<double> table(n * (size_t)NYXHIP_IH_COLS);
+        nyxhip_ctx* ctx = context();
+        if (nyxhip_ih_batch(ctx, &b, &s, table.data(), (size_t)NYXHIP_IH_COLS) != NYXHIP_OK)
+            throw std::runtime_error(std::string("nyxhip_ih_batch: ") + nyxhip_last_error(ctx));
+        for (size_t i = 0; i < n; i++) {
+            LR& r = (*roiData)[(*labels)[start + i]];
+            for (int c = 0; c < NYXHIP_IH_COLS; c++)
+                r.fvals[(int)Feature2D::IH_MEAN_VAL + c].assign(1, table[i * (size_t)NYXHIP_IH_COLS + (size_t)c]);
+        }
+    }
+};
+
 // runParallel (parallel.h:23-42): the GPU batch is the parallel unit, so the slices run back to back on the
 // caller's thread -- same observable contract (every label of [0, datasetSize) reduced on return).
 typedef void (*functype)(size_t, size_t, std::vector<int>*, std::unordered_map<int, LR>*, const Fsettings&, const Dataset&);
@@ -489,6 +548,8 @@ inline void reduce_trivial_rois_manual(std::vector<int>& PendingRoisLabels, std:
     if (Smoms2D_feature::required(fs)) mask |= NYXHIP_FAM_SMOMS;   // reduce_trivial_rois.cpp:326-331
     if (Imoms2D_feature::required(fs)) mask |= NYXHIP_FAM_IMOMS;   // :320-325
     if (mask) reduce_range(mask, 0, PendingRoisLabels.size(), &PendingRoisLabels, &roiData, s, ds);
+    if (IntensityHistogramFeatures::required(fs))                  // a call of its own: the class has no bit of the family mask
+        IntensityHistogramFeatures::reduce(0, PendingRoisLabels.size(), &PendingRoisLabels, &roiData, s, ds);
 }
 
 } // namespace NyxusHip

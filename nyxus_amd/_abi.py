@@ -59,6 +59,7 @@ SLIDE_MONTAGE, SLIDE_PER_TILE, SLIDE_GIVEN = 0, 1, 2
 
 MAX_GLCM_ANGLES = 4
 NEIGHBOR_COLS = 9            # NYXHIP_NEIGHBOR_COLS: the table of nyxhip_neighbors_batch / _tiles (no family bit: the class relates the ROIs of an image)
+IH_COLS = 46                 # NYXHIP_IH_COLS: the table of nyxhip_ih_batch / _tiles (no family bit: every bit of the mask is spoken for)
 MAX_GABOR_FILTERS = 16
 
 

@@ -29,6 +29,7 @@ ABI_SYMBOLS = [
     "nyxhip_featurize_tiles_v2", "nyxhip_fetch_result", "nyxhip_featurize_tiles_sharded", "nyxhip_fetch_result_sharded",
     "nyxhip_launch_report", "nyxhip_featurize_batch_at", "nyxhip_featurize_batch_async_at",
     "nyxhip_neighbor_column_name", "nyxhip_neighbors_batch", "nyxhip_neighbors_tiles",
+    "nyxhip_ih_column_name", "nyxhip_ih_batch", "nyxhip_ih_tiles",
 ]
 
 
@@ -120,6 +121,14 @@ def load() -> C.CDLL:
         lib.nyxhip_neighbors_tiles.argtypes = [C.c_void_p, P(_abi.Tiles), C.c_int32, P(_abi.Settings), C.c_void_p, C.c_void_p, C.c_uint64,
                                                C.c_void_p, C.c_size_t, P(C.c_uint64)]
         lib.nyxhip_neighbors_tiles.restype = C.c_int
+    if hasattr(lib, "nyxhip_ih_batch"):          # (absent from older builds of the ABI selected through NYXHIP_LIB for A/B runs)
+        lib.nyxhip_ih_column_name.argtypes = [C.c_int, C.c_char_p, C.c_size_t]
+        lib.nyxhip_ih_column_name.restype = C.c_int
+        lib.nyxhip_ih_batch.argtypes = [C.c_void_p, P(_abi.Batch), P(_abi.Settings), C.c_void_p, C.c_size_t]
+        lib.nyxhip_ih_batch.restype = C.c_int
+        lib.nyxhip_ih_tiles.argtypes = [C.c_void_p, P(_abi.Tiles), P(_abi.Settings), C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_size_t,
+                                        P(C.c_uint64)]
+        lib.nyxhip_ih_tiles.restype = C.c_int
     if hasattr(lib, "nyxhip_launch_report"):     # (absent from older builds of the ABI selected through NYXHIP_LIB for A/B runs)
         lib.nyxhip_launch_report.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
         lib.nyxhip_launch_report.restype = C.c_int
@@ -149,6 +158,19 @@ def neighbor_column_names() -> List[str]:
         rc = lib.nyxhip_neighbor_column_name(i, buf, 128)
         if rc != 0:
             raise NyxHipError(rc, f"neighbor column {i}")
+        out.append(buf.value.decode())
+    return out
+
+
+def ih_column_names() -> List[str]:
+    """The 46 columns of nyxhip_ih_batch / _tiles, enum order."""
+    lib = load()
+    buf = C.create_string_buffer(128)
+    out = []
+    for i in range(_abi.IH_COLS):
+        rc = lib.nyxhip_ih_column_name(i, buf, 128)
+        if rc != 0:
+            raise NyxHipError(rc, f"intensity-histogram column {i}")
         out.append(buf.value.decode())
     return out
 
@@ -255,6 +277,40 @@ class Context:
         t.max_device_bytes = int(max_device_bytes)
         n = C.c_uint64(0)
         self._check(self._lib.nyxhip_neighbors_tiles(self._h, C.byref(t), int(distance), C.byref(s), None, None, 0, None, 0, C.byref(n)))
+        labels = np.zeros(n.value, np.uint32); tiles = np.zeros(n.value, np.uint32); table = np.empty((n.value, ncol), np.float64)
+        self._check(self._lib.nyxhip_fetch_result(self._h, labels.ctypes.data, tiles.ctypes.data, table.ctypes.data, ncol))
+        return tiles, labels, table
+
+    def ih_host(self, batch: _abi.HostBatch, s: _abi.Settings) -> np.ndarray:
+        """The intensity-histogram columns [n_roi x 46] of a host batch (nyxhip_ih_batch); NaN / inf are left in place."""
+        out = np.empty((batch.n_roi, _abi.IH_COLS), np.float64)
+        cb = batch.c_struct()
+        self._check(self._lib.nyxhip_ih_batch(self._h, C.byref(cb), C.byref(s), out.ctypes.data, _abi.IH_COLS))
+        return out
+
+    def ih_device(self, cb: _abi.Batch, s: _abi.Settings, out_ptr: int, ld: int):
+        """Device pointers in ``cb`` (px_offset, inten, min_inten, max_inten) and a device table; synchronous (nyxhip_ih_batch)."""
+        self._check(self._lib.nyxhip_ih_batch(self._h, C.byref(cb), C.byref(s), C.c_void_p(out_ptr), ld))
+
+    def ih_tiles_host(self, inten: np.ndarray, label: np.ndarray, s: _abi.Settings, max_device_bytes: int = 0):
+        """The intensity-histogram columns of a stack [n_tiles, H, W] of host tiles (nyxhip_ih_tiles).  Returns (tile_index, labels,
+        table [n_roi x 46]) in the (tile, label) row order of featurize_tiles_host."""
+        if inten.shape != label.shape or inten.ndim != 3:
+            raise ValueError("stacks must be 3-D arrays [n_tiles, H, W] of the same shape")
+        dt = {np.dtype(np.uint8): _abi.U8, np.dtype(np.uint16): _abi.U16, np.dtype(np.uint32): _abi.U32}
+        inten = np.ascontiguousarray(inten if inten.dtype in dt else inten.astype(np.uint32))
+        label = np.ascontiguousarray(label if label.dtype in dt else label.astype(np.uint32))
+        nt, h, w = inten.shape
+        ncol = _abi.IH_COLS
+        if nt == 0:
+            return np.zeros(0, np.uint32), np.zeros(0, np.uint32), np.zeros((0, ncol))
+        t = _abi.Tiles()
+        t.inten = inten.ctypes.data; t.label = label.ctypes.data
+        t.inten_dtype = dt[inten.dtype]; t.label_dtype = dt[label.dtype]
+        t.width = w; t.height = h; t.n_tiles = nt; t.memory = _abi.MEM_HOST; t.slide_mode = _abi.SLIDE_MONTAGE
+        t.max_device_bytes = int(max_device_bytes)
+        n = C.c_uint64(0)
+        self._check(self._lib.nyxhip_ih_tiles(self._h, C.byref(t), C.byref(s), None, None, 0, None, 0, C.byref(n)))
         labels = np.zeros(n.value, np.uint32); tiles = np.zeros(n.value, np.uint32); table = np.empty((n.value, ncol), np.float64)
         self._check(self._lib.nyxhip_fetch_result(self._h, labels.ctypes.data, tiles.ctypes.data, table.ctypes.data, ncol))
         return tiles, labels, table

@@ -5,6 +5,7 @@
 //   nyxhip_tiles.hip     the fused tile path and its host staging
 //   nyxhip_api.hip       context life cycle, the batch entry points, timing, launch report
 //   nyxhip_neighbors.hip the neighbor entries: column names, the launches over a device-resident batch, nyxhip_neighbors_batch
+//   nyxhip_ih.hip        the intensity-histogram entries: column names, the launches over a device-resident batch, nyxhip_ih_batch
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -27,6 +28,7 @@
 #include "roi_erosion.h"
 #include "roi_circle.h"
 #include "roi_neighbors.h"
+#include "roi_ih.h"
 
 // One hipMalloc allocation, grow-only.  hipFree waits for the device's work by itself; the stream handed to reserve() states which
 // work the site knows to be using the old block.
@@ -272,5 +274,12 @@ int launch_contour_families(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t mas
 int neighbors_device(nyxhip_ctx* ctx, const nyxhip_batch* b, const uint32_t* d_ox, const uint32_t* d_oy, const uint64_t* d_image_offset, uint64_t n_images,
                      const uint32_t* d_image_id, int32_t pixel_distance, const nyxhip_settings* s, double* d_out, size_t ld, uint32_t max_px,
                      uint32_t max_area, uint32_t max_side);
+// nyxhip_ih.hip: the kIhCols intensity-histogram columns of a device-resident batch -> d_out [n_roi x ld] (enqueued on the context's stream).
+// Reads px_offset, inten, min_inten, max_inten of the batch.  max_px: the largest ROI (0: not known).
+int ih_settings_check(nyxhip_ctx* ctx, const nyxhip_settings* s);      // NYXHIP_ERR_UNSUPPORTED beyond kIhMaxBins
+int ih_device(nyxhip_ctx* ctx, const nyxhip_batch* b, const nyxhip_settings* s, double* d_out, size_t ld, uint32_t max_px);
+// the tile path's reducers besides the family kernels (the neighbor_distance slot of tiles_run / tiles_chunk): > 0 the neighbor class at that
+// distance, kTilesReducerIh the intensity-histogram class
+constexpr int32_t kTilesReducerIh = -1;
 
 } // namespace nyxhip

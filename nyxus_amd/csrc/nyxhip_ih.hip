@@ -1,0 +1,105 @@
+// nyxhip_ih.hip -- the intensity-histogram entries of include/nyxhip.h: column names, the launches over a device-resident batch (ih_device) and
+// nyxhip_ih_batch.  The tile entry (nyxhip_ih_tiles) lives with the tile path in nyxhip_tiles.hip.
+#include "nyxhip_ctx.h"
+
+using namespace nyxhip;
+
+namespace nyxhip {
+
+static const char* const kIhNames[kIhCols] = {
+    "IH_MEAN_VAL", "IH_VARIANCE_VAL", "IH_SKEWNESS_VAL", "IH_EXCESS_KURTOSIS_VAL", "IH_MEDIAN_VAL", "IH_MINIMUM_VAL", "IH_P10_VAL", "IH_P90_VAL",
+    "IH_MAXIMUM_VAL", "IH_MODE_VAL", "IH_INTERQUANTILE_RANGE_VAL", "IH_RANGE_VAL", "IH_MEAN_ABSOLUTE_DEVIATION_VAL",
+    "IH_ROBUST_MEAN_ABSOLUTE_DEVIATION_VAL", "IH_MEDIAN_ABSOLUTE_DEVIATION_VAL", "IH_COEFFICIENT_OF_VARIATION_VAL",
+    "IH_QUANTILE_COEFFICIENT_OF_DISPERSION_VAL", "IH_ENTROPY_VAL", "IH_UNIFORMITY_VAL", "IH_ROBUST_MEAN_VAL",
+    "IH_MEAN_IDX", "IH_VARIANCE_IDX", "IH_SKEWNESS_IDX", "IH_EXCESS_KURTOSIS_IDX", "IH_MEDIAN_IDX", "IH_MINIMUM_IDX", "IH_P10_IDX", "IH_P90_IDX",
+    "IH_MAXIMUM_IDX", "IH_MODE_IDX", "IH_INTERQUANTILE_RANGE_IDX", "IH_RANGE_IDX", "IH_MEAN_ABSOLUTE_DEVIATION_IDX",
+    "IH_ROBUST_MEAN_ABSOLUTE_DEVIATION_IDX", "IH_MEDIAN_ABSOLUTE_DEVIATION_IDX", "IH_COEFFICIENT_OF_VARIATION_IDX",
+    "IH_QUANTILE_COEFFICIENT_OF_DISPERSION_IDX", "IH_ENTROPY_IDX", "IH_UNIFORMITY_IDX",
+    "IH_MAX_GRADIENT", "IH_MAX_GRADIENT_IDX", "IH_MIN_GRADIENT", "IH_MIN_GRADIENT_IDX", "IH_ROBUST_MEAN_IDX", "IH_NUM_BINS", "IH_BIN_SIZE"};
+
+int ih_settings_check(nyxhip_ctx* ctx, const nyxhip_settings* s)
+{
+    if (s->ibsi && s->grey_depth > kIhMaxBins)
+        return fail(ctx, NYXHIP_ERR_UNSUPPORTED, "intensity histogram: grey_depth beyond 4096 bins (the counters of a workgroup's ROIs live in 64 KiB of LDS)");
+    return NYXHIP_OK;
+}
+
+int ih_device(nyxhip_ctx* ctx, const nyxhip_batch* b, const nyxhip_settings* s, double* d_out, size_t ld, uint32_t max_px)
+{
+    if (b->n_roi == 0) return NYXHIP_OK;
+    if (int rc = ih_settings_check(ctx, s)) return rc;
+    // A/B knob of tools/ih_probe.py: every ROI through the workgroup form
+    static const bool one_form = [] { const char* e = getenv("NYXHIP_IH_ONE_FORM"); return e && *e && *e != '0'; }();
+    IhArgs a;
+    memset(&a, 0, sizeof(a));
+    a.n_roi = b->n_roi; a.px_offset = b->px_offset; a.inten = b->inten; a.vmin = b->min_inten; a.vmax = b->max_inten;
+    a.n_bins = s->grey_depth; a.ibsi = s->ibsi; a.soft_nan = s->soft_nan; a.out = d_out; a.ld = ld;
+    a.wave_px = one_form ? 0u : kIhWavePx;
+    // max_px == 0: not known.  Every ROI belongs to exactly one form; a form without a member is not launched when that is known.
+    // (An empty ROI belongs to the wave form, which writes its soft_nan row.)
+    const bool block_form = max_px == 0 || max_px > a.wave_px;
+    if (int rc = launch_roi_ih(a, ctx->stream(), true, block_form))
+        return fail(ctx, NYXHIP_ERR_HIP, std::string("intensity-histogram kernel: launch failed: ") + hipGetErrorString((hipError_t)rc));
+    return NYXHIP_OK;
+}
+
+} // namespace nyxhip
+
+extern "C" {
+
+int nyxhip_ih_column_name(int col, char* buf, size_t buf_len)
+{
+    if (!buf || buf_len == 0 || col < 0 || col >= kIhCols) return NYXHIP_ERR_INVALID_ARG;
+    snprintf(buf, buf_len, "%s", kIhNames[col]);
+    return NYXHIP_OK;
+}
+
+int nyxhip_ih_batch(nyxhip_ctx* ctx, const nyxhip_batch* b, const nyxhip_settings* s, double* out, size_t ld)
+{
+    if (!ctx) return NYXHIP_ERR_INVALID_ARG;
+    if (!b || !s || !out) return fail(ctx, NYXHIP_ERR_INVALID_ARG, "null batch / settings / out_table");
+    if (b->n_roi && (!b->px_offset || !b->inten || !b->min_inten || !b->max_inten))
+        return fail(ctx, NYXHIP_ERR_INVALID_ARG, "batch has null array pointers (the intensity-histogram entries read px_offset, inten, min_inten, max_inten)");
+    if (ld < (size_t)kIhCols) return fail(ctx, NYXHIP_ERR_INVALID_ARG, "out_ld smaller than the column count");
+    if (b->n_roi > 0x7FFFFFFFull) return fail(ctx, NYXHIP_ERR_INVALID_ARG, "too many ROIs in one batch");
+    if (b->memory != NYXHIP_MEM_DEVICE && b->memory != NYXHIP_MEM_HOST) return fail(ctx, NYXHIP_ERR_INVALID_ARG, "bad batch->memory");
+    if (int rc = ih_settings_check(ctx, s)) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (b->n_roi == 0) return NYXHIP_OK;
+    hipStream_t st = ctx->stream();
+    if (b->memory == NYXHIP_MEM_DEVICE) {
+        if (int rc = ih_device(ctx, b, s, out, ld, b->max_px)) return rc;
+        return nyxhip_sync(ctx);
+    }
+    // host batch: check the CSR array, stage the four arrays into one device slab, run, copy the table back
+    const uint64_t nr = b->n_roi, npx = b->px_offset[nr];
+    uint32_t max_px = 0;
+    for (uint64_t r = 0; r < nr; r++) {
+        if (b->px_offset[r + 1] < b->px_offset[r]) return fail(ctx, NYXHIP_ERR_INVALID_ARG, "px_offset is not monotone");
+        const uint64_t n = b->px_offset[r + 1] - b->px_offset[r];
+        if (n > 0xFFFFFFFFull) return fail(ctx, NYXHIP_ERR_ROI_TOO_LARGE, "ROI exceeds 2^32 pixels");
+        max_px = std::max(max_px, (uint32_t)n);
+    }
+    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    const size_t o_off = 0, o_i = al(o_off + 8 * (nr + 1)), o_mn = al(o_i + 4 * npx), o_mx = al(o_mn + 4 * nr), o_out = al(o_mx + 4 * nr),
+                 total = al(o_out + 8ull * nr * kIhCols);
+    if (int rc = ensure_stage(ctx, total)) return rc;
+    char* const base = ctx->d_stage.as<char>();
+    HIP_TRY(ctx, hipMemcpyAsync(base + o_off, b->px_offset, 8 * (nr + 1), hipMemcpyHostToDevice, st));
+    if (npx) HIP_TRY(ctx, hipMemcpyAsync(base + o_i, b->inten, 4 * npx, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(base + o_mn, b->min_inten, 4 * nr, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(base + o_mx, b->max_inten, 4 * nr, hipMemcpyHostToDevice, st));
+    nyxhip_batch d;
+    memset(&d, 0, sizeof(d));
+    d.n_roi = nr; d.memory = NYXHIP_MEM_DEVICE;
+    d.px_offset = (const uint64_t*)(base + o_off); d.inten = (const uint32_t*)(base + o_i);
+    d.min_inten = (const uint32_t*)(base + o_mn); d.max_inten = (const uint32_t*)(base + o_mx);
+    double* const d_out = (double*)(base + o_out);
+    if (int rc = ih_device(ctx, &d, s, d_out, (size_t)kIhCols, std::max(max_px, 1u))) return rc;
+    HIP_TRY(ctx, hipMemcpy2DAsync(out, ld * sizeof(double), d_out, (size_t)kIhCols * sizeof(double), (size_t)kIhCols * sizeof(double), nr,
+                                  hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    return check_status(ctx);
+}
+
+} // extern "C"

@@ -142,6 +142,24 @@ FAM_NEIGHBORS = 1 << 32
 for _n in NEIGHBORS:
     FAMILY_OF[_n] = FAM_NEIGHBORS
 
+# IntensityHistogramFeatures (featureset.h:584-637): the 46 IBSI intensity-histogram codes at the very end of Feature2D, behind IMOM_WHU7.  Like
+# the neighbor class it is no family of the C ABI's mask (every bit is spoken for): FAM_IH is a marker of this module alone (bit 33, it never
+# crosses the ABI -- split_neighbors() takes it off, split_ih() reads it) that sends a call to the entries of its own (nyxhip_ih_tiles).
+# The class exists in IBSI mode only: with `ibsi` off the codes are dropped at call time (env_features.cpp:516-527; nyxus.py).
+_IH_STATS = ["MEAN", "VARIANCE", "SKEWNESS", "EXCESS_KURTOSIS", "MEDIAN", "MINIMUM", "P10", "P90", "MAXIMUM", "MODE", "INTERQUANTILE_RANGE", "RANGE",
+             "MEAN_ABSOLUTE_DEVIATION", "ROBUST_MEAN_ABSOLUTE_DEVIATION", "MEDIAN_ABSOLUTE_DEVIATION", "COEFFICIENT_OF_VARIATION",
+             "QUANTILE_COEFFICIENT_OF_DISPERSION", "ENTROPY", "UNIFORMITY"]
+IH = (["IH_%s_VAL" % k for k in _IH_STATS] + ["IH_ROBUST_MEAN_VAL"] + ["IH_%s_IDX" % k for k in _IH_STATS]
+      + ["IH_MAX_GRADIENT", "IH_MAX_GRADIENT_IDX", "IH_MIN_GRADIENT", "IH_MIN_GRADIENT_IDX", "IH_ROBUST_MEAN_IDX", "IH_NUM_BINS", "IH_BIN_SIZE"])
+FAM_IH = 1 << 33
+for _n in IH:
+    FAMILY_OF[_n] = FAM_IH
+
+
+def split_ih(mask: int) -> bool:
+    """Whether the intensity-histogram marker is set."""
+    return bool(mask & FAM_IH)
+
 
 def split_neighbors(mask: int) -> Tuple[int, bool]:
     """(the family mask of the C ABI, whether the neighbor marker was set)."""
@@ -162,6 +180,7 @@ GROUPS: Dict[str, List[str]] = {
     "*SGEOMOMS*": SMOMS,
     "*IGEOMOMS*": IMOMS,
     "*ALL_NEIGHBOR*": NEIGHBORS,
+    "*ALL_IH*": IH,                  # FG2_IH; served in IBSI mode only
 }
 
 # enum order of every feature code the path covers (one entry per Feature2D code)
@@ -187,11 +206,15 @@ EXPAND_ORDER: List[str] = FULL_ORDER[:_E] + CIRCLES + GEODETIC + FULL_ORDER[_E:]
 # five lists before it).  expand() orders by this list.
 _R = EXPAND_ORDER.index("ROI_RADIUS_MEDIAN") + 1
 REQUEST_ORDER: List[str] = EXPAND_ORDER[:_R] + NEIGHBORS + EXPAND_ORDER[_R:]
+# ... and REQUEST_ORDER with the intensity-histogram codes behind IMOM_WHU7, the end of the enum (REQUEST_ORDER keeps the codes it was
+# introduced with, like the six lists before it).  expand() orders by this list.
+IH_REQUEST_ORDER: List[str] = REQUEST_ORDER + IH
 
 
 def expand(features: List[str]) -> Tuple[int, List[str]]:
     """Expands group tokens, validates names, returns (family mask, requested feature codes in enum order).  The mask holds
-    FAM_NEIGHBORS (bit 32, not a bit of the C ABI: split_neighbors) when a neighbor code is among them."""
+    FAM_NEIGHBORS (bit 32, not a bit of the C ABI: split_neighbors) when a neighbor code is among them, and FAM_IH (bit 33, split_ih) when an
+    intensity-histogram code is."""
     want = set()
     unknown = []
     for f in features:
@@ -210,10 +233,11 @@ def expand(features: List[str]) -> Tuple[int, List[str]]:
             f"ROI_RADIUS_MEDIAN, MIN_FERET_ANGLE, MAX_FERET_ANGLE and STAT_{{FERET,MARTIN,NASSENSTEIN}}_DIAM_{{MIN,MAX,MEAN,MEDIAN,STDDEV,MODE}}, "
             f"{{MAXCHORDS,ALLCHORDS}}_{{MAX,MAX_ANG,MIN,MIN_ANG,MEDIAN,MEAN,MODE,STDDEV}}, MAJOR_AXIS_LENGTH, MINOR_AXIS_LENGTH, ELONGATION, "
             f"ECCENTRICITY, ORIENTATION, ROUNDNESS, EROSIONS_2_VANISH, EROSIONS_2_VANISH_COMPLEMENT, DIAMETER_MIN_ENCLOSING_CIRCLE, "
-            f"DIAMETER_CIRCUMSCRIBING_CIRCLE, DIAMETER_INSCRIBING_CIRCLE, GEODETIC_LENGTH, THICKNESS, {', '.join(NEIGHBORS)}")
+            f"DIAMETER_CIRCUMSCRIBING_CIRCLE, DIAMETER_INSCRIBING_CIRCLE, GEODETIC_LENGTH, THICKNESS, {', '.join(NEIGHBORS)}, "
+            f"{', '.join(IH)} (IBSI mode)")
     if not want:
         raise ValueError("no features requested")
-    ordered = [n for n in REQUEST_ORDER if n in want]
+    ordered = [n for n in IH_REQUEST_ORDER if n in want]
     mask = 0
     for n in ordered:
         mask |= FAMILY_OF[n]

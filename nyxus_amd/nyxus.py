@@ -86,10 +86,24 @@ class Nyxus:
 
     def _set_features(self, features: List[str]):
         """self._mask: the family mask of the C ABI; self._neighbors: a neighbor code is requested (featureset.FAM_NEIGHBORS) -- served
-        by the neighbor entry (nyxhip_neighbors_tiles) with `neighbor_distance`, its nine columns to the right of the family table."""
+        by the neighbor entry (nyxhip_neighbors_tiles) with `neighbor_distance`, its nine columns to the right of the family table;
+        self._ih: an intensity-histogram code is requested (featureset.FAM_IH) -- served by nyxhip_ih_tiles, its 46 columns last."""
         self._features = list(features)
         full, self._requested = featureset.expand(self._features)
         self._mask, self._neighbors = featureset.split_neighbors(full)
+        self._ih = featureset.split_ih(full)
+
+    def _active(self):
+        """(the feature codes of a call, whether the intensity-histogram entry runs).  The IH class exists in IBSI mode only: with `ibsi`
+        off at call time its codes are dropped, as the reference drops them when it expands the feature groups
+        (env_features.cpp:516-527); a request that then holds nothing is an error."""
+        ih = self._ih and bool(self._settings.ibsi)
+        req = self._requested
+        if self._ih and not ih:
+            req = [c for c in req if featureset.FAMILY_OF[c] != featureset.FAM_IH]
+        if not req:
+            raise ValueError("no features requested")
+        return req, ih
 
     # -- Gabor bank: customize_gabor_feature_imp -> parse_gabor_options_raw_inputs (cli_gabor_options.cpp:14-120)
     def set_gabor_feature_params(self, **kw):
@@ -135,8 +149,10 @@ class Nyxus:
 
     def _featurize_stack(self, I: np.ndarray, M: np.ndarray, slide_mode: int):
         """The family table of the stack and, when a neighbor code is requested, the nine neighbor columns to its right (one image per
-        tile; neighbor codes alone: no family call).  With `gpu_devices` the family call is shared by the listed devices; the neighbor
-        call runs on the first context only."""
+        tile; neighbor codes alone: no family call), then the 46 intensity-histogram columns when one of them is requested in IBSI mode.
+        With `gpu_devices` the family call is shared by the listed devices; the neighbor call and the intensity-histogram call run on
+        the first context only."""
+        _, ih = self._active()
         ctx = self._context()
         tiles = labels = table = None
         if self._mask:
@@ -151,16 +167,27 @@ class Nyxus:
                 if not (np.array_equal(nt, tiles) and np.array_equal(nl, labels)):
                     raise RuntimeError("the neighbor call and the family call disagree about the ROIs of the stack")
                 table = np.ascontiguousarray(np.hstack([table, ntab]))
+        if ih:
+            ht, hl, htab = ctx.ih_tiles_host(I, M, self._settings, max_device_bytes=self._device_budget())
+            if table is None:
+                tiles, labels, table = ht, hl, htab
+            else:
+                if not (np.array_equal(ht, tiles) and np.array_equal(hl, labels)):
+                    raise RuntimeError("the intensity-histogram call and the family call disagree about the ROIs of the stack")
+                table = np.ascontiguousarray(np.hstack([table, htab]))
         _lib.load().nyxhip_finalize_table(table.ctypes.data, table.shape[0], table.shape[1], table.shape[1],
                                           C.c_double(self._settings.soft_nan))
         return tiles, labels, table
 
     def _columns(self):
+        requested, ih = self._active()
         names = _lib.column_names(self._mask, self._settings) if self._mask else []
         if self._neighbors:
             names = names + _lib.neighbor_column_names()
+        if ih:
+            names = names + _lib.ih_column_names()
         angles = [self._settings.glcm_angles[i] for i in range(self._settings.glcm_n_angles)]
-        sel = featureset.column_selector(self._requested, names, angles)
+        sel = featureset.column_selector(requested, names, angles)
         return [names[i] for i in sel], sel
 
     def featurize(self, intensity_images: np.ndarray, label_images: np.ndarray, intensity_names: list = [],
