@@ -120,7 +120,13 @@ enum {
  * GLCMFeature::angles / symmetric_glcm (features/glcm.cpp:8-9) and the Gabor
  * bank (features/gabor.cpp:14-25). */
 typedef struct nyxhip_settings {
-    double soft_nan;          /* NyxSetting::SOFTNAN  (default 0.0)            */
+    double soft_nan;          /* NyxSetting::SOFTNAN  (default 0.0): written where the
+                                 reference writes it AND the value reaches its table.
+                                 Not so for GLCM on a ROI whose binned minimum equals
+                                 its binned maximum: glcm.cpp:27-95 assigns it, save_value
+                                 (:210-215) replaces it, and the row is 0.0.  INTENSITY
+                                 and the moment families never write it (raw NaN stays:
+                                 nyxhip_finalize_table).                             */
     double tiny;              /* NyxSetting::TINY     (default 1e-10)          */
     int32_t grey_depth;       /* NyxSetting::GREYDEPTH: >0 matlab binning with
                                  that many levels, <0 radiomics binning with

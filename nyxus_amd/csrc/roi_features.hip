@@ -1845,9 +1845,9 @@ __device__ __forceinline__ void roi_features_body(const RoiArgs& A, const uint64
         const bool degenerate = FAM == 3 ? bin_pixel(vmin, vmin, vmax, B->glcm_grey_depth) == bin_pixel(vmax, vmin, vmax, B->glcm_grey_depth) : s_stat[S_NG] != 0.0;
         if (tid == 0)
             B->glcm_ng[roi] = degenerate ? 0u : (uint32_t)Ng;
-        if (degenerate) {
+        if (degenerate) {                             // 0.0, not soft_nan: save_value() undoes the guard's assignments (glcm.cpp:210-215)
             for (int c = tid; c < kGlcmAngled * na + kGlcmAve; c += BS)
-                o[c] = B->soft_nan;
+                o[c] = 0.0;
             return;
         }
         const bool symmetric = B->glcm_symmetric != 0;
@@ -2083,9 +2083,9 @@ __device__ __forceinline__ void roi_features_body(const RoiArgs& A, const uint64
         const bool split = SPLIT && !degenerate && !too_big;
         if (SPLIT && tid == 0)
             B->glcm_ng[roi] = split ? (uint32_t)Ng : 0u;
-        if (degenerate) {
+        if (degenerate) {                             // 0.0, not soft_nan: save_value() undoes the guard's assignments (glcm.cpp:210-215)
             for (int c = tid; c < ncol_g; c += BS)
-                o[c] = B->soft_nan;
+                o[c] = 0.0;
         } else if (too_big) {
             for (int c = tid; c < ncol_g; c += BS)
                 o[c] = __longlong_as_double(0x7ff8000000000000LL);

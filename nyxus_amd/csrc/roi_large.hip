@@ -540,7 +540,7 @@ __global__ __launch_bounds__(256) void large_finish_kernel(const LargeArgs A)
         const int na = A.glcm_na, ncol_g = kGlcmAngled * na + kGlcmAve;
         const int greyInfo = A.ibsi ? 0 : A.grey_depth;
         if (bin_pixel(vmin, vmin, vmax, A.glcm_grey_depth) == bin_pixel(vmax, vmin, vmax, A.glcm_grey_depth)) {   // glcm.cpp:27-95
-            for (int c = tid; c < ncol_g; c += BS) o[c] = A.soft_nan;
+            for (int c = tid; c < ncol_g; c += BS) o[c] = 0.0;   // not soft_nan: save_value() undoes the guard's assignments (glcm.cpp:210-215)
             return;
         }
         // level values | per-angle features | per-angle marginals: in LDS up to ~240 levels, else in the ROI's block (IBSI on wide data)
@@ -554,7 +554,7 @@ __global__ __launch_bounds__(256) void large_finish_kernel(const LargeArgs A)
             for (int i = tid; i < Ng; i += BS) s_I[i] = (double)(i + 1);
         const uint32_t* const gP = (const uint32_t*)(R.base + R.L.P);
         const uint64_t NN = (uint64_t)Ng * Ng;
-        if (Ng <= 0) {
+        if (Ng <= 0) {                               // no level past the guard: every matrix is blank (glcm.cpp:260-295), whose soft_nan survives save_value()
             for (int c = tid; c < ncol_g; c += BS) o[c] = A.soft_nan;
             return;
         }

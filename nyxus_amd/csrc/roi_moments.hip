@@ -79,8 +79,10 @@ __global__ __launch_bounds__(64 * kContourWaves) void roi_contour_kernel(const M
 
     for (uint32_t i = lane; i < np; i += 64) img[i] = 0;
     wav_sync<GS>();
-    for_each_cloud_pixel<64>(A.inten + off, A.x + off, A.y + off, n, lane, [&](uint32_t, uint32_t, uint32_t px, uint32_t py) {   // padded image, contour.cpp:661-666
-        if (px < (uint32_t)w && py < (uint32_t)h) img[mad24(py + 1, (uint32_t)W2, px + 1)] = kPix;
+    // padded image, contour.cpp:661-666: the reference stores `inten + 1` in a 32-bit cell, so a pixel of intensity 2^32 - 1 wraps to 0 and
+    // is background to the border scan (its moments still count it: they read the cloud)
+    for_each_cloud_pixel<64>(A.inten + off, A.x + off, A.y + off, n, lane, [&](uint32_t, uint32_t v, uint32_t px, uint32_t py) {
+        if (px < (uint32_t)w && py < (uint32_t)h && v != 0xFFFFFFFFu) img[mad24(py + 1, (uint32_t)W2, px + 1)] = kPix;
     });
     wav_sync<GS>();
 

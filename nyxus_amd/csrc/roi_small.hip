@@ -534,7 +534,7 @@ __device__ __forceinline__ void small_one(const RoiArgs& A, const uint64_t slot,
         // the code of the workgroup kernel.  One angle after the other over one 4 KiB matrix.
         double* const og = out_row + A.col_glcm;
         if (degenerate) {
-            for (int c = lane; c < kGlcmAngled * na + kGlcmAve; c += 64) og[c] = A.soft_nan;
+            for (int c = lane; c < kGlcmAngled * na + kGlcmAve; c += 64) og[c] = 0.0;   // not soft_nan: save_value() undoes the guard's assignments (glcm.cpp:210-215)
             return;
         }
         const uint32_t pitch = w + 2;
@@ -651,7 +651,7 @@ __device__ __forceinline__ void small_one(const RoiArgs& A, const uint64_t slot,
         double* const og = out_row + A.col_glcm;
         if (lane == 0 && A.glcm_ng) A.glcm_ng[roi] = degenerate ? 0u : (uint32_t)Ng;
         if (degenerate) {
-            for (int c = lane; c < kGlcmAngled * na + kGlcmAve; c += 64) og[c] = A.soft_nan;
+            for (int c = lane; c < kGlcmAngled * na + kGlcmAve; c += 64) og[c] = 0.0;   // not soft_nan: save_value() undoes the guard's assignments (glcm.cpp:210-215)
             return;
         }
         // co-occurrence counts (glcm.cpp:343-485): centre b at (row, col), neighbour a at (row + dy, col + dx); pairs with a level-0

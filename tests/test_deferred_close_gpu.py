@@ -73,6 +73,8 @@ def same(a, b):
 @pytest.mark.parametrize("slide", [False, True])
 @pytest.mark.parametrize("soft_nan", [0.0, -7.5])
 def test_edge_rois_match_the_oracle(hip_ctx, mask, slide, soft_nan):
+    """(At soft_nan = -7.5 the GLCM row of a blank or constant ROI is 0.0, not soft_nan: the oracle follows the reference's table there,
+    glcm.cpp:27-95 undone by save_value at :210-215 -- tests/test_soft_nan_cpu.py.)"""
     s = _abi.default_settings(8)
     s.soft_nan = soft_nan
     rois = edge_rois()
