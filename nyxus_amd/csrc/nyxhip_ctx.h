@@ -2,6 +2,7 @@
 // device and pinned memory, error reporting, and the functions the units call in each other.
 //   nyxhip_columns.hip   column catalogue, settings checks, defaults
 //   nyxhip_dispatch.hip  layouts, argument blocks, size classes: a device-resident batch -> kernel launches
+//   nyxhip_contour.hip   the families without size classes: pixel-cloud and contour launchers, their deferred lists (deferred_list.h)
 //   nyxhip_tiles.hip     the fused tile path and its host staging
 //   nyxhip_api.hip       context life cycle, the batch entry points, timing, launch report
 //   nyxhip_neighbors.hip the neighbor entries: column names, the launches over a device-resident batch, nyxhip_neighbors_batch
@@ -65,6 +66,9 @@ struct DevBuf {
         return hipSuccess;
     }
 };
+
+// The two buffers of a deferred list (deferred_list.h): 64 header words + the index list | the listed ROIs' per-workgroup workspace.
+struct DeferredBufs { DevBuf list, ws; };
 
 // One page-locked host block and the event of the last copy out of it: complete (both) or empty (neither).
 struct PinnedSlot {
@@ -148,18 +152,11 @@ struct nyxhip_ctx {
     // contour planes beyond LDS: index list (launch_contour_families); per-workgroup global scratch of every workspace launch
     DevBuf d_spill_list;
     DevBuf d_spill;
-    // outline kernel (roi_outline.hip): list of the ROIs whose bit planes exceed LDS, and their global bit planes
-    DevBuf d_outline_list;
-    DevBuf d_outline_bits;
-    // caliper kernel (roi_caliper.hip): list of the ROIs whose boxes are wider than the LDS column table, and their global tables
-    DevBuf d_caliper_list;
-    DevBuf d_caliper_ws;
-    // chords kernel (roi_chords.hip): list of the ROIs served on global planes (plane beyond LDS, or zero-intensity pixels), and the planes
-    DevBuf d_chords_list;
-    DevBuf d_chords_ws;
-    // erosion kernel (roi_erosion.hip): list of the ROIs whose two bit planes exceed the LDS planes, and their global planes
-    DevBuf d_erosion_list;
-    DevBuf d_erosion_ws;
+    // deferred lists of nyxhip_contour.hip, one per owner: the ROIs beyond the kernel's LDS carve, and their global workspaces
+    DeferredBufs d_outline;            // roi_outline.hip: bit planes beyond LDS
+    DeferredBufs d_caliper;            // roi_caliper.hip: boxes wider than the LDS column table
+    DeferredBufs d_chords;             // roi_chords.hip: plane beyond LDS, or zero-intensity pixels
+    DeferredBufs d_erosion;            // roi_erosion.hip: two bit planes beyond the LDS planes
     // neighbor entries (roi_neighbors.hip): geometry table + candidate counts and offsets | candidate lists, minima, flags
     DevBuf d_nb_geo;
     DevBuf d_nb_cand;
@@ -257,6 +254,8 @@ int fail(nyxhip_ctx* ctx, int code, const std::string& msg);   // records msg (c
 // nyxhip_columns.hip
 bool settings_ok(const nyxhip_settings* s, uint32_t mask, std::string& why);
 // nyxhip_dispatch.hip
+int use_lane(nyxhip_ctx* ctx, int lane, hipStream_t* st);   // the stream of workspace lane `lane`, forked from the call's stream on first use
+size_t large_budget(size_t dflt);                           // NYXHIP_LARGE_BUDGET_MB when set, else dflt
 uint32_t pow2ceil(uint32_t v);
 int make_layout(uint32_t mask, const nyxhip_settings* s, int n_cols, uint32_t max_px, uint32_t max_area, uint32_t max_range, LdsLayout& L,
                 std::string& why, size_t cap = 0, uint32_t vmax = 0, bool wide_only = false);
@@ -267,6 +266,7 @@ void clear_runs(nyxhip_ctx* ctx);
 int launch_device(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t mask, const nyxhip_settings* s, double* d_out, size_t ld, uint32_t max_px,
                   uint32_t max_area, uint32_t max_range, uint32_t max_side, bool hinted = true);
 int validate(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t mask, const nyxhip_settings* s, double* out, size_t ld);
+// nyxhip_contour.hip
 int launch_contour_families(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t mask, const nyxhip_settings* s, double* d_out, size_t ld, uint32_t max_px,
                             uint32_t max_area, uint32_t max_side, bool allow_lane, MomArgs* contour_out = nullptr);
 // nyxhip_neighbors.hip: the neighbor columns of a device-resident batch -> d_out [n_roi x ld] (enqueued on the context's stream).  The rows of

@@ -428,436 +428,6 @@ int build_args(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t mask, const nyxh
     return NYXHIP_OK;
 }
 
-// ROIs whose padded flag plane exceeds the LDS cap of the contour kernel -> index list
-__global__ void classify_plane_kernel(uint64_t n_roi, const uint32_t* bw, const uint32_t* bh, uint32_t cap, uint32_t* list, uint32_t* n_out)
-{
-    uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
-    if (i >= n_roi) return;
-    if ((uint64_t)(bw[i] + 2) * (bh[i] + 2) > cap)
-        list[atomicAdd(n_out, 1u)] = (uint32_t)i;
-}
-
-// A workspace lane: a high-priority stream forked from the call's stream (nyxhip_ctx::lane_fork, recorded at the start of launch_device_all),
-// joined into it at the end of the call (LaneJoin).  The lanes carry chains of short, latency-bound kernels -- a few hundred workgroups each --
-// beside the main stream's chip-filling grids: at the device's highest priority their workgroups are placed first and the chain is not starved.
-int use_lane(nyxhip_ctx* ctx, int lane, hipStream_t* st)
-{
-    if (!ctx->lane_stream[lane]) {
-        static const bool no_prio = [] { const char* e = getenv("NYXHIP_NO_LANE_PRIORITY"); return e && *e && *e != '0'; }();   // A/B knob
-        int lo = 0, hi = 0;
-        if (no_prio || hipDeviceGetStreamPriorityRange(&lo, &hi) != hipSuccess) lo = hi = 0;
-        HIP_TRY(ctx, hipStreamCreateWithPriority(&ctx->lane_stream[lane], hipStreamNonBlocking, hi));
-        HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->lane_done[lane], hipEventDisableTiming));
-    }
-    if (!ctx->lane_used[lane]) {
-        HIP_TRY(ctx, hipStreamWaitEvent(ctx->lane_stream[lane], ctx->lane_fork, 0));   // the batch and the class lists are complete on the main stream
-        ctx->lane_used[lane] = true;
-    }
-    *st = ctx->lane_stream[lane];
-    return NYXHIP_OK;
-}
-
-// The caliper classes (roi_caliper.hip) on `st`: one workgroup per ROI over the pixel clouds, no contour.  Columns: between
-// FRACT_DIM_PERIMETER and EULER_NUMBER.  The origins are those the entry point left in the context (NULL: (0, 0)).  ROIs whose
-// boxes are wider than the LDS column table go through a classifier and a list launch over global tables, like the outline
-// kernel's deferred ROIs.
-int launch_caliper(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t mask, const nyxhip_settings* s, double* d_out, size_t ld, uint32_t max_side,
-                   hipStream_t st)
-{
-    CalArgs ca;
-    memset(&ca, 0, sizeof(ca));
-    ca.n_roi = b->n_roi;
-    ca.px_offset = b->px_offset; ca.x = b->x; ca.y = b->y; ca.bbox_w = b->bbox_w;
-    ca.origin_x = ctx->origin_x_next; ca.origin_y = ctx->origin_y_next;
-    ca.out = d_out; ca.ld = ld; ca.status = ctx->d_status.as<int>();
-    ca.fams = mask & kCaliper;
-    ca.col_feret = nyxhip_n_columns(mask & (NYXHIP_FAM_INTENSITY | kEllipseErosion | NYXHIP_FAM_FRACTAL), s);
-    ca.col_martin = ca.col_feret + ((mask & NYXHIP_FAM_FERET) ? kFeretCols : 0);
-    ca.col_nassenstein = ca.col_martin + ((mask & NYXHIP_FAM_MARTIN) ? kMartinCols : 0);
-    ca.soft_nan = s->soft_nan;
-    // the reference's expression (rotation.cpp:56-58) on the host's libm, as the reference evaluates it
-    for (int k = 0; k < kCaliperAngles; k++) {
-        const float theta = (float)(10 * k) * float(3.14159265358979323846) / 180.f;
-        ca.sn[k] = std::sin((double)theta); ca.cs[k] = std::cos((double)theta);
-    }
-    const uint32_t side = std::max<uint32_t>(max_side, 1u);
-    ca.cols_cap = std::min<uint32_t>(kCaliperColsLds, (side + 7u) & ~7u);
-    ca.defer_wide = side > kCaliperColsLds ? 1u : 0u;
-    if (launch_roi_caliper(ca, st, (uint32_t)b->n_roi) != 0)
-        return fail(ctx, NYXHIP_ERR_HIP, "caliper kernel: launch failed");
-    if (!ca.defer_wide) return NYXHIP_OK;
-    const size_t list_bytes = 4ull * b->n_roi + 512;
-    HIP_TRY(ctx, ctx->d_caliper_list.reserve(list_bytes, st));
-    uint32_t* d_cnt = ctx->d_caliper_list.as<uint32_t>();
-    uint32_t* d_list = d_cnt + 64;
-    HIP_TRY(ctx, hipMemsetAsync(d_cnt, 0, 4, st));
-    if (launch_caliper_classify(b->n_roi, b->bbox_w, ca.cols_cap, d_list, d_cnt, st) != 0)
-        return fail(ctx, NYXHIP_ERR_HIP, "caliper classifier: launch failed");
-    uint32_t n_wide = 0;
-    HIP_TRY(ctx, hipMemcpyAsync(&n_wide, d_cnt, 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipStreamSynchronize(st));
-    if (!n_wide) return NYXHIP_OK;
-    const uint32_t ws_cols = (std::min<uint32_t>(side, 65535u) + 31u) & ~31u;
-    const uint64_t stride = (uint64_t)kCaliperBytesPerCol * ws_cols;
-    const uint32_t chunk = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(n_wide, ((uint64_t)1 << 30) / stride));
-    HIP_TRY(ctx, ctx->d_caliper_ws.reserve((size_t)(stride * chunk), st));
-    CalArgs cw = ca;
-    cw.defer_wide = 0; cw.ws = ctx->d_caliper_ws.as<unsigned char>(); cw.ws_cols = ws_cols;
-    for (uint32_t o = 0; o < n_wide; o += chunk) {
-        cw.roi_index = d_list + o;
-        if (launch_roi_caliper(cw, st, std::min(chunk, n_wide - o)) != 0)
-            return fail(ctx, NYXHIP_ERR_HIP, "caliper kernel: launch failed");
-    }
-    return NYXHIP_OK;
-}
-
-// ChordsFeature (roi_chords.hip) on `st`: one workgroup per ROI over the pixel clouds, no contour.  Columns: between the Nassenstein
-// columns and EULER_NUMBER.  The origins are those the entry point left in the context (NULL: (0, 0)).  ROIs whose rotated bit plane
-// may exceed the LDS plane, and ROIs with zero-intensity pixels (min_inten == 0), go through a classifier and a list launch over
-// global planes.  Which ROIs those are is known on the device only: the classifier's three counters are read back on every call
-// (one stream synchronisation, as the caliper and outline kernels have for their wide boxes).
-int launch_chords(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t mask, const nyxhip_settings* s, double* d_out, size_t ld, uint32_t max_side,
-                  hipStream_t st)
-{
-    ChordArgs ca;
-    memset(&ca, 0, sizeof(ca));
-    ca.n_roi = b->n_roi;
-    ca.px_offset = b->px_offset; ca.x = b->x; ca.y = b->y; ca.inten = b->inten; ca.bbox_w = b->bbox_w; ca.bbox_h = b->bbox_h;
-    ca.min_inten = b->min_inten;
-    ca.origin_x = ctx->origin_x_next; ca.origin_y = ctx->origin_y_next;
-    ca.out = d_out; ca.ld = ld; ca.status = ctx->d_status.as<int>();
-    ca.col0 = nyxhip_n_columns(mask & (NYXHIP_FAM_INTENSITY | kEllipseErosion | NYXHIP_FAM_FRACTAL | kCaliper), s);
-    // the reference's loop (chords.cpp:22-23) and its expressions (rotation.cpp:70-82: the angle is passed as float) on the host's libm
-    {
-        const double step = M_PI / double(kChordsAngles);
-        int k = 0;
-        for (double ang = 0; ang < M_PI && k < kChordsAngles; ang += step, k++) {
-            const float theta = (float)ang;
-            ca.ang[k] = ang; ca.sn[k] = std::sin((double)theta); ca.cs[k] = std::cos((double)theta);
-        }
-        if (k != kChordsAngles)
-            return fail(ctx, NYXHIP_ERR_HIP, "chords: the angle loop did not give 20 angles");
-    }
-    const uint32_t side = std::min<uint32_t>(std::max<uint32_t>(max_side, 1u), 65535u);
-    ca.lds_words = (uint32_t)std::min<uint64_t>(kChordsLdsWords, chords_plane_words(side, side));
-    const size_t list_bytes = 4ull * b->n_roi + 512;
-    HIP_TRY(ctx, ctx->d_chords_list.reserve(list_bytes, st));
-    uint32_t* d_hdr = ctx->d_chords_list.as<uint32_t>();
-    uint32_t* d_list = d_hdr + 64;
-    HIP_TRY(ctx, hipMemsetAsync(d_hdr, 0, 12, st));
-    if (launch_chords_classify(b->n_roi, b->bbox_w, b->bbox_h, b->min_inten, ca.lds_words, d_list, d_hdr, st) != 0)
-        return fail(ctx, NYXHIP_ERR_HIP, "chords classifier: launch failed");
-    if (launch_roi_chords(ca, st, (uint32_t)b->n_roi) != 0)
-        return fail(ctx, NYXHIP_ERR_HIP, "chords kernel: launch failed");
-    uint32_t hdr[3] = {0, 0, 0};
-    HIP_TRY(ctx, hipMemcpyAsync(hdr, d_hdr, 12, hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipStreamSynchronize(st));
-    const uint32_t n_list = hdr[0];
-    if (!n_list) return NYXHIP_OK;
-    ChordArgs cw = ca;
-    cw.ws_words = ((uint64_t)hdr[1] + 63) & ~63ull;
-    cw.ws_cells = ((uint64_t)hdr[2] * hdr[2] + 63) & ~63ull;
-    const uint64_t stride = 4ull * (cw.ws_words + cw.ws_cells);
-    const uint32_t chunk = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(n_list, ((uint64_t)1 << 30) / stride));
-    HIP_TRY(ctx, ctx->d_chords_ws.reserve((size_t)(stride * chunk), st));
-    cw.ws = ctx->d_chords_ws.as<uint32_t>();
-    for (uint32_t o = 0; o < n_list; o += chunk) {
-        cw.roi_index = d_list + o;
-        if (launch_roi_chords(cw, st, std::min(chunk, n_list - o)) != 0)
-            return fail(ctx, NYXHIP_ERR_HIP, "chords kernel: launch failed");
-    }
-    return NYXHIP_OK;
-}
-
-// EllipseFittingFeature and ErosionPixelsFeature (roi_erosion.hip) on `st`, over the pixel clouds: no contour, no origin.  Columns:
-// directly behind the intensity block.  The ellipse sums take a wave per ROI, and a workgroup per ROI of more than kEllipseWavePx
-// pixels when the batch can hold one.  The erosion takes a workgroup per ROI with its two bit planes in LDS; when the batch's extrema
-// allow a box beyond kErosionLdsWords, those ROIs go through a classifier and a list launch over global planes (the pattern of
-// launch_caliper: one read-back, and only then).
-int launch_ellipse_erosion(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t mask, const nyxhip_settings* s, double* d_out, size_t ld, uint32_t max_px,
-                           uint32_t max_area, uint32_t max_side, hipStream_t st)
-{
-    EroArgs ea;
-    memset(&ea, 0, sizeof(ea));
-    ea.n_roi = b->n_roi;
-    ea.px_offset = b->px_offset; ea.x = b->x; ea.y = b->y; ea.bbox_w = b->bbox_w; ea.bbox_h = b->bbox_h;
-    ea.min_inten = b->min_inten; ea.max_inten = b->max_inten;
-    ea.out = d_out; ea.ld = ld; ea.status = ctx->d_status.as<int>();
-    ea.col_ellipse = nyxhip_n_columns(mask & NYXHIP_FAM_INTENSITY, s);
-    ea.col_erosion = ea.col_ellipse + ((mask & NYXHIP_FAM_ELLIPSE) ? kEllipseCols : 0);
-    if (mask & NYXHIP_FAM_ELLIPSE) {
-        const uint32_t most = max_px ? max_px : max_area;                      // (a batch without a stated pixel maximum: no ROI has more than its box)
-        if (launch_roi_ellipse(ea, st, most > kEllipseWavePx) != 0)
-            return fail(ctx, NYXHIP_ERR_HIP, "ellipse kernel: launch failed");
-    }
-    if (!(mask & NYXHIP_FAM_EROSION)) return NYXHIP_OK;
-    // bound of two planes over boxes of at most max_area cells and max_side a side: (w / 32 + 1) * h <= area / 32 + side
-    const uint64_t bound = std::max<uint64_t>(2ull * ((uint64_t)max_area / 32u + max_side), 2u);
-    ea.lds_words = (uint32_t)std::min<uint64_t>(kErosionLdsWords, bound);
-    ea.defer_large = bound > kErosionLdsWords ? 1u : 0u;
-    if (launch_roi_erosion(ea, st, (uint32_t)b->n_roi) != 0)
-        return fail(ctx, NYXHIP_ERR_HIP, "erosion kernel: launch failed");
-    if (!ea.defer_large) return NYXHIP_OK;
-    const size_t list_bytes = 4ull * b->n_roi + 512;
-    HIP_TRY(ctx, ctx->d_erosion_list.reserve(list_bytes, st));
-    uint32_t* d_hdr = ctx->d_erosion_list.as<uint32_t>();
-    uint32_t* d_list = d_hdr + 64;
-    HIP_TRY(ctx, hipMemsetAsync(d_hdr, 0, 8, st));
-    if (launch_erosion_classify(b->n_roi, b->bbox_w, b->bbox_h, ea.lds_words, d_list, d_hdr, st) != 0)
-        return fail(ctx, NYXHIP_ERR_HIP, "erosion classifier: launch failed");
-    uint32_t hdr[2] = {0, 0};
-    HIP_TRY(ctx, hipMemcpyAsync(hdr, d_hdr, 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipStreamSynchronize(st));
-    const uint32_t n_list = hdr[0];
-    if (!n_list) return NYXHIP_OK;
-    EroArgs ew = ea;
-    ew.defer_large = 0;
-    ew.ws_stride = (2ull * hdr[1] + 63) & ~63ull;
-    const uint32_t chunk = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(n_list, ((uint64_t)1 << 30) / (4 * ew.ws_stride)));
-    HIP_TRY(ctx, ctx->d_erosion_ws.reserve((size_t)(4 * ew.ws_stride * chunk), st));
-    ew.ws = ctx->d_erosion_ws.as<uint32_t>();
-    for (uint32_t o = 0; o < n_list; o += chunk) {
-        ew.roi_index = d_list + o;
-        if (launch_roi_erosion(ew, st, std::min(chunk, n_list - o)) != 0)
-            return fail(ctx, NYXHIP_ERR_HIP, "erosion kernel: launch failed");
-    }
-    return NYXHIP_OK;
-}
-
-// Contour (roi_moments.hip) + the families that read it: the 2-D geometric moments (roi_moments.hip) and the radial intensity
-// distribution (roi_radial.hip).  The contour of every ROI goes to a context-owned workspace at the ROI's CSR offset (a contour
-// never has more points than the ROI has pixels) ONCE per call; the moments kernel and / or the radial kernel read it back.
-// (The workspace keeps its per-pixel double plane for a radial-only call too: the contour kernel's walk stack lives there.)
-// The outline kernel (roi_outline.hip) is the third reader, the circle kernel (roi_circle.hip) the fourth; a mask that holds none of the contour families (EULER_NUMBER alone) skips
-// the contour chain and launches it by itself.  allow_lane = false: everything stays on the call's stream (the caller has joined the
-// lanes: the feature kernels of a GLCM launch zero the outline columns, so the outline kernel must follow all of them).
-// contour_out != NULL: the contour chain runs whatever the mask holds (0: the chain alone, no reader, d_out unused) and the argument
-// block that names its workspace (ws_contour / n_contour) is handed back -- the neighbor entries read the contours themselves.
-int contour_families(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t mask, const nyxhip_settings* s, double* d_out, size_t ld,
-                   uint32_t max_px, uint32_t max_area, uint32_t max_side, bool allow_lane, MomArgs* contour_out = nullptr)
-{
-    hipStream_t st = ctx->stream();
-    const bool do_out = (mask & kOutline) != 0, need_contour = (mask & kContourFams) != 0 || contour_out != nullptr;
-    OutArgs oa;
-    memset(&oa, 0, sizeof(oa));
-    bool out_deferred = false;                             // some ROI's bit planes may exceed LDS: a list launch follows the readers
-    if (do_out) {
-        oa.fams = mask & kOutline;
-        oa.has_contour = need_contour ? 1u : 0u;
-        oa.col_fractal = nyxhip_n_columns(mask & (NYXHIP_FAM_INTENSITY | kEllipseErosion), s);   // (the ellipse and erosion columns precede it)
-        oa.col_euler = oa.col_fractal + ((mask & NYXHIP_FAM_FRACTAL) ? kFractalCols : 0) + nyxhip_n_columns(mask & (kCaliper | NYXHIP_FAM_CHORDS), s);   // (enum order)
-        oa.col_radius = oa.col_euler + ((mask & NYXHIP_FAM_EULER) ? kEulerCols : 0) + nyxhip_n_columns(mask & kCircleGeodetic, s);   // (the circle and geodetic columns precede it)
-        if (mask & (NYXHIP_FAM_FRACTAL | NYXHIP_FAM_EULER)) {
-            // bound of outline_bit_words over boxes of at most max_area cells and max_side a side: rows of w / 32 + 1 words, the pyramid
-            // at most as much again plus a word and a row per level
-            const uint64_t bound = 2ull * ((uint64_t)max_area / 32u + max_side) + 2ull * max_side + 64u;
-            oa.bits_cap = (uint32_t)std::min<uint64_t>(kOutlineBitsLds, bound);
-            out_deferred = bound > kOutlineBitsLds;
-            oa.defer_bits = out_deferred ? 1u : 0u;
-        }
-    }
-    // the ROIs the outline launches deferred, from global bit planes: on `s_`, behind everything that wrote their contours
-    auto launch_outline_deferred = [&](hipStream_t s_) -> int {
-        if (!out_deferred) return NYXHIP_OK;
-        const size_t list_bytes = 4ull * b->n_roi + 512;
-        HIP_TRY(ctx, ctx->d_outline_list.reserve(list_bytes, s_));
-        uint32_t* d_cnt = ctx->d_outline_list.as<uint32_t>();
-        uint32_t* d_list = d_cnt + 64;
-        HIP_TRY(ctx, hipMemsetAsync(d_cnt, 0, 4, s_));
-        const uint32_t pyramid = (mask & NYXHIP_FAM_FRACTAL) ? 1u : 0u;
-        if (launch_outline_classify(b->n_roi, b->bbox_w, b->bbox_h, pyramid, oa.bits_cap, d_list, d_cnt, s_) != 0)
-            return fail(ctx, NYXHIP_ERR_HIP, "outline classifier: launch failed");
-        uint32_t n_big = 0;
-        HIP_TRY(ctx, hipMemcpyAsync(&n_big, d_cnt, 4, hipMemcpyDeviceToHost, s_));
-        HIP_TRY(ctx, hipStreamSynchronize(s_));
-        if (!n_big) return NYXHIP_OK;
-        const uint32_t sd = std::min<uint32_t>(max_side, 65535u);
-        const uint64_t stride = (std::min<uint64_t>(2ull * ((uint64_t)max_area / 32u + max_side) + 2ull * max_side + 64u, outline_bit_words(sd, sd, pyramid != 0)) + 63) & ~63ull;
-        const uint32_t chunk = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(n_big, ((uint64_t)1 << 30) / (4 * stride)));
-        HIP_TRY(ctx, ctx->d_outline_bits.reserve((size_t)(4 * stride * chunk), s_));
-        OutArgs ob = oa;
-        ob.defer_bits = 0; ob.bits_ws = ctx->d_outline_bits.as<uint32_t>(); ob.bits_stride = stride;
-        ob.m.sp.defer_large = 0;
-        for (uint32_t o = 0; o < n_big; o += chunk) {
-            ob.m.sp.roi_index = d_list + o;
-            if (launch_roi_outline(ob, s_, std::min(chunk, n_big - o)) != 0)
-                return fail(ctx, NYXHIP_ERR_HIP, "outline kernel: launch failed");
-        }
-        return NYXHIP_OK;
-    };
-    // the circle / geodetic classes (roi_circle.hip): the fourth reader of the contour, columns directly behind EULER_NUMBER
-    const bool do_circ = (mask & kCircleGeodetic) != 0;
-    CircArgs cg;
-    memset(&cg, 0, sizeof(cg));
-    if (do_circ) {
-        cg.fams = mask & kCircleGeodetic;
-        cg.col_circles = nyxhip_n_columns(mask & (NYXHIP_FAM_INTENSITY | kEllipseErosion | NYXHIP_FAM_FRACTAL | kCaliper | NYXHIP_FAM_CHORDS | NYXHIP_FAM_EULER), s);
-        cg.col_geodetic = cg.col_circles + ((mask & NYXHIP_FAM_CIRCLES) ? kCirclesCols : 0);
-        cg.origin_x = ctx->origin_x_next; cg.origin_y = ctx->origin_y_next;
-    }
-    if (mask & kCaliper)
-        if (int crc = launch_caliper(ctx, b, mask, s, d_out, ld, max_side, st)) return crc;
-    if (mask & NYXHIP_FAM_CHORDS)
-        if (int crc = launch_chords(ctx, b, mask, s, d_out, ld, max_side, st)) return crc;
-    if (mask & kEllipseErosion)
-        if (int crc = launch_ellipse_erosion(ctx, b, mask, s, d_out, ld, max_px, max_area, max_side, st)) return crc;
-    if (!need_contour && !do_out)
-        return NYXHIP_OK;                                  // the caliper classes / the chords / the ellipse and erosion classes alone
-    if (!need_contour) {
-        // EULER_NUMBER alone: no contour, no staged pixels -- the bit plane only
-        MomArgs& m = oa.m;
-        m.n_roi = b->n_roi;
-        m.px_offset = b->px_offset; m.x = b->x; m.y = b->y; m.inten = b->inten; m.bbox_w = b->bbox_w; m.bbox_h = b->bbox_h;
-        m.out = d_out; m.ld = ld; m.status = ctx->d_status.as<int>();
-        if (launch_roi_outline(oa, st, (uint32_t)b->n_roi) != 0)
-            return fail(ctx, NYXHIP_ERR_HIP, "outline kernel: launch failed");
-        return launch_outline_deferred(st);
-    }
-    // A batch with boxes beyond the LDS plane sends those to a wave per ROI over a global workspace (a few hundred waves, ~10 ms of
-    // latency for the heavy-tailed batch): with other families in the call the whole moments chain goes to a lane of its own and
-    // runs beside them (enqueued last, dependent only on the batch).  Its scratch is the lane's, not the main stream's.
-    static const bool no_mom_lane = [] { const char* e = getenv("NYXHIP_NO_MOM_LANE"); return e && *e && *e != '0'; }();   // A/B knob
-    const bool big_boxes = (uint64_t)kContourWaves * (((uint64_t)max_area + 4ull * max_side + 4 + 15) & ~15ull) > (uint64_t)roi_features_max_lds();
-    const bool on_lane = allow_lane && !no_mom_lane && big_boxes && (mask & ~kTailFams) && ctx->lane_fork;
-    if (on_lane)
-        if (int lrc = use_lane(ctx, nyxhip_ctx::kMomLane, &st)) return lrc;
-    DevBuf& spill = on_lane ? ctx->lane_buf[nyxhip_ctx::kMomLane] : ctx->d_spill;
-    uint64_t total_px = 0;
-    HIP_TRY(ctx, hipMemcpyAsync(&total_px, b->px_offset + b->n_roi, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipStreamSynchronize(st));
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    const size_t o_k = 0, o_n = al(4 * (size_t)total_px + 256), o_l = al(o_n + 4 * (size_t)b->n_roi + 256), need = al(o_l + 8 * (size_t)total_px + 256);
-    HIP_TRY(ctx, ctx->d_mom.reserve(need, st, need + need / 8));
-    char* base = ctx->d_mom.as<char>();
-    MomArgs m;
-    memset(&m, 0, sizeof(m));
-    m.n_roi = b->n_roi;
-    m.px_offset = b->px_offset; m.x = b->x; m.y = b->y; m.inten = b->inten; m.bbox_w = b->bbox_w; m.bbox_h = b->bbox_h;
-    m.out = d_out; m.ld = ld; m.status = ctx->d_status.as<int>();
-    m.mask = mask & kMoments;
-    m.col_smoms = nyxhip_n_columns(mask & ~kMoments, s);     // (every other family, the radial distribution included, precedes the moments)
-    m.col_imoms = m.col_smoms + ((mask & NYXHIP_FAM_SMOMS) ? kMomCols : 0);
-    m.ws_contour = (uint32_t*)(base + o_k); m.n_contour = (uint32_t*)(base + o_n); m.ws_L = (double*)(base + o_l);
-    if (!ctx->d_logtab) {                                 // log(sqrt(d) + 0.001), d < 32768: boxes up to 128 x 128 never evaluate a logarithm
-        constexpr uint32_t kLogTab = 32768;
-        HIP_TRY(ctx, ctx->d_logtab.reserve(8ull * kLogTab, nullptr));
-        if (launch_moments_logtab(ctx->d_logtab.as<double>(), kLogTab, st) != 0) return fail(ctx, NYXHIP_ERR_HIP, "moments log table: launch failed");
-        ctx->logtab_n = kLogTab;
-    }
-    m.log_tab = ctx->d_logtab.as<double>(); m.log_tab_n = ctx->logtab_n;
-    // LDS of the moments kernel from the batch extrema: every pixel of the largest ROI (up to kMomPxLds; larger ROIs sweep HBM),
-    // a contour of up to the bounding box's perimeter (what a convex ROI can have; longer ones are read from HBM), its step table
-    m.px_cap = std::min<uint32_t>((uint32_t)kMomPxLds, (std::max<uint32_t>(max_px ? max_px : max_area, 1u) + 7u) & ~7u);
-    m.k_cap = std::min<uint32_t>((uint32_t)kMomContourLds, std::max<uint32_t>(256u, (4u * std::min<uint32_t>(max_side, 65536u) + 63u) & ~63u));
-    m.step_cap = std::min<uint32_t>((uint32_t)kMomStepTab, m.k_cap);
-    const bool do_mom = (mask & kMoments) != 0, do_rad = (mask & NYXHIP_FAM_RADIAL) != 0;
-    RadArgs ra;
-    memset(&ra, 0, sizeof(ra));
-    if (do_rad) {
-        // columns: FRAC_AT_D | GABOR | MEAN_FRAC | RADIAL_CV (enum order)
-        const uint32_t before = NYXHIP_FAM_INTENSITY | kBehindIntensity | NYXHIP_FAM_GLCM | kTexture | kDependence;
-        ra.col_frac = nyxhip_n_columns(mask & before, s);
-        ra.col_mean = ra.col_frac + kRadialBins + ((mask & NYXHIP_FAM_GABOR) ? s->gabor_n_filters : 0);
-        ra.col_cv = ra.col_mean + kRadialBins;
-        // the wedge of the eight directions that lie ON an octant boundary: the reference expression (radial_distribution.cpp:92-96)
-        // on the host's libm, as the reference evaluates it; every other direction is an exact integer test in the kernel
-        static const int kDirX[8] = {1, 1, 0, -1, -1, -1, 0, 1}, kDirY[8] = {0, 1, 1, 1, 0, -1, -1, -1};
-        const double two_pi = 2.0 * 3.14159265358979323846;
-        for (int k = 0; k < 8; k++) {
-            double ang = std::atan2((double)kDirY[k], (double)kDirX[k]);
-            if (ang < 0) ang = two_pi + ang;
-            const double angW = two_pi / double(kRadialBins);
-            const int w_bin = std::min(std::max(int(ang / angW), 0), kRadialBins - 1);
-            ra.wedge_tab |= (uint32_t)w_bin << (4 * k);
-        }
-    }
-    // the readers of a contour launch, on its stream: the moments of `mm` and / or the radial distribution over the same ROIs
-    auto launch_readers = [&](const MomArgs& mm, hipStream_t s_, uint32_t g) -> int {
-        int r = do_mom ? launch_roi_moments(mm, s_, g) : 0;
-        if (r == 0 && do_rad) {
-            ra.m = mm;
-            r = launch_roi_radial(ra, s_, g);
-        }
-        if (r == 0 && do_out) {
-            oa.m = mm;
-            r = launch_roi_outline(oa, s_, g);
-        }
-        if (r == 0 && do_circ) {
-            cg.m = mm;
-            r = launch_roi_circle(cg, s_, g);
-        }
-        return r;
-    };
-    const uint64_t full_plane = (uint64_t)max_area + 4ull * max_side + 4;      // (w + 2)(h + 2) <= area + 2(w + h) + 4
-    const uint32_t grid = (uint32_t)b->n_roi;
-    const uint32_t lds_cap = (uint32_t)roi_features_max_lds();
-    int rc;
-    hipStream_t st_join = nullptr;                         // the big boxes' stream when it is not `st`
-    if ((uint64_t)kContourWaves * ((full_plane + 15) & ~15ull) <= lds_cap) {   // kContourWaves planes per workgroup
-        m.plane_cap = (uint32_t)full_plane;
-        rc = launch_roi_contour(m, st, grid);
-        if (rc == 0) rc = launch_readers(m, st, grid);
-    } else {
-        // the bulk of the batch from LDS (16 KiB planes keep ten waves per CU), the oversized ROIs from a global workspace: a wave per ROI,
-        // a few hundred waves and ~10 ms of latency for the heavy-tailed batch.  Two independent chains -- big boxes: list, contour over the
-        // workspace, moments of the list | bulk: contour from LDS (skipping the big boxes), moments of everybody else -- on two lanes when
-        // the call has lanes (other families to run beside), one after the other on the call's stream otherwise.
-        m.plane_cap = 16 * 1024;
-        hipStream_t st_big = st;
-        if (on_lane)
-            if (int lrc = use_lane(ctx, nyxhip_ctx::kMomLaneBig, &st_big)) return lrc;
-        if (st_big != st) st_join = st_big;
-        const size_t list_bytes = 4ull * b->n_roi + 256;
-        HIP_TRY(ctx, ctx->d_spill_list.reserve(list_bytes, st_big));
-        uint32_t* d_cnt = ctx->d_spill_list.as<uint32_t>();
-        uint32_t* d_list = d_cnt + 64;
-        HIP_TRY(ctx, hipMemsetAsync(d_cnt, 0, 4, st_big));
-        hipLaunchKernelGGL(classify_plane_kernel, dim3((unsigned)((b->n_roi + 255) / 256)), dim3(256), 0, st_big, b->n_roi, b->bbox_w, b->bbox_h,
-                           m.plane_cap, d_list, d_cnt);
-        uint32_t n_large = 0;
-        HIP_TRY(ctx, hipMemcpyAsync(&n_large, d_cnt, 4, hipMemcpyDeviceToHost, st_big));
-        HIP_TRY(ctx, hipStreamSynchronize(st_big));
-        rc = 0;
-        if (n_large) {
-            if (full_plane > 0xFFFFFFF0ull) return fail(ctx, NYXHIP_ERR_ROI_TOO_LARGE, "bounding box too large for the contour plane");
-            const size_t stride = al((size_t)full_plane);
-            const uint32_t chunk = (uint32_t)std::max<size_t>(1, std::min<size_t>(n_large, ((size_t)4 << 30) / stride));
-            const size_t sneed = stride * chunk;
-            HIP_TRY(ctx, spill.reserve(sneed, st_big));
-            MomArgs m2 = m;
-            m2.plane_cap = (uint32_t)full_plane;
-            m2.sp.defer_large = 0;
-            m2.sp.scratch = spill.as<unsigned char>(); m2.sp.stride = stride;
-            for (uint32_t o = 0; o < n_large && rc == 0; o += chunk) {
-                m2.sp.roi_index = d_list + o;
-                rc = launch_roi_contour(m2, st_big, std::min(chunk, n_large - o));
-            }
-            if (rc == 0) {                                    // moments of the big boxes: the list
-                MomArgs m3 = m;
-                m3.sp.roi_index = d_list;
-                rc = launch_readers(m3, st_big, n_large);
-            }
-        }
-        if (rc == 0) {
-            m.sp.defer_large = 1;                             // both kernels skip the big boxes
-            rc = launch_roi_contour(m, st, grid);
-            if (rc == 0) rc = launch_readers(m, st, grid);
-        }
-    }
-    if (rc != 0)
-        return fail(ctx, NYXHIP_ERR_HIP, std::string("contour / moments / radial / outline / circle kernel launch failed: ") + hipGetErrorString((hipError_t)rc));
-    if (contour_out) *contour_out = m;
-    if (out_deferred) {
-        if (st_join) {                                     // the deferred ROIs' contours may come from the big boxes' lane
-            HIP_TRY(ctx, hipEventRecord(ctx->lane_done[nyxhip_ctx::kMomLaneBig], st_join));
-            HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->lane_done[nyxhip_ctx::kMomLaneBig], 0));
-        }
-        oa.m = m;
-        return launch_outline_deferred(st);
-    }
-    return NYXHIP_OK;
-}
-
 // ---- size classes ------------------------------------------------------------------------------------------------------------
 // The reference has no coupling between the ROIs of a batch: every worker thread takes ROIs of any size
 // (the reference's src/nyx/parallel.h:23-42, roi_cache.h:31-84).  Here a launch carves its LDS for the largest ROI it holds, so
@@ -950,14 +520,6 @@ static Extrema class_bounds(int cls, const nyxhip_settings* s)
     E.vmax = s->ibsi ? kLdsLevels : 0u;
     E.wide_only = (cls & 1) != 0;
     return E;
-}
-
-// Workspace budget of a large-ROI path: NYXHIP_LARGE_BUDGET_MB when set (tests: a small budget sends a class through the chunked form;
-// read per call), else the path's default.
-static size_t large_budget(size_t dflt)
-{
-    const char* const be = getenv("NYXHIP_LARGE_BUDGET_MB");
-    return be && atoll(be) > 0 ? (size_t)atoll(be) << 20 : dflt;
 }
 
 // INTENSITY + GLCM of one class by the several-workgroups-per-ROI kernels of roi_large.hip.  Members whose intensity range the
@@ -1704,7 +1266,7 @@ int launch_device_all(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t mask, con
         // behind every feature launch of the call -- the lanes join here and the contour chain stays on the call's stream.
         const bool after_all = (mask & kBehindIntensity) && (mask & NYXHIP_FAM_GLCM);
         if (after_all) lane_join.join();
-        if (int mrc = contour_families(ctx, b, mask, s, d_out, ld, max_px, max_area, max_side, !after_all))
+        if (int mrc = launch_contour_families(ctx, b, mask, s, d_out, ld, max_px, max_area, max_side, !after_all))
             return mrc;
     }
     return NYXHIP_OK;
@@ -1715,10 +1277,32 @@ int launch_device_all(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t mask, con
 // ---- what the other host units call (declared in nyxhip_ctx.h) ----
 namespace nyxhip {
 
-int launch_contour_families(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t mask, const nyxhip_settings* s, double* d_out, size_t ld, uint32_t max_px,
-                            uint32_t max_area, uint32_t max_side, bool allow_lane, MomArgs* contour_out)
+// A workspace lane: a high-priority stream forked from the call's stream (nyxhip_ctx::lane_fork, recorded at the start of launch_device_all),
+// joined into it at the end of the call (LaneJoin).  The lanes carry chains of short, latency-bound kernels -- a few hundred workgroups each --
+// beside the main stream's chip-filling grids: at the device's highest priority their workgroups are placed first and the chain is not starved.
+int use_lane(nyxhip_ctx* ctx, int lane, hipStream_t* st)
 {
-    return contour_families(ctx, b, mask, s, d_out, ld, max_px, max_area, max_side, allow_lane, contour_out);
+    if (!ctx->lane_stream[lane]) {
+        static const bool no_prio = [] { const char* e = getenv("NYXHIP_NO_LANE_PRIORITY"); return e && *e && *e != '0'; }();   // A/B knob
+        int lo = 0, hi = 0;
+        if (no_prio || hipDeviceGetStreamPriorityRange(&lo, &hi) != hipSuccess) lo = hi = 0;
+        HIP_TRY(ctx, hipStreamCreateWithPriority(&ctx->lane_stream[lane], hipStreamNonBlocking, hi));
+        HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->lane_done[lane], hipEventDisableTiming));
+    }
+    if (!ctx->lane_used[lane]) {
+        HIP_TRY(ctx, hipStreamWaitEvent(ctx->lane_stream[lane], ctx->lane_fork, 0));   // the batch and the class lists are complete on the main stream
+        ctx->lane_used[lane] = true;
+    }
+    *st = ctx->lane_stream[lane];
+    return NYXHIP_OK;
+}
+
+// Workspace budget of a large-ROI path or a deferred list (deferred_list.h): NYXHIP_LARGE_BUDGET_MB when set (tests: a small budget
+// sends a class, or a list, through the chunked form; read per call), else the path's default.
+size_t large_budget(size_t dflt)
+{
+    const char* const be = getenv("NYXHIP_LARGE_BUDGET_MB");
+    return be && atoll(be) > 0 ? (size_t)atoll(be) << 20 : dflt;
 }
 
 uint32_t pow2ceil(uint32_t v)

@@ -37,7 +37,7 @@ struct CalArgs {
 };
 
 int launch_roi_caliper(const CalArgs& a, void* stream, uint32_t grid);
-// ROIs whose boxes are wider than `cap` columns -> index list
-int launch_caliper_classify(uint64_t n_roi, const uint32_t* bw, uint32_t cap, uint32_t* list, uint32_t* n_out, void* stream);
+// predicate of the deferred list (deferred_list.h): ROIs whose boxes are wider than `cap` columns
+struct CaliperWide { const uint32_t* bw; uint32_t cap; __device__ bool operator()(uint64_t i, uint32_t* hdr) const; };
 
 } // namespace nyxhip

@@ -21,6 +21,7 @@
 #include "device_math.h"
 #include "roi_caliper.h"
 #include "launch_util.h"
+#include "deferred_list.h"
 #include "../../include/nyxhip.h"
 
 namespace nyxhip {
@@ -335,13 +336,11 @@ __global__ __launch_bounds__(kCB) void roi_caliper_kernel(const CalArgs R)
     else caliper_body(R, S, cal_lds, R.cols_cap, w, ox, oy, row_out, tid, sweep);
 }
 
-__global__ void caliper_classify_kernel(uint64_t n_roi, const uint32_t* bw, uint32_t cap, uint32_t* list, uint32_t* n_out)
+__device__ bool CaliperWide::operator()(uint64_t i, uint32_t*) const
 {
-    const uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
-    if (i >= n_roi) return;
-    if (bw[i] > cap)
-        list[atomicAdd(n_out, 1u)] = (uint32_t)i;
+    return bw[i] > cap;
 }
+template int deferred_classify<CaliperWide>(uint64_t, const CaliperWide&, uint32_t*, hipStream_t);
 
 int launch_roi_caliper(const CalArgs& a, void* stream, uint32_t grid)
 {
@@ -349,14 +348,6 @@ int launch_roi_caliper(const CalArgs& a, void* stream, uint32_t grid)
         return 0;
     const uint32_t dyn = kCaliperBytesPerCol * a.cols_cap;                   // (<= 24 KiB)
     hipLaunchKernelGGL(roi_caliper_kernel, dim3(grid), dim3(kCB), dyn, (hipStream_t)stream, a);
-    return (int)hipGetLastError();
-}
-
-int launch_caliper_classify(uint64_t n_roi, const uint32_t* bw, uint32_t cap, uint32_t* list, uint32_t* n_out, void* stream)
-{
-    if (n_roi == 0)
-        return 0;
-    hipLaunchKernelGGL(caliper_classify_kernel, dim3((unsigned)((n_roi + 255) / 256)), dim3(256), 0, (hipStream_t)stream, n_roi, bw, cap, list, n_out);
     return (int)hipGetLastError();
 }
 

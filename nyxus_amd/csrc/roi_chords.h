@@ -58,9 +58,8 @@ struct ChordArgs {
 };
 
 int launch_roi_chords(const ChordArgs& a, void* stream, uint32_t grid);
-// ROIs for the list launch -> list; hdr[0] = their number, hdr[1] = largest chords_plane_words among them (saturated),
-// hdr[2] = largest chords_plane_side among those with min_inten == 0
-int launch_chords_classify(uint64_t n_roi, const uint32_t* bw, const uint32_t* bh, const uint32_t* min_inten, uint32_t lds_words,
-                           uint32_t* list, uint32_t* hdr, void* stream);
+// predicate of the deferred list (deferred_list.h): the ROIs of the list launch; hdr[1] = largest chords_plane_words among them
+// (saturated), hdr[2] = largest chords_plane_side among those with min_inten == 0
+struct ChordsListed { const uint32_t *bw, *bh, *min_inten; uint32_t lds_words; __device__ bool operator()(uint64_t i, uint32_t* hdr) const; };
 
 } // namespace nyxhip

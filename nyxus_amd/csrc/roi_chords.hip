@@ -27,6 +27,7 @@
 #include "sort_lds.h"
 #include "roi_chords.h"
 #include "launch_util.h"
+#include "deferred_list.h"
 #include "../../include/nyxhip.h"
 
 namespace nyxhip {
@@ -305,17 +306,15 @@ __global__ __launch_bounds__(kHB) void roi_chords_kernel(const ChordArgs R)
     }
 }
 
-__global__ void chords_classify_kernel(uint64_t n_roi, const uint32_t* bw, const uint32_t* bh, const uint32_t* min_inten, uint32_t lds_words,
-                                       uint32_t* list, uint32_t* hdr)
+__device__ bool ChordsListed::operator()(uint64_t i, uint32_t* hdr) const
 {
-    const uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
-    if (i >= n_roi) return;
-    if (!chords_listed(bw[i], bh[i], min_inten[i], lds_words)) return;
-    list[atomicAdd(&hdr[0], 1u)] = (uint32_t)i;
+    if (!chords_listed(bw[i], bh[i], min_inten[i], lds_words)) return false;
     const uint64_t pw = chords_plane_words(bw[i], bh[i]);
     atomicMax(&hdr[1], pw > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)pw);
     if (min_inten[i] == 0u) atomicMax(&hdr[2], chords_plane_side(bw[i], bh[i]));
+    return true;
 }
+template int deferred_classify<ChordsListed>(uint64_t, const ChordsListed&, uint32_t*, hipStream_t);
 
 int launch_roi_chords(const ChordArgs& a, void* stream, uint32_t grid)
 {
@@ -323,16 +322,6 @@ int launch_roi_chords(const ChordArgs& a, void* stream, uint32_t grid)
         return 0;
     const uint32_t dyn = 4u * (a.lds_words > kChordsSortWords ? a.lds_words : kChordsSortWords);   // (16 .. 32 KiB)
     hipLaunchKernelGGL(roi_chords_kernel, dim3(grid), dim3(kHB), dyn, (hipStream_t)stream, a);
-    return (int)hipGetLastError();
-}
-
-int launch_chords_classify(uint64_t n_roi, const uint32_t* bw, const uint32_t* bh, const uint32_t* min_inten, uint32_t lds_words,
-                           uint32_t* list, uint32_t* hdr, void* stream)
-{
-    if (n_roi == 0)
-        return 0;
-    hipLaunchKernelGGL(chords_classify_kernel, dim3((unsigned)((n_roi + 255) / 256)), dim3(256), 0, (hipStream_t)stream, n_roi, bw, bh, min_inten,
-                       lds_words, list, hdr);
     return (int)hipGetLastError();
 }
 

@@ -42,8 +42,9 @@ struct EroArgs {
 };
 
 int launch_roi_erosion(const EroArgs& a, void* stream, uint32_t grid);
-// ROIs whose two planes exceed `cap` words -> index list; hdr[0] = their number, hdr[1] = largest plane (words of ONE plane, saturated)
-int launch_erosion_classify(uint64_t n_roi, const uint32_t* bw, const uint32_t* bh, uint32_t cap, uint32_t* list, uint32_t* hdr, void* stream);
+// predicate of the deferred list (deferred_list.h): ROIs whose two planes exceed `cap` words; hdr[1] = largest plane among them
+// (words of ONE plane, saturated)
+struct ErosionListed { const uint32_t *bw, *bh; uint32_t cap; __device__ bool operator()(uint64_t i, uint32_t* hdr) const; };
 // the ellipse columns of every ROI: a wave per ROI of <= kEllipseWavePx pixels, and, when `with_large`, a workgroup per larger ROI
 int launch_roi_ellipse(const EroArgs& a, void* stream, bool with_large);
 

@@ -24,6 +24,7 @@
 #include "device_math.h"
 #include "roi_erosion.h"
 #include "launch_util.h"
+#include "deferred_list.h"
 #include "../../include/nyxhip.h"
 
 namespace nyxhip {
@@ -232,15 +233,14 @@ __global__ __launch_bounds__(kEB) void roi_erosion_kernel(const EroArgs R)
     if (tid == 0) o[0] = (double)v;
 }
 
-__global__ void erosion_classify_kernel(uint64_t n_roi, const uint32_t* bw, const uint32_t* bh, uint32_t cap, uint32_t* list, uint32_t* hdr)
+__device__ bool ErosionListed::operator()(uint64_t i, uint32_t* hdr) const
 {
-    const uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
-    if (i >= n_roi) return;
-    if (!erosion_listed(bw[i], bh[i], cap)) return;
-    list[atomicAdd(&hdr[0], 1u)] = (uint32_t)i;
+    if (!erosion_listed(bw[i], bh[i], cap)) return false;
     const uint64_t pw = erosion_plane_words(bw[i], bh[i]);
     atomicMax(&hdr[1], pw > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)pw);
+    return true;
 }
+template int deferred_classify<ErosionListed>(uint64_t, const ErosionListed&, uint32_t*, hipStream_t);
 
 // a wave per ROI: workgroup b, wave v serves ROI kEW * b + v when it has at most kEllipseWavePx pixels
 __global__ __launch_bounds__(kEB) void roi_ellipse_wave_kernel(const EroArgs R)
@@ -299,14 +299,6 @@ int launch_roi_erosion(const EroArgs& a, void* stream, uint32_t grid)
         return 0;
     const uint32_t dyn = 4u * (a.roi_index ? 0u : a.lds_words);              // (<= 32 KiB)
     hipLaunchKernelGGL(roi_erosion_kernel, dim3(grid), dim3(kEB), dyn, (hipStream_t)stream, a);
-    return (int)hipGetLastError();
-}
-
-int launch_erosion_classify(uint64_t n_roi, const uint32_t* bw, const uint32_t* bh, uint32_t cap, uint32_t* list, uint32_t* hdr, void* stream)
-{
-    if (n_roi == 0)
-        return 0;
-    hipLaunchKernelGGL(erosion_classify_kernel, dim3((unsigned)((n_roi + 255) / 256)), dim3(256), 0, (hipStream_t)stream, n_roi, bw, bh, cap, list, hdr);
     return (int)hipGetLastError();
 }
 

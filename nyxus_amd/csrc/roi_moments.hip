@@ -19,6 +19,7 @@
 #include "device_math.h"
 #include "roi_kernel.h"
 #include "launch_util.h"
+#include "deferred_list.h"
 #include "contour_descent.h"
 #include "../../include/nyxhip.h"
 
@@ -671,6 +672,13 @@ int launch_roi_contour(const MomArgs& a, void* stream, uint32_t grid)
         hipLaunchKernelGGL(roi_contour_kernel<false>, dim3(wgs), dim3(64 * kContourWaves), kContourWaves * ((a.plane_cap + 15u) & ~15u), (hipStream_t)stream, b);
     return (int)hipGetLastError();
 }
+
+// ROIs whose padded flag plane exceeds the LDS cap of the contour kernel
+__device__ bool ContourPlaneBig::operator()(uint64_t i, uint32_t*) const
+{
+    return (uint64_t)(bw[i] + 2) * (bh[i] + 2) > cap;
+}
+template int deferred_classify<ContourPlaneBig>(uint64_t, const ContourPlaneBig&, uint32_t*, hipStream_t);
 
 __global__ void moments_logtab_kernel(double* tab, uint32_t n)
 {

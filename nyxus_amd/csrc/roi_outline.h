@@ -46,8 +46,7 @@ struct OutArgs {
 };
 
 int launch_roi_outline(const OutArgs& a, void* stream, uint32_t grid);
-// ROIs whose bit planes exceed `cap` words -> index list
-int launch_outline_classify(uint64_t n_roi, const uint32_t* bw, const uint32_t* bh, uint32_t pyramid, uint32_t cap, uint32_t* list, uint32_t* n_out,
-                            void* stream);
+// predicate of the deferred list (deferred_list.h): ROIs whose bit planes exceed `cap` words
+struct OutlineBitsBig { const uint32_t *bw, *bh; uint32_t pyramid, cap; __device__ bool operator()(uint64_t i, uint32_t* hdr) const; };
 
 } // namespace nyxhip

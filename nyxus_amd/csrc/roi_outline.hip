@@ -19,6 +19,7 @@
 #include "device_math.h"
 #include "roi_outline.h"
 #include "launch_util.h"
+#include "deferred_list.h"
 #include "contour_descent.h"
 #include "../../include/nyxhip.h"
 
@@ -381,14 +382,11 @@ __global__ __launch_bounds__(kOB) void roi_outline_kernel(const OutArgs R)
     }
 }
 
-__global__ void outline_classify_kernel(uint64_t n_roi, const uint32_t* bw, const uint32_t* bh, uint32_t pyramid, uint32_t cap, uint32_t* list,
-                                        uint32_t* n_out)
+__device__ bool OutlineBitsBig::operator()(uint64_t i, uint32_t*) const
 {
-    const uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
-    if (i >= n_roi) return;
-    if (outline_bit_words(bw[i], bh[i], pyramid != 0) > cap)
-        list[atomicAdd(n_out, 1u)] = (uint32_t)i;
+    return outline_bit_words(bw[i], bh[i], pyramid != 0) > cap;
 }
+template int deferred_classify<OutlineBitsBig>(uint64_t, const OutlineBitsBig&, uint32_t*, hipStream_t);
 
 int launch_roi_outline(const OutArgs& a, void* stream, uint32_t grid)
 {
@@ -397,15 +395,6 @@ int launch_roi_outline(const OutArgs& a, void* stream, uint32_t grid)
     // (<= 24 + 8 + 4 + 8 KiB: below the 64 KiB that needs an opt-in)
     const uint32_t dyn = 8u * a.m.px_cap + 4u * a.m.k_cap + ((2u * a.m.step_cap + 15u) & ~15u) + 4u * a.bits_cap;
     hipLaunchKernelGGL(roi_outline_kernel, dim3(grid), dim3(kOB), dyn, (hipStream_t)stream, a);
-    return (int)hipGetLastError();
-}
-
-int launch_outline_classify(uint64_t n_roi, const uint32_t* bw, const uint32_t* bh, uint32_t pyramid, uint32_t cap, uint32_t* list, uint32_t* n_out,
-                            void* stream)
-{
-    if (n_roi == 0)
-        return 0;
-    hipLaunchKernelGGL(outline_classify_kernel, dim3((unsigned)((n_roi + 255) / 256)), dim3(256), 0, (hipStream_t)stream, n_roi, bw, bh, pyramid, cap, list, n_out);
     return (int)hipGetLastError();
 }
 
