@@ -237,7 +237,19 @@ int nyxhip_n_columns(uint32_t family_mask, const nyxhip_settings* s)
 int nyxhip_column_name(uint32_t family_mask, const nyxhip_settings* s, int col, char* buf, size_t buf_len)
 {
     if (!s || !buf || buf_len == 0) return NYXHIP_ERR_INVALID_ARG;
-    auto v = column_names(family_mask & kImplemented, s);
+    // callers walk a mask's columns one call per column: the list of the last (mask, settings) asked for is kept per thread
+    struct Key { uint32_t mask; int32_t na, nf, ang[NYXHIP_MAX_GLCM_ANGLES]; };
+    Key key{family_mask & kImplemented, s->glcm_n_angles, s->gabor_n_filters, {}};
+    for (int a = 0; a < NYXHIP_MAX_GLCM_ANGLES; a++) key.ang[a] = s->glcm_angles[a];
+    thread_local Key last_key;
+    thread_local bool have_last = false;
+    thread_local std::vector<std::string> last;
+    if (!have_last || memcmp(&key, &last_key, sizeof(Key)) != 0) {
+        last = column_names(key.mask, s);
+        last_key = key;
+        have_last = true;
+    }
+    const auto& v = last;
     if (col < 0 || col >= (int)v.size()) return NYXHIP_ERR_INVALID_ARG;
     snprintf(buf, buf_len, "%s", v[col].c_str());
     return NYXHIP_OK;
