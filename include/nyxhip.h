@@ -395,6 +395,28 @@ int nyxhip_ih_tiles(nyxhip_ctx* ctx, const nyxhip_tiles* tiles, const nyxhip_set
                     uint32_t* out_labels, uint32_t* out_tile_index, uint64_t max_rows,
                     double* out_table, size_t out_ld, uint64_t* n_roi_out);
 
+/* ---- whole-slide mode ---------------------------------------------------------------
+ * The reference's second mode (featurize_files(files, None, single_roi = True), featurize_directory() without a label directory;
+ * workflow_2d_whole.cpp:36-213, reduce_trivial_rois.cpp:798-819, slideprops.cpp:101-254): every slide is ONE ROI with label 1 that
+ * covers the whole image, zero-valued pixels included.  Area = width * height, the box is the image with origin (0, 0), aux_min /
+ * aux_max are the extrema over all pixels, and the slide extrema are the same two values (COVERED_IMAGE_INTENSITY_RANGE = range / range).
+ *
+ * `slides` is the struct of the tile path: inten [n_tiles][height][width] of inten_dtype, memory NYXHIP_MEM_HOST or NYXHIP_MEM_DEVICE
+ * (the images AND out_table), max_device_bytes as there.  `label` must be NULL (NYXHIP_ERR_INVALID_ARG otherwise); label_dtype,
+ * slide_mode, slide_min and slide_max are not read.  One row per slide, in input order, nyxhip_n_columns(family_mask, s) columns in the
+ * order and under the names of every other entry.  Row t has the bits of nyxhip_featurize_batch on the one-ROI batch whose cloud is
+ * the slide's pixels in row-major order (x = i % width, y = i / width, intensity widened to 32 bits), bbox_w = width, bbox_h = height,
+ * min_inten / max_inten the slide's extrema and slide_min / slide_max the same extrema as doubles.
+ *
+ * Served: any non-empty subset of bits 0-9 (NYXHIP_FAM_ALL without the two moment classes, which weight differently in this mode:
+ * 2d_geomoments_basic.cpp:122-123).  Any other valid family bit is NYXHIP_ERR_UNSUPPORTED; a bit that is invalid everywhere stays
+ * NYXHIP_ERR_INVALID_ARG.  width or height of 0 or above 65534 is NYXHIP_ERR_UNSUPPORTED (coordinates inside an ROI are 16-bit);
+ * n_tiles == 0 is NYXHIP_OK and writes nothing; a single slide that does not fit max_device_bytes is NYXHIP_ERR_ROI_TOO_LARGE.  The
+ * stack is processed in chunks of slides that fit the budget; host chunks travel through the pinned staging ring of the tile path, the
+ * copy of chunk c + 1 beside the reduce of chunk c.  Every family keeps the limits it has behind nyxhip_featurize_batch.  Synchronous. */
+int nyxhip_featurize_slides(nyxhip_ctx* ctx, const nyxhip_tiles* slides, uint32_t family_mask,
+                            const nyxhip_settings* s, double* out_table, size_t out_ld);
+
 /* ---- measurement hooks -------------------------------------------------------
  * Average device time (ms) per featurize call since the last nyxhip_timing_reset(),
  * measured with hipEvents recorded on the launch stream around EVERYTHING the call
@@ -416,7 +438,7 @@ int nyxhip_timing_get(nyxhip_ctx* ctx, double* avg_kernel_ms, uint64_t* n_launch
  * -4 / -5: one-wave / four-wave shape kernels; "rois" is then the batch size); "workspace" 0 = kernels
  * with their state in LDS, else the kernel groups that run from the global workspace (bit 0 INTENSITY + GLCM, 1 texture,
  * 2 shape, 3 dependence); "cooperative" = families of the class served by several workgroups per ROI (ROIs beyond LDS): bit 0 INTENSITY +
- * GLCM, bit 1 GLRLM + GLSZM + NGTDM;
+ * GLCM, bit 1 GLRLM + GLSZM + NGTDM, bit 2 Gabor, bit 3 (with bit 0, nyxhip_featurize_slides only) the members were dense slides read in place, no clouds;
  * "ms" = device time of the class's launches on the call's stream and "lane_ms" = fork-to-end time of the class's workspace
  * launches on their own stream (large classes run them beside the main stream; null otherwise) when
  * nyxhip_timing_enable(ctx, 2) was in force for the call (waits for them), else null.  Counterpart in the

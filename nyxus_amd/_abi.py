@@ -57,6 +57,7 @@ MEM_HOST_OWN_MAPPING = 2   # nyxhip_tiles only: host arrays the caller declares 
 U8, U16, U32 = 1, 2, 4                       # tile element types (bytes per element)
 SLIDE_MONTAGE, SLIDE_PER_TILE, SLIDE_GIVEN = 0, 1, 2
 
+FAM_WHOLE_SLIDE = 0x3FF     # the families nyxhip_featurize_slides serves: bits 0-9, FAM_ALL without the two moment classes
 MAX_GLCM_ANGLES = 4
 NEIGHBOR_COLS = 9            # NYXHIP_NEIGHBOR_COLS: the table of nyxhip_neighbors_batch / _tiles (no family bit: the class relates the ROIs of an image)
 IH_COLS = 46                 # NYXHIP_IH_COLS: the table of nyxhip_ih_batch / _tiles (no family bit: every bit of the mask is spoken for)

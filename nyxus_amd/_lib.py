@@ -30,6 +30,7 @@ ABI_SYMBOLS = [
     "nyxhip_launch_report", "nyxhip_featurize_batch_at", "nyxhip_featurize_batch_async_at",
     "nyxhip_neighbor_column_name", "nyxhip_neighbors_batch", "nyxhip_neighbors_tiles",
     "nyxhip_ih_column_name", "nyxhip_ih_batch", "nyxhip_ih_tiles",
+    "nyxhip_featurize_slides",
 ]
 
 
@@ -129,6 +130,9 @@ def load() -> C.CDLL:
         lib.nyxhip_ih_tiles.argtypes = [C.c_void_p, P(_abi.Tiles), P(_abi.Settings), C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_size_t,
                                         P(C.c_uint64)]
         lib.nyxhip_ih_tiles.restype = C.c_int
+    if hasattr(lib, "nyxhip_featurize_slides"):  # (absent from older builds of the ABI selected through NYXHIP_LIB for A/B runs)
+        lib.nyxhip_featurize_slides.argtypes = [C.c_void_p, P(_abi.Tiles), C.c_uint32, P(_abi.Settings), C.c_void_p, C.c_size_t]
+        lib.nyxhip_featurize_slides.restype = C.c_int
     if hasattr(lib, "nyxhip_launch_report"):     # (absent from older builds of the ABI selected through NYXHIP_LIB for A/B runs)
         lib.nyxhip_launch_report.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
         lib.nyxhip_launch_report.restype = C.c_int
@@ -388,6 +392,33 @@ class Context:
         table = np.empty((n.value, ncol), np.float64)
         self._check(self._lib.nyxhip_fetch_result(self._h, labels.ctypes.data, tiles.ctypes.data, table.ctypes.data, ncol))
         return tiles, labels, table
+
+    def featurize_slides_host(self, inten: np.ndarray, mask: int, s: _abi.Settings, max_device_bytes: int = 0) -> np.ndarray:
+        """Whole-slide mode (nyxhip_featurize_slides): a stack [n, H, W] of uint8 / uint16 / uint32 host slides, every slide one ROI
+        with label 1 that covers the whole image.  Returns the table [n, n_columns], rows in input order; NaN / inf are left in place."""
+        dt = {np.dtype(np.uint8): _abi.U8, np.dtype(np.uint16): _abi.U16, np.dtype(np.uint32): _abi.U32}
+        if inten.ndim != 3 or inten.dtype not in dt:
+            raise ValueError("slides must be a 3-D array [n, H, W] of uint8, uint16 or uint32")
+        inten = np.ascontiguousarray(inten)
+        n, h, w = inten.shape
+        ncol = self.n_columns(mask, s)
+        out = np.empty((n, max(ncol, 0)), np.float64)
+        t = _abi.Tiles()
+        t.inten = inten.ctypes.data; t.label = None
+        t.inten_dtype = dt[inten.dtype]; t.width = w; t.height = h; t.n_tiles = n; t.memory = _abi.MEM_HOST
+        t.max_device_bytes = int(max_device_bytes)
+        self._check(self._lib.nyxhip_featurize_slides(self._h, C.byref(t), mask, C.byref(s), out.ctypes.data, max(ncol, 1)))
+        return out
+
+    def featurize_slides_device(self, inten_ptr: int, dtype: int, n: int, h: int, w: int, mask: int, s: _abi.Settings, out_ptr: int, ld: int,
+                                max_device_bytes: int = 0):
+        """The same entry on device memory: `inten_ptr` is a device array [n, h, w] of element type `dtype` (_abi.U8 / U16 / U32),
+        `out_ptr` a device table [n x ld] of doubles.  Synchronous."""
+        t = _abi.Tiles()
+        t.inten = inten_ptr; t.label = None
+        t.inten_dtype = dtype; t.width = w; t.height = h; t.n_tiles = n; t.memory = _abi.MEM_DEVICE
+        t.max_device_bytes = int(max_device_bytes)
+        self._check(self._lib.nyxhip_featurize_slides(self._h, C.byref(t), mask, C.byref(s), C.c_void_p(out_ptr), ld))
 
     def sync(self):
         self._check(self._lib.nyxhip_sync(self._h))

@@ -4,6 +4,7 @@
 //   nyxhip_dispatch.hip  layouts, argument blocks, size classes: a device-resident batch -> kernel launches
 //   nyxhip_contour.hip   the families without size classes: pixel-cloud and contour launchers, their deferred lists (deferred_list.h)
 //   nyxhip_tiles.hip     the fused tile path and its host staging
+//   nyxhip_slides.hip    whole-slide mode: nyxhip_featurize_slides (one ROI per slide, no label image)
 //   nyxhip_api.hip       context life cycle, the batch entry points, timing, launch report
 //   nyxhip_neighbors.hip the neighbor entries: column names, the launches over a device-resident batch, nyxhip_neighbors_batch
 //   nyxhip_ih.hip        the intensity-histogram entries: column names, the launches over a device-resident batch, nyxhip_ih_batch
@@ -108,10 +109,14 @@ struct ClassRun {              // one size class of one call, as launched (nyxhi
     int workspace;             // kernel groups that ran from a global workspace instead of LDS: bit 0 INTENSITY + GLCM, 1 texture, 2 shape, 3 dependence
     hipEvent_t e0, e1;         // around the class's launches on the main stream (timing enabled), else NULL
     hipEvent_t e2 = nullptr;   // ... and the end of its launches on its workspace lane
-    int cooperative = 0;       // bit 0: INTENSITY + GLCM by the several-workgroups-per-ROI kernels of roi_large.hip, bit 1: the texture families (roi_large_tex.hip)
+    int cooperative = 0;       // bit 0: INTENSITY + GLCM by the several-workgroups-per-ROI kernels of roi_large.hip, bit 1: the texture families (roi_large_tex.hip), bit 2: Gabor, bit 3: bit 0's kernels on dense slides (whole-slide mode)
 };
 struct ClassTotals {           // sums over the members of a class (class header): what the large-ROI path sizes its workspace from
     uint64_t px, area, range1; // pixels, bounding-box cells, histogram entries (range + 1 of the members whose range the path serves)
+};
+struct DenseSrc {              // whole-slide mode: the dense images the next run_large call reads instead of clouds (NULL: clouds)
+    const void* inten = nullptr;
+    int dt = 0;                // NYXHIP_U8 | NYXHIP_U16 | NYXHIP_U32
 };
 constexpr int NYXHIP_INTERNAL_NEEDS_CLOUDS = -1000;   // run_class: a launch group of a window-mode call needs the materialised clouds
 
@@ -175,6 +180,7 @@ struct nyxhip_ctx {
     PinnedSlot h_stage[kStageSlots];
     int h_stage_next = 0;
     nyxhip::WindowSrc win_next = {};                   // set by the tile path for its next launch_device call: read ROIs from their tile windows
+    DenseSrc dense_next;                       // set by launch_dense_slides around its run_large call
     uint32_t tile_cap_hint = 0;                // per-tile table size that served the last call
     // result kept for nyxhip_fetch_result() (host-memory calls with out_table == NULL): device-resident, grow-only
     //   [res_cap x res_cols] doubles | [res_cap] labels | [res_cap] tile indices
@@ -223,6 +229,13 @@ struct OriginScope {
     ~OriginScope() { c->origin_x_next = c->origin_y_next = nullptr; }
 };
 
+// Waits for two streams on every way out of a scope: a host pipeline must not return -- error returns included -- while copies out of
+// the caller's arrays or kernels on them are in flight (the caller may free the arrays the moment the entry returns).
+struct StreamDrain {
+    hipStream_t a, b;
+    ~StreamDrain() { (void)hipStreamSynchronize(a); (void)hipStreamSynchronize(b); }
+};
+
 // families the kernels cover so far
 constexpr uint32_t kTexture = NYXHIP_FAM_GLRLM | NYXHIP_FAM_GLSZM | NYXHIP_FAM_NGTDM;
 constexpr uint32_t kShape = NYXHIP_FAM_GABOR | NYXHIP_FAM_ZERNIKE;
@@ -266,6 +279,11 @@ void clear_runs(nyxhip_ctx* ctx);
 int launch_device(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t mask, const nyxhip_settings* s, double* d_out, size_t ld, uint32_t max_px,
                   uint32_t max_area, uint32_t max_range, uint32_t max_side, bool hinted = true);
 int validate(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t mask, const nyxhip_settings* s, double* out, size_t ld);
+int launch_dense_slides(nyxhip_ctx* ctx, const nyxhip_batch* b, const void* d_inten, int dt, uint32_t mask, const nyxhip_settings* s, double* d_out, size_t ld,
+                        const Extrema& E, const ClassTotals& tot, bool* served);   // whole-slide mode: INTENSITY + GLCM of dense images (roi_large.hip)
+// nyxhip_tiles.hip: what the host pipelines share (the tile path and the whole-slide path of nyxhip_slides.hip)
+hipError_t staged_h2d(nyxhip_ctx* ctx, void* dst, const void* src, size_t bytes, hipStream_t st);   // pageable host -> device through the pinned ring
+int ensure_copy_pipeline(nyxhip_ctx* ctx);                                                          // copy_stream, slot_ready / slot_free
 // nyxhip_contour.hip
 int launch_contour_families(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t mask, const nyxhip_settings* s, double* d_out, size_t ld, uint32_t max_px,
                             uint32_t max_area, uint32_t max_side, bool allow_lane, MomArgs* contour_out = nullptr);

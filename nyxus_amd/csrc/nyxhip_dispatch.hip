@@ -317,7 +317,7 @@ int make_dep_layout(uint32_t mask, const nyxhip_settings* s, uint32_t max_area, 
 __global__ void add_offset_kernel(const uint32_t* in, uint32_t add, uint32_t n, uint32_t* out)
 {
     uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) out[i] = in[i] + add;
+    if (i < n) out[i] = (in ? in[i] : i) + add;           // (in == NULL: add, add + 1, ...)
 }
 
 // Fills the three argument blocks for one set of extrema; `cap` = 0 -> LDS carve-outs, else spill layouts.
@@ -548,6 +548,7 @@ static int run_large(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t mask, cons
     for (int i = 0; i < kMaxAngles; i++) a.glcm_angles[i] = s->glcm_angles[i];
     a.n_hist = abs(s->grey_depth);
     if (const char* e = getenv("NYXHIP_LARGE_DBG")) a.dbg = (uint32_t)atoi(e);
+    a.dense = ctx->dense_next.inten; a.dense_dt = (uint32_t)ctx->dense_next.dt;   // whole-slide mode: the members are dense images (launch_dense_slides)
     a.vec_ok = (((uintptr_t)b->inten & 15u) == 0 && ((uintptr_t)b->x & 7u) == 0 && ((uintptr_t)b->y & 7u) == 0) ? 1u : 0u;
     const bool do_int = mask1 & NYXHIP_FAM_INTENSITY, do_glcm = mask1 & NYXHIP_FAM_GLCM;
     const int greyInfo = s->ibsi ? 0 : s->grey_depth;
@@ -1507,6 +1508,33 @@ int check_status(nyxhip_ctx* ctx)
         return fail(ctx, st, "device-side error " + std::to_string(st));
     }
     return NYXHIP_OK;
+}
+
+// Whole-slide mode, the dense chain: INTENSITY + GLCM of a device batch whose ROIs are dense images -- b->x, b->y and b->inten are NULL, ROI r
+// is the elements [px_offset[r], px_offset[r + 1]) of d_inten, row-major in its box -- by the several-workgroups-per-ROI kernels of
+// roi_large.hip with the dense load kernel in front.  E / tot: extrema and totals of the batch, as the class headers of
+// launch_device_all state them for a class.  Every ROI must have a range below kLargeRangeMax.  *served = false: the settings do not
+// fit those kernels and nothing was launched.
+int launch_dense_slides(nyxhip_ctx* ctx, const nyxhip_batch* b, const void* d_inten, int dt, uint32_t mask, const nyxhip_settings* s, double* d_out, size_t ld,
+                        const Extrema& E, const ClassTotals& tot, bool* served)
+{
+    hipStream_t st = ctx->stream();
+    const uint32_t n = (uint32_t)b->n_roi;
+    clear_runs(ctx);
+    const size_t list_bytes = 4ull * n + 256;
+    HIP_TRY(ctx, ctx->d_cls_list.reserve(list_bytes, st, list_bytes + list_bytes / 4));
+    uint32_t* const list = ctx->d_cls_list.as<uint32_t>();
+    if (int rc = launch_add_offset(nullptr, 0, n, list, st))
+        return fail(ctx, NYXHIP_ERR_HIP, std::string("list launch failed: ") + hipGetErrorString((hipError_t)rc));
+    ctx->dense_next = DenseSrc{d_inten, dt};
+    const int rc = run_large(ctx, b, mask, s, d_out, ld, E, tot, list, n, served);
+    ctx->dense_next = DenseSrc{};
+    if (rc == NYXHIP_OK && *served) {
+        ClassRun r{2 * (kSizeClasses - 1) + (E.range < 16384u ? 0 : 1), n, E, 0, nullptr, nullptr};
+        r.cooperative = 1 | 8;                          // bit 3: the load pass read dense images (nyxhip_launch_report)
+        ctx->runs.push_back(r);
+    }
+    return rc;
 }
 
 int launch_add_offset(const uint32_t* in, uint32_t add, uint32_t n, uint32_t* out, hipStream_t st)

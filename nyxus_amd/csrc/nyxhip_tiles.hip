@@ -208,6 +208,10 @@ static int res_reserve(nyxhip_ctx* ctx, size_t rows, size_t n_cols, hipStream_t 
     return NYXHIP_OK;
 }
 
+} // extern "C"
+
+namespace nyxhip {
+
 // [src, src + bytes) of pageable host memory -> device through the context's pinned ring: per piece of at most kStageSlotBytes, wait for
 // the slot's previous DMA, copy the piece into the slot with a few host threads (one thread moves ~10 GB/s, the link takes 50), enqueue
 // the DMA, go on with the next slot.  Host copy of piece i + 1 and DMA of piece i overlap.
@@ -229,7 +233,7 @@ static void parallel_copy(void* dst, const void* src, size_t n)
     if (rest < n) memcpy((char*)dst + rest, (const char*)src + rest, n - rest);
     for (auto& t : th) t.join();
 }
-static hipError_t staged_h2d(nyxhip_ctx* ctx, void* dst, const void* src, size_t bytes, hipStream_t st)
+hipError_t staged_h2d(nyxhip_ctx* ctx, void* dst, const void* src, size_t bytes, hipStream_t st)
 {
     static const bool no_stage = [] { const char* e = getenv("NYXHIP_NO_STAGING"); return e && *e && *e != '0'; }();   // A/B knob: the runtime's own pageable path
     if (no_stage || bytes < ((size_t)1 << 20)) return hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st);
@@ -248,6 +252,23 @@ static hipError_t staged_h2d(nyxhip_ctx* ctx, void* dst, const void* src, size_t
     }
     return hipSuccess;
 }
+
+// The copy stream and the slot events of the host pipelines (tile path, whole-slide path): chunk c + 1 is copied into device slot (c + 1) & 1
+// on the copy stream while the kernels of chunk c read slot c & 1 on the call's stream.
+int ensure_copy_pipeline(nyxhip_ctx* ctx)
+{
+    if (ctx->copy_stream) return NYXHIP_OK;
+    HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking));
+    for (int k = 0; k < 2; k++) {
+        HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->slot_ready[k], hipEventDisableTiming));
+        HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->slot_free[k], hipEventDisableTiming));
+    }
+    return NYXHIP_OK;
+}
+
+} // namespace nyxhip
+
+extern "C" {
 
 // Host tiles reach the device in one of two ways (nyxhip_tiles::memory):
 //   NYXHIP_MEM_HOST              any host memory.  The bytes go through the library's OWN pinned staging ring (staged_h2d: hipHostMalloc'ed
@@ -370,13 +391,7 @@ static int tiles_run(nyxhip_ctx* ctx, const nyxhip_tiles* t, uint32_t family_mas
     }
 
     // ---- host tiles: copy chunk c + 1 while chunk c is reduced --------------------------------------------------------------
-    if (!ctx->copy_stream) {
-        HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking));
-        for (int k = 0; k < 2; k++) {
-            HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->slot_ready[k], hipEventDisableTiming));
-            HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->slot_free[k], hipEventDisableTiming));
-        }
-    }
+    if (int prc = ensure_copy_pipeline(ctx)) return prc;
     const size_t slot_need = (size_t)chunk * tile_in_bytes + 512;
     const uint64_t n_chunks = (t->n_tiles + chunk - 1) / chunk;
     for (int k = 0; k < (n_chunks > 1 ? 2 : 1); k++)
@@ -401,10 +416,7 @@ static int tiles_run(nyxhip_ctx* ctx, const nyxhip_tiles* t, uint32_t family_mas
     };
     // every exit below -- the error returns included -- first waits for the copies and kernels still in flight: the pin guard above
     // unregisters the caller's arrays, and the caller may free them the moment this function returns
-    struct Drain {
-        hipStream_t a, b;
-        ~Drain() { (void)hipStreamSynchronize(a); (void)hipStreamSynchronize(b); }
-    } drain{ctx->copy_stream, st};
+    StreamDrain drain{ctx->copy_stream, st};
     if (int urc = upload(0)) return urc;
     for (uint64_t c = 0; c < n_chunks; c++) {
         const int k = (int)(c & 1);

@@ -412,6 +412,19 @@ int launch_tile_rank(TileRows U, const uint32_t* tile_row_begin, const unsigned 
 int launch_tile_clouds(const void* inten, int dt_inten, const void* label, int dt_label, uint32_t W, uint32_t H, TileRows R, uint32_t n_roi,
                        uint16_t* cx, uint16_t* cy, uint32_t* cv, void* stream);
 
+// ---- whole-slide mode: every slide is one ROI that covers the whole image (roi_slide.hip) ---------------------------------------
+struct SlideRows {       // the per-ROI arrays of a nyxhip_batch, one entry per slide ([n_slides], px_offset [n_slides + 1])
+    uint32_t* label;
+    uint64_t* px_offset;
+    uint32_t *bbox_w, *bbox_h, *vmin, *vmax;
+    double *slide_min, *slide_max;
+};
+// extrema over all pixels of every slide, then the rows: label 1, px_offset = t * w * h, box = the image, slide extrema = the ROI's
+int launch_slide_headers(const void* inten, int dt_inten, uint32_t w, uint32_t h, uint32_t n_slides, SlideRows R, void* stream);
+// the row-major clouds of slides first .. first + n_slides of a chunk, each at its place in the chunk's arrays (slide t owns
+// [t * w * h, (t + 1) * w * h)): x = i % w, y = i / w, intensity widened to 32 bits
+int launch_slide_clouds(const void* inten, int dt_inten, uint32_t w, uint32_t h, uint32_t first, uint32_t n_slides, uint16_t* cx, uint16_t* cy, uint32_t* cv, void* stream);
+
 // ---- large-ROI path: INTENSITY + GLCM of an ROI by several workgroups (roi_large.hip) ---------------------------------------------
 // The reference gives any ROI to any worker (/root/reference/src/nyx/parallel.h:23-42); here an ROI beyond the LDS classes is cut
 // into slabs of its pixel cloud (load pass) and strips of its bounding-box plane (co-occurrence pass), every slab / strip a
@@ -479,6 +492,11 @@ struct LargeArgs {
     uint32_t fin_P_bytes;          // ... of which the matrices may take this much (staged from the workspace; 0: read in place)
     uint32_t vec_ok;               // 1: inten is 16-byte and x / y are 8-byte aligned (groups of four pixels load as vectors)
     uint32_t dbg;                  // timing experiments only (NYXHIP_LARGE_DBG): 1 no plane stores, 2 no histogram counts, 4 no table flush, 8 no sums
+    // whole-slide mode: the members are dense images instead of clouds (x, y, inten are NULL).  Pixel i of member r is element
+    // px_offset[r] + i of `dense`, row-major; the load kernel reads the image in its own element type and the plane of a member has
+    // the image's layout, so nothing is scattered and no coordinate exists.
+    const void* dense;             // NULL: clouds
+    uint32_t dense_dt;             // NYXHIP_U8 | NYXHIP_U16 | NYXHIP_U32
 };
 int launch_large_features(const LargeArgs& a, void* stream);
 

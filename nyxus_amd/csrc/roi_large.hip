@@ -5,7 +5,8 @@
 // while the rest of the chip idles.  Here such an ROI is cut up:
 //
 //   large_prep_kernel    one thread per ROI: its block of the workspace, its slabs / strips in the two work maps
-//   large_load_kernel    one workgroup per SLAB of the pixel cloud (the only pass over HBM: 8 B per pixel): exact sums, the
+//   large_load_kernel    one workgroup per SLAB of the pixel cloud (the only pass over HBM: 8 B per pixel; large_load_dense_kernel:
+//                        per slab of a dense image, whole-slide mode, 1 / 2 / 4 B per pixel): exact sums, the
 //                        intensity histogram over [min, max] (counted in LDS, flushed with contiguous atomic adds), the binned
 //                        bounding-box plane (features/texture_feature.h binning) scattered to the workspace
 //   large_cooc_kernel    one workgroup per STRIP of plane rows: co-occurrence counts of all angles (features/glcm.cpp:343-485)
@@ -99,10 +100,15 @@ __global__ __launch_bounds__(256) void large_prep_kernel(const LargeArgs A)
         large_roi(A, j, R, false);
         served = large_served(R);
         if (served) {
-            g_load = (uint32_t)(((R.off & 3ull) + R.n + A.px_per_wg - 1) / A.px_per_wg);   // slabs start at the group of four that holds the first pixel
-            // scan order of the cloud, read off a pair of pixels in its middle (the first column of a disk is a single pixel)
-            const uint64_t m = R.off + (R.n >= 2 ? R.n / 2 - 1 : 0);
-            large_set_orientation(R, (R.n >= 2 && A.x[m + 1] == A.x[m] && (uint32_t)A.y[m + 1] == (uint32_t)A.y[m] + 1u) ? 1u : 0u);
+            if (A.dense) {                                  // a dense image: slabs of its own pixel index, the plane is the image (row-major); no cloud to probe
+                g_load = (uint32_t)(((uint64_t)R.n + A.px_per_wg - 1) / A.px_per_wg);
+                large_set_orientation(R, 0u);
+            } else {
+                g_load = (uint32_t)(((R.off & 3ull) + R.n + A.px_per_wg - 1) / A.px_per_wg);   // slabs start at the group of four that holds the first pixel
+                // scan order of the cloud, read off a pair of pixels in its middle (the first column of a disk is a single pixel)
+                const uint64_t m = R.off + (R.n >= 2 ? R.n / 2 - 1 : 0);
+                large_set_orientation(R, (R.n >= 2 && A.x[m + 1] == A.x[m] && (uint32_t)A.y[m + 1] == (uint32_t)A.y[m] + 1u) ? 1u : 0u);
+            }
             const uint32_t rps = rows_per_strip(R.pw);
             g_cooc = (A.mask & NYXHIP_FAM_GLCM) ? (R.ph + rps - 1) / rps : 0u;
         }
@@ -136,7 +142,91 @@ __global__ __launch_bounds__(256) void large_prep_kernel(const LargeArgs A)
     for (uint32_t s = 0; s < g_cooc; s++) A.map_cooc[b_cooc + s] = make_uint2(j, s);
 }
 
-// ---- load: one workgroup per slab of the cloud --------------------------------------------------------------------------------
+// ---- load: one workgroup per slab of the cloud (or of a dense image) -----------------------------------------------------------
+// What a load workgroup does with one pixel value, however it reached it: the two exact sums, the histogram count (16-bit counters in
+// LDS when the ROI's range fits tab_lds, else global atomics), and the binned level of the plane (features/texture_feature.h binning:
+// matlab, radiomics with the level flags, or IBSI; intensity 0 gives level 0), clipped to the plane's element type.
+template <bool P16>
+struct LargePixel {
+    uint32_t* s_tab;
+    uint32_t* T;
+    uint16_t* flags;
+    uint32_t vmin, vmax, range, lvl_cap, dbg;
+    int greyInfo;
+    double mslope;
+    bool do_int, do_glcm, tab_in_lds;
+    unsigned long long sum, sumsq;
+    __device__ __forceinline__ uint32_t operator()(uint32_t v)
+    {
+        sum += v;
+        sumsq += (uint32_t)(v * v);                                           // unsigned-int product, wraps (intensity.cpp:90)
+        if (do_int && !(dbg & 2)) {
+            const uint32_t ci = v - vmin;
+            if (tab_in_lds) atomicAdd(&s_tab[ci >> 1], 1u << (16 * (ci & 1u)));
+            else if (ci <= range) atomicAdd(&T[ci], 1u);
+        }
+        uint32_t lvl = 0;
+        if (do_glcm && v != 0) {                                              // original intensity 0 is skipped by the scan (glcm.cpp:445)
+            if (greyInfo > 0) {   // matlab binning of a non-zero value: floor(slope v + 1) >= 1 already (the conversion truncates a positive value)
+                const uint32_t sc = (uint32_t)(mslope * (double)v + 1.0);
+                lvl = sc > (uint32_t)greyInfo ? (uint32_t)greyInfo : sc;
+            } else
+                lvl = greyInfo < 0 ? bin_radiomix(v, vmin, vmax, -greyInfo) : v;
+            if (greyInfo < 0 && lvl <= lvl_cap) flags[lvl] = 1;
+        }
+        constexpr uint32_t lvl_clip = P16 ? 0xFFFFu : 0xFFu;
+        return lvl > lvl_clip ? lvl_clip : lvl;
+    }
+};
+
+// The start of a load workgroup: the LDS table cleared (one barrier when it is used).  lds_raw: [tab_lds / 2] words of two 16-bit counters,
+// then the [2 * 16] words of large_slab_close.
+template <bool P16>
+__device__ __forceinline__ LargePixel<P16> large_slab_open(const LargeArgs& A, const LargeRoi& R, unsigned char* lds_raw, int tid, int BS)
+{
+    LargePixel<P16> px;
+    px.do_int = (A.mask & NYXHIP_FAM_INTENSITY) != 0; px.do_glcm = (A.mask & NYXHIP_FAM_GLCM) != 0;
+    px.s_tab = (uint32_t*)lds_raw;
+    px.T = (uint32_t*)(R.base + R.L.tab);
+    px.flags = (uint16_t*)(R.base + R.L.lvl);
+    px.vmin = R.vmin; px.vmax = R.vmax; px.range = R.range; px.lvl_cap = R.lvl_cap; px.dbg = A.dbg;
+    px.tab_in_lds = px.do_int && R.range < A.tab_lds;                        // (a slab has < 65536 pixels: 16-bit counters never carry)
+    if (px.tab_in_lds) {
+        for (uint32_t i = tid; i < (R.range + 2) / 2; i += BS) px.s_tab[i] = 0;
+        __syncthreads();
+    }
+    px.greyInfo = A.ibsi ? 0 : A.grey_depth;
+    px.mslope = px.greyInfo > 0 ? (double)px.greyInfo / ((double)R.vmax - 0.) : 0.0;
+    px.sum = 0; px.sumsq = 0;
+    return px;
+}
+
+// The end of a load workgroup: the two sums into the ROI's header (one pair of atomic adds per workgroup), the LDS table into the ROI's
+// table with contiguous atomic adds.
+template <bool P16>
+__device__ __forceinline__ void large_slab_close(const LargeArgs& A, const LargeRoi& R, LargePixel<P16>& px, unsigned char* lds_raw, int tid, int BS)
+{
+    const int lane = tid & 63, wave = tid >> 6, NWV = BS >> 6;
+    unsigned long long* const s_red = (unsigned long long*)(lds_raw + 2ull * A.tab_lds);   // [2 * 16]
+    unsigned long long* const hdr = (unsigned long long*)R.base;
+    const unsigned long long sum = wave_sum_u64(px.sum), sumsq = wave_sum_u64(px.sumsq);
+    if (lane == 0) { s_red[wave] = sum; s_red[16 + wave] = sumsq; }
+    __syncthreads();                                                          // (also: every LDS count of the slab is in)
+    if (tid == 0) {
+        unsigned long long a = 0, b = 0;
+        for (int wv = 0; wv < NWV; wv++) { a += s_red[wv]; b += s_red[16 + wv]; }
+        atomicAdd(&hdr[0], a);
+        atomicAdd(&hdr[1], b);
+    }
+    if (px.tab_in_lds && !(A.dbg & 4)) {
+        const uint16_t* const t16 = (const uint16_t*)px.s_tab;
+        for (uint32_t i = tid; i <= R.range; i += BS) {                       // contiguous adds: a wave covers 256 bytes of the table
+            const uint32_t c = t16[i];
+            if (c) atomicAdd(&px.T[i], c);
+        }
+    }
+}
+
 template <bool P16>
 __global__ __launch_bounds__(1024) void large_load_kernel(const LargeArgs A)
 {
@@ -145,22 +235,11 @@ __global__ __launch_bounds__(1024) void large_load_kernel(const LargeArgs A)
     const uint2 job = A.map_load[blockIdx.x];
     LargeRoi R;
     if (!large_roi(A, job.x, R, true)) return;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, BS = blockDim.x, NWV = BS >> 6;
-    const bool do_int = (A.mask & NYXHIP_FAM_INTENSITY) != 0, do_glcm = (A.mask & NYXHIP_FAM_GLCM) != 0;
-    uint32_t* const s_tab = (uint32_t*)lds_raw;                              // [tab_lds / 2] words of two 16-bit counters
-    unsigned long long* const s_red = (unsigned long long*)(lds_raw + 2ull * A.tab_lds);   // [2 * 16]
-    unsigned long long* const hdr = (unsigned long long*)R.base;
-    uint32_t* const T = (uint32_t*)(R.base + R.L.tab);
-    uint16_t* const flags = (uint16_t*)(R.base + R.L.lvl);
+    const int tid = threadIdx.x, BS = blockDim.x;
     using plane_t = typename std::conditional<P16, uint16_t, uint8_t>::type;
     plane_t* const plane = (plane_t*)(R.base + R.L.plane);
-    const bool tab_in_lds = do_int && R.range < A.tab_lds;                   // (a slab has < 65536 pixels: 16-bit counters never carry)
-    if (tab_in_lds) {
-        for (uint32_t i = tid; i < (R.range + 2) / 2; i += BS) s_tab[i] = 0;
-        __syncthreads();
-    }
-    const int greyInfo = A.ibsi ? 0 : A.grey_depth;
-    const double mslope = greyInfo > 0 ? (double)greyInfo / ((double)R.vmax - 0.) : 0.0;
+    LargePixel<P16> value = large_slab_open<P16>(A, R, lds_raw, tid, BS);
+    const bool do_glcm = value.do_glcm;
     // Slabs are cut in the batch's GLOBAL pixel index, at multiples of four from the group of four that holds the ROI's first pixel:
     // a thread takes four consecutive pixels -- one 16-byte load of intensities, one 8-byte load each of x and y (the arrays of a
     // batch are 16 / 8-byte aligned: vec_ok) -- where a pixel per lane cost three loads per pixel.  The ROI's first and last group
@@ -168,30 +247,11 @@ __global__ __launch_bounds__(1024) void large_load_kernel(const LargeArgs A)
     const uint64_t roi_lo = R.off, roi_hi = R.off + R.n;
     const uint64_t gs = (R.off & ~3ull) + (uint64_t)job.y * A.px_per_wg;      // first global index of the slab (a multiple of four)
     const uint64_t ge = gs + A.px_per_wg < roi_hi ? gs + A.px_per_wg : roi_hi;
-    unsigned long long sum = 0, sumsq = 0;
-    const uint32_t lvl_clip = P16 ? 0xFFFFu : 0xFFu;
     const uint32_t pw_ = R.tr ? R.h : R.w;                                    // cell = major * pw_ + minor: below 2^32 (box sides are 16-bit)
     auto pixel = [&](uint32_t v, uint32_t px, uint32_t py) {
-        sum += v;
-        sumsq += (uint32_t)(v * v);                                           // unsigned-int product, wraps (intensity.cpp:90)
-        if (do_int && !(A.dbg & 2)) {
-            const uint32_t ci = v - R.vmin;
-            if (tab_in_lds) atomicAdd(&s_tab[ci >> 1], 1u << (16 * (ci & 1u)));
-            else if (ci <= R.range) atomicAdd(&T[ci], 1u);
-        }
-        if (do_glcm) {
-            uint32_t lvl = 0;
-            if (v != 0) {                                                      // original intensity 0 is skipped by the scan (glcm.cpp:445)
-                if (greyInfo > 0) {   // matlab binning of a non-zero value: floor(slope v + 1) >= 1 already (the conversion truncates a positive value)
-                    const uint32_t sc = (uint32_t)(mslope * (double)v + 1.0);
-                    lvl = sc > (uint32_t)greyInfo ? (uint32_t)greyInfo : sc;
-                } else
-                    lvl = greyInfo < 0 ? bin_radiomix(v, R.vmin, R.vmax, -greyInfo) : v;
-                if (greyInfo < 0 && lvl <= R.lvl_cap) flags[lvl] = 1;
-            }
-            if (px < R.w && py < R.h && !(A.dbg & 1))
-                plane[(R.tr ? px : py) * pw_ + (R.tr ? py : px)] = (plane_t)(lvl > lvl_clip ? lvl_clip : lvl);
-        }
+        const uint32_t lvl = value(v);
+        if (do_glcm && px < R.w && py < R.h && !(A.dbg & 1))
+            plane[(R.tr ? px : py) * pw_ + (R.tr ? py : px)] = (plane_t)lvl;
     };
     constexpr int kU = 4;
     for (uint64_t gb = gs; gb < ge; gb += 4ull * kU * BS) {
@@ -221,23 +281,85 @@ __global__ __launch_bounds__(1024) void large_load_kernel(const LargeArgs A)
             }
         }
     }
-    sum = wave_sum_u64(sum);
-    sumsq = wave_sum_u64(sumsq);
-    if (lane == 0) { s_red[wave] = sum; s_red[16 + wave] = sumsq; }
-    __syncthreads();                                                          // (also: every LDS count of the slab is in)
-    if (tid == 0) {
-        unsigned long long a = 0, b = 0;
-        for (int wv = 0; wv < NWV; wv++) { a += s_red[wv]; b += s_red[16 + wv]; }
-        atomicAdd(&hdr[0], a);
-        atomicAdd(&hdr[1], b);
-    }
-    if (tab_in_lds && !(A.dbg & 4)) {
-        const uint16_t* const t16 = (const uint16_t*)s_tab;
-        for (uint32_t i = tid; i <= R.range; i += BS) {                       // contiguous adds: a wave covers 256 bytes of the table
-            const uint32_t c = t16[i];
-            if (c) atomicAdd(&T[i], c);
+    large_slab_close<P16>(A, R, value, lds_raw, tid, BS);
+}
+
+// ---- load, dense: one workgroup per slab of consecutive pixels of a dense image (whole-slide mode) ---------------------------------
+// The image is read in its own element type, 16 bytes per lane and load (16 / 8 / 4 pixels); the levels of those pixels are
+// consecutive plane cells -- the plane has the image's layout -- and leave in one vector store.  The head and the tail of a slab that
+// are not 16-byte aligned (a slide of an odd pixel count in a stack, a chunk that starts in the middle of the caller's array) go
+// element by element; where the 16-byte boundaries of the image and of the plane do not coincide, the levels of a load are stored
+// one by one.
+template <typename T, uint32_t NW>
+__device__ __forceinline__ uint32_t dense_value(const uint32_t (&wd)[NW], uint32_t k)
+{
+    if constexpr (sizeof(T) == 4) return wd[k];
+    else if constexpr (sizeof(T) == 2) return (wd[k >> 1] >> (16u * (k & 1u))) & 0xFFFFu;
+    else return (wd[k >> 2] >> (8u * (k & 3u))) & 0xFFu;
+}
+
+template <typename T, bool P16>
+__global__ __launch_bounds__(1024) void large_load_dense_kernel(const LargeArgs A)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
+    if (blockIdx.x >= A.ctr[2]) return;
+    const uint2 job = A.map_load[blockIdx.x];
+    LargeRoi R;
+    if (!large_roi(A, job.x, R, true)) return;
+    const int tid = threadIdx.x, BS = blockDim.x;
+    using plane_t = typename std::conditional<P16, uint16_t, uint8_t>::type;
+    constexpr uint32_t EPV = 16 / sizeof(T);                                  // pixels of a 16-byte load
+    constexpr uint32_t OUTW = EPV * sizeof(plane_t) / 4;                      // 32-bit words their levels fill: 1, 2, 4 or 8
+    constexpr uint32_t OUT_ALIGN = OUTW >= 4 ? 16u : 4u * OUTW;
+    plane_t* const plane = (plane_t*)(R.base + R.L.plane);
+    LargePixel<P16> value = large_slab_open<P16>(A, R, lds_raw, tid, BS);
+    const bool store = value.do_glcm && !(A.dbg & 1);
+    const T* const p = (const T*)A.dense + R.off;
+    const uint64_t s0 = (uint64_t)job.y * A.px_per_wg, s1 = s0 + A.px_per_wg < R.n ? s0 + A.px_per_wg : R.n;   // the slab, in pixels of the image
+    if (s0 < s1) {
+        // [s0, e0) element by element up to the image's first 16-byte boundary, [e0, e1) as vectors, [e1, s1) element by element
+        const uintptr_t a = (uintptr_t)(p + s0);
+        uint64_t head = (a % sizeof(T)) ? s1 - s0 : (uint64_t)(((16u - (uint32_t)(a & 15u)) & 15u) / sizeof(T));
+        if (head > s1 - s0) head = s1 - s0;
+        const uint64_t e0 = s0 + head, nv = (s1 - e0) / EPV, e1 = e0 + nv * EPV;
+        const uint4* const src = (const uint4*)(p + e0);
+        const bool vec_store = ((uintptr_t)(plane + e0) % OUT_ALIGN) == 0;
+        auto vec = [&](const uint4 q, uint64_t i) {
+            const uint32_t wd[4] = {q.x, q.y, q.z, q.w};
+            uint32_t out[OUTW] = {};
+            uint32_t lv[EPV];
+#pragma unroll
+            for (uint32_t k = 0; k < EPV; k++) {
+                lv[k] = value(dense_value<T, 4>(wd, k));
+                if constexpr (P16) out[k >> 1] |= lv[k] << (16u * (k & 1u));
+                else out[k >> 2] |= lv[k] << (8u * (k & 3u));
+            }
+            if (!store) return;
+            plane_t* const d = plane + e0 + i * EPV;
+            if (vec_store) {
+                if constexpr (OUTW == 1) *(uint32_t*)d = out[0];
+                else if constexpr (OUTW == 2) *(uint2*)d = make_uint2(out[0], out[1]);
+                else {
+#pragma unroll
+                    for (uint32_t k = 0; k < OUTW; k += 4) *(uint4*)((uint32_t*)d + k) = make_uint4(out[k], out[k + 1], out[k + 2], out[k + 3]);
+                }
+            } else {
+#pragma unroll
+                for (uint32_t k = 0; k < EPV; k++) d[k] = (plane_t)lv[k];
+            }
+        };
+        for (uint64_t i = tid; i < nv; i += 2ull * BS) {                      // two loads in flight before the first use
+            const bool two = i + BS < nv;
+            const uint4 q0 = src[i];
+            uint4 q1 = make_uint4(0, 0, 0, 0);
+            if (two) q1 = src[i + BS];
+            vec(q0, i);
+            if (two) vec(q1, i + BS);
         }
+        for (uint64_t i = s0 + tid; i < e0; i += BS) { const uint32_t l = value((uint32_t)p[i]); if (store) plane[i] = (plane_t)l; }
+        for (uint64_t i = e1 + tid; i < s1; i += BS) { const uint32_t l = value((uint32_t)p[i]); if (store) plane[i] = (plane_t)l; }
     }
+    large_slab_close<P16>(A, R, value, lds_raw, tid, BS);
 }
 
 // ---- co-occurrence: one workgroup per strip of plane rows ---------------------------------------------------------------------
@@ -609,6 +731,9 @@ int launch_large_features(const LargeArgs& a, void* stream)
             // (dynamic LDS beyond 64 KiB is an opt-in per kernel; the static words of a kernel count against the CU's 160 KiB too)
             const struct { const void* f; int bytes; } k[] = {
                 {(const void*)large_load_kernel<false>, 136 * 1024}, {(const void*)large_load_kernel<true>, 136 * 1024},
+                {(const void*)large_load_dense_kernel<uint8_t, false>, 136 * 1024}, {(const void*)large_load_dense_kernel<uint8_t, true>, 136 * 1024},
+                {(const void*)large_load_dense_kernel<uint16_t, false>, 136 * 1024}, {(const void*)large_load_dense_kernel<uint16_t, true>, 136 * 1024},
+                {(const void*)large_load_dense_kernel<uint32_t, false>, 136 * 1024}, {(const void*)large_load_dense_kernel<uint32_t, true>, 136 * 1024},
                 {(const void*)large_cooc_kernel<false>, 120 * 1024}, {(const void*)large_cooc_kernel<true>, 120 * 1024},
                 {(const void*)large_finish_kernel, 64 * 1024}};
             for (const auto& e : k)
@@ -619,6 +744,14 @@ int launch_large_features(const LargeArgs& a, void* stream)
     hipLaunchKernelGGL(large_prep_kernel, dim3((a.n_list + 255) / 256), dim3(256), 0, st, a);
     const size_t lds_load = 2ull * a.tab_lds + 2 * 16 * 8;
     const uint32_t bs_load = a.px_per_wg / 32u;                              // 32 pixels per thread: 256 / 512 / 1024 threads
+    if (a.dense) {
+        auto dense = [&](auto t) {
+            using T = decltype(t);
+            if (a.plane16) hipLaunchKernelGGL((large_load_dense_kernel<T, true>), dim3(a.cap_load), dim3(bs_load), lds_load, st, a);
+            else hipLaunchKernelGGL((large_load_dense_kernel<T, false>), dim3(a.cap_load), dim3(bs_load), lds_load, st, a);
+        };
+        if (a.dense_dt == NYXHIP_U8) dense(uint8_t{}); else if (a.dense_dt == NYXHIP_U16) dense(uint16_t{}); else dense(uint32_t{});
+    } else
     if (a.plane16) hipLaunchKernelGGL(large_load_kernel<true>, dim3(a.cap_load), dim3(bs_load), lds_load, st, a);
     else hipLaunchKernelGGL(large_load_kernel<false>, dim3(a.cap_load), dim3(bs_load), lds_load, st, a);
     if (a.mask & NYXHIP_FAM_GLCM) {

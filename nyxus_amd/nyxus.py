@@ -254,18 +254,25 @@ class Nyxus:
 
     def featurize_directory(self, intensity_dir: str, label_dir: Optional[str] = None, file_pattern: Optional[str] = ".*",
                             output_type: Optional[str] = "pandas", output_path: Optional[str] = ""):
+        """The files of `intensity_dir` that match `file_pattern`, with the label image of the same name in `label_dir`.
+        `label_dir` None or equal to `intensity_dir`: whole-slide mode, as the reference decides it (singleROI = intensity_dir ==
+        labels_dir, dirs_and_files.cpp:77) -- every file is one ROI with label 1 that covers the whole image (_featurize_slides),
+        `intensity_image` is the joined path.  The reference leaves the row order of that mode to the filesystem and to the completion
+        order of its threads; here the files are taken in SORTED order -- this package's choice."""
         import pandas as pd
         if not os.path.exists(intensity_dir):
             raise IOError(f"Provided intensity image directory '{intensity_dir}' does not exist.")
         if label_dir is not None and not os.path.exists(label_dir):
             raise IOError(f"Provided label image directory '{label_dir}' does not exist.")
-        if label_dir is None:
-            label_dir = intensity_dir
         if output_type not in self._valid_output_types:
             raise ValueError(f"Invalid output type {output_type}. Valid output types are {self._valid_output_types}.")
         if output_type != "pandas":
             raise ValueError("arrowipc / parquet writers are outside the MI355X hot path (SURVEY.md section 8); use 'pandas'")
         rx = re.compile(file_pattern)
+        if label_dir is None or os.path.abspath(label_dir) == os.path.abspath(intensity_dir):
+            # whole-slide mode (see the docstring): one row per file, files in sorted order
+            files = sorted(f for f in os.listdir(intensity_dir) if rx.fullmatch(f) and os.path.isfile(os.path.join(intensity_dir, f)))
+            return self._featurize_slides([os.path.join(intensity_dir, f) for f in files])
         files = sorted(f for f in os.listdir(intensity_dir) if rx.fullmatch(f) and os.path.isfile(os.path.join(label_dir, f)))
         return self._featurize_file_pairs([os.path.join(intensity_dir, f) for f in files], [os.path.join(label_dir, f) for f in files])
 
@@ -311,6 +318,51 @@ class Nyxus:
         df.insert(0, "intensity_image", np.concatenate(names_i) if names_i else np.empty(0, dtype=object))
         return df
 
+    def _whole_slide_refusals(self):
+        """Whole-slide mode serves the families of bits 0-9 (nyxhip_featurize_slides): any other requested code -- the moment classes,
+        the contour-based shape families, the neighbor and the intensity-histogram codes, the latter whatever `ibsi` says -- is an
+        error raised before anything touches the device."""
+        bad = [c for c in self._requested if featureset.FAMILY_OF[c] & ~_abi.FAM_WHOLE_SLIDE]
+        if bad:
+            raise ValueError(f"feature(s) {bad} are not served in whole-slide mode (single_roi=True, or a directory without label images): "
+                             "it serves the intensity, GLCM, GLRLM, GLSZM, NGTDM, GLDZM, GLDM and NGLDM families, GABOR and ZERNIKE2D")
+
+    def _featurize_slides(self, intensity_files: list):
+        """Whole-slide mode (nyxhip_featurize_slides): every file is one ROI with label 1 that covers the whole image; consecutive
+        slides of equal shape and element type share a call.  Rows in input order: [intensity_image = the path as given,
+        mask_image = "", ROI_label = 1, t_index = 0, features...] (output_2_buffer.cpp:182-185).  With `gpu_devices` the call runs on
+        the first context only."""
+        import pandas as pd
+        from . import tiff_ingest
+        self._whole_slide_refusals()
+        cols, sel = self._columns()
+        blocks = []
+
+        def flush(stack):
+            if not stack:
+                return
+            table = self._context().featurize_slides_host(np.stack(stack), self._mask, self._settings, max_device_bytes=self._device_budget())
+            _lib.load().nyxhip_finalize_table(table.ctypes.data, table.shape[0], table.shape[1], table.shape[1], C.c_double(self._settings.soft_nan))
+            blocks.append(table[:, sel])
+
+        stack = []
+        for f in intensity_files:
+            I = tiff_ingest.read_tiff(f)
+            if I.dtype not in (np.uint8, np.uint16, np.uint32):
+                I = I.astype(np.uint32)
+            if stack and (I.shape != stack[0].shape or I.dtype != stack[0].dtype or len(stack) * I.nbytes > (1 << 30)):
+                flush(stack)
+                stack = []
+            stack.append(I)
+        flush(stack)
+        n = len(intensity_files)
+        df = pd.DataFrame(np.concatenate(blocks) if blocks else np.zeros((0, len(cols))), columns=cols)
+        df.insert(0, "t_index", np.zeros(n))
+        df.insert(0, "ROI_label", np.ones(n, np.uint32))
+        df.insert(0, "mask_image", np.asarray([""] * n, dtype=object))
+        df.insert(0, "intensity_image", np.asarray([str(f) for f in intensity_files], dtype=object))
+        return df
+
     @staticmethod
     def to_csv(df, path: str) -> None:
         """Writes a feature DataFrame in the format of the reference's CSV writer (save_features_2_csv,
@@ -332,7 +384,8 @@ class Nyxus:
 
     def featurize_files(self, intensity_files: list, mask_files: list, single_roi: bool, output_type: Optional[str] = "pandas",
                         output_path: Optional[str] = ""):
-        """Image file pairs passed as lists (reference nyxus.py:524-593)."""
+        """Image file pairs passed as lists (reference nyxus.py:524-593).  single_roi=True: whole-slide mode -- every intensity file is
+        one ROI with label 1 that covers the whole image, `mask_files` is ignored and may be None (_featurize_slides)."""
         if intensity_files is None:
             raise IOError("The list of intensity file paths is empty")
         if mask_files is None and not single_roi:
@@ -341,8 +394,10 @@ class Nyxus:
             raise ValueError(f"Invalid output type {output_type}. Valid output types are {self._valid_output_types}")
         if output_type != "pandas":
             raise ValueError("arrowipc / parquet writers are outside the MI355X hot path (SURVEY.md section 8); use 'pandas'")
-        if single_roi:
-            raise ValueError("single-ROI (whole-slide) featurization is outside the MI355X hot path (SURVEY.md section 8)")
+        if single_roi:                                   # whole-slide mode: mask_files is not read
+            if len(intensity_files) == 0:
+                raise ValueError("The list of intensity file paths is empty")
+            return self._featurize_slides(list(intensity_files))
         if len(intensity_files) != len(mask_files):
             raise ValueError("intensity_files and mask_files must have the same length")
         return self._featurize_file_pairs(list(intensity_files), list(mask_files))
