@@ -417,6 +417,52 @@ int nyxhip_ih_tiles(nyxhip_ctx* ctx, const nyxhip_tiles* tiles, const nyxhip_set
 int nyxhip_featurize_slides(nyxhip_ctx* ctx, const nyxhip_tiles* slides, uint32_t family_mask,
                             const nyxhip_settings* s, double* out_table, size_t out_ld);
 
+/* ---- image quality: focus score and saturation ---------------------------------------
+ * Four of the six codes of the reference's FeatureIMQ (featureset.h:920-931), the classes behind its ImageQuality Python class
+ * (reduce_trivial_rois.cpp:388-412, :631-654): FocusScoreFeature (features/focus_score.cpp:188-282) and SaturationFeature
+ * (features/saturation.cpp:74-95).  They live in an enum of their own, so the class has entries and an output table
+ * [n_roi x NYXHIP_IMQ_COLS] of its own, like the neighbor and intensity-histogram classes; nyxhip_n_columns / nyxhip_column_name do not
+ * know it.  Columns, in enum order: FOCUS_SCORE, LOCAL_FOCUS_SCORE, MAX_SATURATION, MIN_SATURATION.
+ *
+ * Everything is taken over the ROI's dense plane P (bbox_h rows, bbox_w columns): the intensity at every cloud pixel and 0 at every
+ * other cell of the box (LR::aux_image_matrix) -- the background takes part.  With n = bbox_w * bbox_h and
+ * L = P[y-1][x] + P[y+1][x] + P[y][x-1] + P[y][x+1] - 4 P[y][x] (cells outside the plane are 0):
+ *   FOCUS_SCORE        the population variance of L over all n cells
+ *   LOCAL_FOCUS_SCORE  tiles of M = bbox_h / 2 rows and N = bbox_w / 2 columns at (y0, x0), y0 in {0, M, ..} while y0 < bbox_h - M and
+ *                      x0 likewise (the reference's loop bound, as it is): each tile's own Laplacian (zeros outside the TILE) and
+ *                      population variance; the sum of the tile variances / 4.  A box with a side of 1 makes the reference's loop
+ *                      run for ever: settings.soft_nan here, the other three columns as defined.
+ *   MAX_SATURATION     #(P == max P) / n
+ *   MIN_SATURATION     #(P == min P) / n, and 0 when min P == max P.  An ROI that does not fill its box has min P = 0.
+ * An ROI without pixels or with an empty box has four times settings.soft_nan.  NaN / inf are not replaced (nyxhip_finalize_table).
+ * The two saturation columns have the reference's bits.  The sums behind the focus columns are exact integers (the sum of L in 64 bits,
+ * of L^2 in 128), so they agree with the reference's fp64 sums to rounding, and a row has the same bits whatever shares its call.
+ * WIDTH: the 64-bit sum of L cannot overflow while 4 * max_inten * n < 2^63.  An ROI (or slide) beyond that bound is
+ * NYXHIP_ERR_UNSUPPORTED; nothing wraps silently.
+ * NOT SERVED, and why:
+ *   POWER_SPECTRUM_SLOPE  features/power_spectrum.cpp:168-175 bins every FFT output by floor(sqrt(value)) + 1 -- the value, not its
+ *                         radius -- and :85-90 index raw_radii (max(rows, cols) entries) with indices up to the padded size: a
+ *                         discontinuous function of floating-point FFT outputs with an out-of-bounds read, which no tolerance pins.
+ *   SHARPNESS             features/sharpness.cpp:200-205 "transposes back" with a sequential in-place swap loop: the identity for a
+ *                         square box, a shape-dependent scramble for any other, w * h dependent steps per ROI; vetted against nothing. */
+#define NYXHIP_IMQ_COLS 4
+int nyxhip_imq_column_name(int col, char* buf, size_t buf_len);
+
+/* Reads px_offset, x, y, inten, bbox_w, bbox_h, min_inten, max_inten of the batch (host or device memory, like nyxhip_ih_batch;
+ * batch->max_px / max_bbox_area are hints as everywhere).  min_inten / max_inten must be the cloud's extrema.  Synchronous. */
+int nyxhip_imq_batch(nyxhip_ctx* ctx, const nyxhip_batch* batch, const nyxhip_settings* s,
+                     double* out_table /* [n_roi x 4] */, size_t out_ld);
+/* The tile path (label scan, ROI assembly, chunks under max_device_bytes) with these classes as the reducer; rows in the (tile, label)
+ * order of nyxhip_featurize_tiles_v2, outputs as there. */
+int nyxhip_imq_tiles(nyxhip_ctx* ctx, const nyxhip_tiles* tiles, const nyxhip_settings* s,
+                     uint32_t* out_labels, uint32_t* out_tile_index, uint64_t max_rows,
+                     double* out_table, size_t out_ld, uint64_t* n_roi_out);
+/* Whole-slide mode under the contract of nyxhip_featurize_slides: `label` must be NULL, inten_dtype U8 / U16 / U32, chunks under
+ * max_device_bytes, one row per slide, n_tiles == 0 is NYXHIP_OK, a side of 0 or above 65534 is NYXHIP_ERR_UNSUPPORTED.  The slides are
+ * read in place (no cloud, no plane).  Row t has the bits of nyxhip_imq_batch on the equivalent one-ROI batch. */
+int nyxhip_imq_slides(nyxhip_ctx* ctx, const nyxhip_tiles* slides, const nyxhip_settings* s,
+                      double* out_table, size_t out_ld);
+
 /* ---- measurement hooks -------------------------------------------------------
  * Average device time (ms) per featurize call since the last nyxhip_timing_reset(),
  * measured with hipEvents recorded on the launch stream around EVERYTHING the call

@@ -131,6 +131,15 @@ enum class Feature2D : int {
     _COUNT_
 };
 
+// The image-quality codes (featureset.h:920-931): an enum of their own whose values continue behind the other feature enums, so that they
+// index the same LR::fvals.  All six are named, as in the reference; FocusScoreFeature and SaturationFeature serve four of them.
+// POWER_SPECTRUM_SLOPE and SHARPNESS have no class here (include/nyxhip.h says why).
+enum class FeatureIMQ : int {
+    FOCUS_SCORE = (int)Feature2D::_COUNT_, LOCAL_FOCUS_SCORE, POWER_SPECTRUM_SLOPE, MAX_SATURATION, MIN_SATURATION, SHARPNESS,
+    _COUNT_,
+    _FIRST_ = FOCUS_SCORE
+};
+
 // ---- settings (feature_settings.h:6-54) ----------------------------------------------------------
 union FeatureSetting { bool bval; int ival; double rval; };
 typedef std::vector<FeatureSetting> Fsettings;
@@ -168,7 +177,7 @@ public:
     PixIntens aux_min = (std::numeric_limits<PixIntens>::max)(), aux_max = 0;
     AABB aabb;
     std::vector<std::vector<double>> fvals;
-    void initialize_fvals() { fvals.assign((size_t)Feature2D::_COUNT_, std::vector<double>(1, 0.0)); }   // roi_cache.cpp:105-110
+    void initialize_fvals() { fvals.assign((size_t)FeatureIMQ::_COUNT_, std::vector<double>(1, 0.0)); }   // roi_cache.cpp:105-110
     // phase-1 bookkeeping of one pixel (feed_pixel_2_metrics, pixel_feed.cpp:19-43 + feed_pixel_2_cache :71-74)
     void feed_pixel(StatsInt x, StatsInt y, PixIntens i)
     {
@@ -186,8 +195,12 @@ struct Dataset { std::vector<SlideProps> dataset_props; };
 // ---- feature-set bits (featureset.h FeatureSet) ------------------------------------------------------
 class FeatureSet {
 public:
-    FeatureSet() : bits((size_t)Feature2D::_COUNT_, false) {}
+    FeatureSet() : bits((size_t)FeatureIMQ::_COUNT_, false) {}
     void enableFeature(Feature2D f) { bits[(size_t)f] = true; }
+    void enableFeature(FeatureIMQ f) { bits[(size_t)f] = true; }
+    void enableFeatures(const std::initializer_list<FeatureIMQ>& F) { for (auto f : F) bits[(size_t)f] = true; }
+    bool isEnabled(FeatureIMQ f) const { return bits[(size_t)f]; }
+    bool anyEnabled(const std::initializer_list<FeatureIMQ>& F) const { for (auto f : F) if (bits[(size_t)f]) return true; return false; }
     void enableFeatures(const std::initializer_list<Feature2D>& F) { for (auto f : F) bits[(size_t)f] = true; }
     bool isEnabled(Feature2D f) const { return bits[(size_t)f]; }
     bool anyEnabled(const std::initializer_list<Feature2D>& F) const { for (auto f : F) if (bits[(size_t)f]) return true; return false; }
@@ -509,6 +522,74 @@ public:
     }
 };
 
+// FocusScoreFeature (features/focus_score.h) and SaturationFeature (features/saturation.h): the two image-quality classes, over
+// nyxhip_imq_batch, which reads the pixel cloud, the box and LR::aux_min / aux_max.  One batch call yields the four columns; each class
+// keeps its own two.  A box with a side of 1 has SOFTNAN as LOCAL_FOCUS_SCORE (the reference's loop does not end on it).
+inline std::vector<double> imq_batch_table(size_t start, size_t end, std::vector<int>* labels, std::unordered_map<int, LR>* roiData, const Fsettings& fst)
+{
+    nyxhip_settings s = make_settings(fst);
+    const size_t n = end - start;
+    std::vector<uint32_t> bw(n), bh(n), mn(n), mx(n), inten;
+    std::vector<uint16_t> x, y;
+    std::vector<uint64_t> off(n + 1, 0);
+    for (size_t i = 0; i < n; i++) {
+        LR& r = (*roiData)[(*labels)[start + i]];
+        bw[i] = r.raw_pixels.empty() ? 0u : (uint32_t)r.aabb.get_width(); bh[i] = r.raw_pixels.empty() ? 0u : (uint32_t)r.aabb.get_height();
+        mn[i] = r.aux_min; mx[i] = r.aux_max;
+        for (const Pixel2& p : r.raw_pixels) { x.push_back((uint16_t)(p.x - r.aabb.get_xmin())); y.push_back((uint16_t)(p.y - r.aabb.get_ymin())); inten.push_back(p.inten); }
+        off[i + 1] = inten.size();
+        if (r.fvals.size() < (size_t)FeatureIMQ::_COUNT_) r.fvals.resize((size_t)FeatureIMQ::_COUNT_, std::vector<double>(1, 0.0));
+    }
+    nyxhip_batch b{};
+    b.n_roi = n; b.px_offset = off.data(); b.x = x.data(); b.y = y.data(); b.inten = inten.data();
+    b.bbox_w = bw.data(); b.bbox_h = bh.data(); b.min_inten = mn.data(); b.max_inten = mx.data();
+    b.memory = NYXHIP_MEM_HOST;
+    std::vector<double> table(n * (size_t)NYXHIP_IMQ_COLS);
+    nyxhip_ctx* ctx = context();
+    if (nyxhip_imq_batch(ctx, &b, &s, table.data(), (size_t)NYXHIP_IMQ_COLS) != NYXHIP_OK)
+        throw std::runtime_error(std::string("nyxhip_imq_batch: ") + nyxhip_last_error(ctx));
+    return table;
+}
+
+// CLASS: the class name; A, B: its two codes; CA, CB: their columns in the table of nyxhip_imq_batch
+#define NYXHIP_IMQ_CLASS(CLASS, A, B, CA, CB)                                                                                                  \
+    class CLASS : public FeatureMethod {                                                                                                      \
+    public:                                                                                                                                   \
+        CLASS() : FeatureMethod(#CLASS) { provided.push_back((int)FeatureIMQ::A); provided.push_back((int)FeatureIMQ::B); }                   \
+        static bool required(const FeatureSet& fs) { return fs.anyEnabled({FeatureIMQ::A, FeatureIMQ::B}); }                                  \
+        void calculate(LR& r, const Fsettings& s) override                                                                                    \
+        {                                                                                                                                     \
+            std::vector<int> L{r.label};                                                                                                      \
+            std::unordered_map<int, LR> data;                                                                                                 \
+            data[r.label] = r;                                                                                                                \
+            reduce(0, 1, &L, &data, s, Dataset());                                                                                            \
+            held = data[r.label].fvals;                                                                                                       \
+        }                                                                                                                                     \
+        void save_value(std::vector<std::vector<double>>& fv) override                                                                        \
+        {                                                                                                                                     \
+            if (held.empty()) throw std::runtime_error(feature_info + ": save_value() before calculate()");                                   \
+            if (fv.size() < (size_t)FeatureIMQ::_COUNT_) fv.resize((size_t)FeatureIMQ::_COUNT_, std::vector<double>(1, 0.0));                 \
+            fv[(int)FeatureIMQ::A] = held[(int)FeatureIMQ::A]; fv[(int)FeatureIMQ::B] = held[(int)FeatureIMQ::B];                             \
+        }                                                                                                                                     \
+        static void extract(LR& r, const Fsettings& s) { CLASS f; f.calculate(r, s); f.save_value(r.fvals); }                                 \
+        static void reduce(size_t start, size_t end, std::vector<int>* labels, std::unordered_map<int, LR>* roiData, const Fsettings& fst,    \
+                           const Dataset&)                                                                                                    \
+        {                                                                                                                                     \
+            if (end <= start) return;                                                                                                         \
+            const std::vector<double> table = imq_batch_table(start, end, labels, roiData, fst);                                              \
+            for (size_t i = 0; i < end - start; i++) {                                                                                        \
+                LR& r = (*roiData)[(*labels)[start + i]];                                                                                     \
+                r.fvals[(int)FeatureIMQ::A].assign(1, table[i * (size_t)NYXHIP_IMQ_COLS + CA]);                                               \
+                r.fvals[(int)FeatureIMQ::B].assign(1, table[i * (size_t)NYXHIP_IMQ_COLS + CB]);                                               \
+            }                                                                                                                                 \
+        }                                                                                                                                     \
+        static void parallel_process_1_batch(size_t start, size_t end, std::vector<int>* labels, std::unordered_map<int, LR>* roiData,        \
+                                             const Fsettings& fst, const Dataset& ds) { reduce(start, end, labels, roiData, fst, ds); }       \
+    };
+NYXHIP_IMQ_CLASS(FocusScoreFeature, FOCUS_SCORE, LOCAL_FOCUS_SCORE, 0, 1)
+NYXHIP_IMQ_CLASS(SaturationFeature, MAX_SATURATION, MIN_SATURATION, 2, 3)
+#undef NYXHIP_IMQ_CLASS
+
 // runParallel (parallel.h:23-42): the GPU batch is the parallel unit, so the slices run back to back on the
 // caller's thread -- same observable contract (every label of [0, datasetSize) reduced on return).
 typedef void (*functype)(size_t, size_t, std::vector<int>*, std::unordered_map<int, LR>*, const Fsettings&, const Dataset&);
@@ -550,6 +631,10 @@ inline void reduce_trivial_rois_manual(std::vector<int>& PendingRoisLabels, std:
     if (mask) reduce_range(mask, 0, PendingRoisLabels.size(), &PendingRoisLabels, &roiData, s, ds);
     if (IntensityHistogramFeatures::required(fs))                  // a call of its own: the class has no bit of the family mask
         IntensityHistogramFeatures::reduce(0, PendingRoisLabels.size(), &PendingRoisLabels, &roiData, s, ds);
+    if (FocusScoreFeature::required(fs))                           // reduce_trivial_rois.cpp:388-393
+        FocusScoreFeature::reduce(0, PendingRoisLabels.size(), &PendingRoisLabels, &roiData, s, ds);
+    if (SaturationFeature::required(fs))                           // :401-405
+        SaturationFeature::reduce(0, PendingRoisLabels.size(), &PendingRoisLabels, &roiData, s, ds);
 }
 
 } // namespace NyxusHip

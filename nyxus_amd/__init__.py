@@ -7,5 +7,6 @@ C ABI of ``include/nyxhip.h``.
 """
 from . import _abi  # noqa: F401
 from .nyxus import Nyxus  # noqa: F401
+from .imq import ImageQuality  # noqa: F401
 
 __version__ = "0.1.0"

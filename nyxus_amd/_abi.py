@@ -61,6 +61,7 @@ FAM_WHOLE_SLIDE = 0x3FF     # the families nyxhip_featurize_slides serves: bits 
 MAX_GLCM_ANGLES = 4
 NEIGHBOR_COLS = 9            # NYXHIP_NEIGHBOR_COLS: the table of nyxhip_neighbors_batch / _tiles (no family bit: the class relates the ROIs of an image)
 IH_COLS = 46                 # NYXHIP_IH_COLS: the table of nyxhip_ih_batch / _tiles (no family bit: every bit of the mask is spoken for)
+IMQ_COLS = 4          # NYXHIP_IMQ_COLS: FOCUS_SCORE, LOCAL_FOCUS_SCORE, MAX_SATURATION, MIN_SATURATION
 MAX_GABOR_FILTERS = 16
 
 

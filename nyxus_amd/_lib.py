@@ -31,6 +31,7 @@ ABI_SYMBOLS = [
     "nyxhip_neighbor_column_name", "nyxhip_neighbors_batch", "nyxhip_neighbors_tiles",
     "nyxhip_ih_column_name", "nyxhip_ih_batch", "nyxhip_ih_tiles",
     "nyxhip_featurize_slides",
+    "nyxhip_imq_column_name", "nyxhip_imq_batch", "nyxhip_imq_tiles", "nyxhip_imq_slides",
 ]
 
 
@@ -130,6 +131,16 @@ def load() -> C.CDLL:
         lib.nyxhip_ih_tiles.argtypes = [C.c_void_p, P(_abi.Tiles), P(_abi.Settings), C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_size_t,
                                         P(C.c_uint64)]
         lib.nyxhip_ih_tiles.restype = C.c_int
+    if hasattr(lib, "nyxhip_imq_batch"):         # (absent from older builds of the ABI selected through NYXHIP_LIB for A/B runs)
+        lib.nyxhip_imq_column_name.argtypes = [C.c_int, C.c_char_p, C.c_size_t]
+        lib.nyxhip_imq_column_name.restype = C.c_int
+        lib.nyxhip_imq_batch.argtypes = [C.c_void_p, P(_abi.Batch), P(_abi.Settings), C.c_void_p, C.c_size_t]
+        lib.nyxhip_imq_batch.restype = C.c_int
+        lib.nyxhip_imq_tiles.argtypes = [C.c_void_p, P(_abi.Tiles), P(_abi.Settings), C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_size_t,
+                                         P(C.c_uint64)]
+        lib.nyxhip_imq_tiles.restype = C.c_int
+        lib.nyxhip_imq_slides.argtypes = [C.c_void_p, P(_abi.Tiles), P(_abi.Settings), C.c_void_p, C.c_size_t]
+        lib.nyxhip_imq_slides.restype = C.c_int
     if hasattr(lib, "nyxhip_featurize_slides"):  # (absent from older builds of the ABI selected through NYXHIP_LIB for A/B runs)
         lib.nyxhip_featurize_slides.argtypes = [C.c_void_p, P(_abi.Tiles), C.c_uint32, P(_abi.Settings), C.c_void_p, C.c_size_t]
         lib.nyxhip_featurize_slides.restype = C.c_int
@@ -175,6 +186,19 @@ def ih_column_names() -> List[str]:
         rc = lib.nyxhip_ih_column_name(i, buf, 128)
         if rc != 0:
             raise NyxHipError(rc, f"intensity-histogram column {i}")
+        out.append(buf.value.decode())
+    return out
+
+
+def imq_column_names() -> List[str]:
+    """The 4 columns of nyxhip_imq_batch / _tiles / _slides, enum order."""
+    lib = load()
+    buf = C.create_string_buffer(128)
+    out = []
+    for i in range(_abi.IMQ_COLS):
+        rc = lib.nyxhip_imq_column_name(i, buf, 128)
+        if rc != 0:
+            raise NyxHipError(rc, f"image-quality column {i}")
         out.append(buf.value.decode())
     return out
 
@@ -318,6 +342,66 @@ class Context:
         labels = np.zeros(n.value, np.uint32); tiles = np.zeros(n.value, np.uint32); table = np.empty((n.value, ncol), np.float64)
         self._check(self._lib.nyxhip_fetch_result(self._h, labels.ctypes.data, tiles.ctypes.data, table.ctypes.data, ncol))
         return tiles, labels, table
+
+    def imq_host(self, batch: _abi.HostBatch, s: _abi.Settings) -> np.ndarray:
+        """The image-quality columns [n_roi x 4] of a host batch (nyxhip_imq_batch); NaN / inf are left in place."""
+        out = np.empty((batch.n_roi, _abi.IMQ_COLS), np.float64)
+        cb = batch.c_struct()
+        self._check(self._lib.nyxhip_imq_batch(self._h, C.byref(cb), C.byref(s), out.ctypes.data, _abi.IMQ_COLS))
+        return out
+
+    def imq_device(self, cb: _abi.Batch, s: _abi.Settings, out_ptr: int, ld: int):
+        """Device pointers in ``cb`` (px_offset, x, y, inten, bbox_w, bbox_h, min_inten, max_inten) and a device table; synchronous
+        (nyxhip_imq_batch)."""
+        self._check(self._lib.nyxhip_imq_batch(self._h, C.byref(cb), C.byref(s), C.c_void_p(out_ptr), ld))
+
+    def imq_tiles_host(self, inten: np.ndarray, label: np.ndarray, s: _abi.Settings, max_device_bytes: int = 0):
+        """The image-quality columns of a stack [n_tiles, H, W] of host tiles (nyxhip_imq_tiles).  Returns (tile_index, labels,
+        table [n_roi x 4]) in the (tile, label) row order of featurize_tiles_host."""
+        if inten.shape != label.shape or inten.ndim != 3:
+            raise ValueError("stacks must be 3-D arrays [n_tiles, H, W] of the same shape")
+        dt = {np.dtype(np.uint8): _abi.U8, np.dtype(np.uint16): _abi.U16, np.dtype(np.uint32): _abi.U32}
+        inten = np.ascontiguousarray(inten if inten.dtype in dt else inten.astype(np.uint32))
+        label = np.ascontiguousarray(label if label.dtype in dt else label.astype(np.uint32))
+        nt, h, w = inten.shape
+        ncol = _abi.IMQ_COLS
+        if nt == 0:
+            return np.zeros(0, np.uint32), np.zeros(0, np.uint32), np.zeros((0, ncol))
+        t = _abi.Tiles()
+        t.inten = inten.ctypes.data; t.label = label.ctypes.data
+        t.inten_dtype = dt[inten.dtype]; t.label_dtype = dt[label.dtype]
+        t.width = w; t.height = h; t.n_tiles = nt; t.memory = _abi.MEM_HOST; t.slide_mode = _abi.SLIDE_MONTAGE
+        t.max_device_bytes = int(max_device_bytes)
+        n = C.c_uint64(0)
+        self._check(self._lib.nyxhip_imq_tiles(self._h, C.byref(t), C.byref(s), None, None, 0, None, 0, C.byref(n)))
+        labels = np.zeros(n.value, np.uint32); tiles = np.zeros(n.value, np.uint32); table = np.empty((n.value, ncol), np.float64)
+        self._check(self._lib.nyxhip_fetch_result(self._h, labels.ctypes.data, tiles.ctypes.data, table.ctypes.data, ncol))
+        return tiles, labels, table
+
+    def imq_slides_host(self, inten: np.ndarray, s: _abi.Settings, max_device_bytes: int = 0) -> np.ndarray:
+        """Whole-slide mode (nyxhip_imq_slides): a stack [n, H, W] of uint8 / uint16 / uint32 host slides, every slide one ROI that
+        covers the whole image.  Returns the table [n, 4], rows in input order; NaN / inf are left in place."""
+        dt = {np.dtype(np.uint8): _abi.U8, np.dtype(np.uint16): _abi.U16, np.dtype(np.uint32): _abi.U32}
+        if inten.ndim != 3 or inten.dtype not in dt:
+            raise ValueError("slides must be a 3-D array [n, H, W] of uint8, uint16 or uint32")
+        inten = np.ascontiguousarray(inten)
+        n, h, w = inten.shape
+        out = np.empty((n, _abi.IMQ_COLS), np.float64)
+        t = _abi.Tiles()
+        t.inten = inten.ctypes.data; t.label = None
+        t.inten_dtype = dt[inten.dtype]; t.width = w; t.height = h; t.n_tiles = n; t.memory = _abi.MEM_HOST
+        t.max_device_bytes = int(max_device_bytes)
+        self._check(self._lib.nyxhip_imq_slides(self._h, C.byref(t), C.byref(s), out.ctypes.data, _abi.IMQ_COLS))
+        return out
+
+    def imq_slides_device(self, inten_ptr: int, dtype: int, n: int, h: int, w: int, s: _abi.Settings, out_ptr: int, ld: int, max_device_bytes: int = 0):
+        """The same entry on device memory: `inten_ptr` is a device array [n, h, w] of element type `dtype` (_abi.U8 / U16 / U32),
+        `out_ptr` a device table [n x ld] of doubles.  Synchronous."""
+        t = _abi.Tiles()
+        t.inten = inten_ptr; t.label = None
+        t.inten_dtype = dtype; t.width = w; t.height = h; t.n_tiles = n; t.memory = _abi.MEM_DEVICE
+        t.max_device_bytes = int(max_device_bytes)
+        self._check(self._lib.nyxhip_imq_slides(self._h, C.byref(t), C.byref(s), C.c_void_p(out_ptr), ld))
 
     def featurize_device_async(self, cb: _abi.Batch, mask: int, s: _abi.Settings, out_ptr: int, ld: int, origin_x_ptr: Optional[int] = None,
                                origin_y_ptr: Optional[int] = None):

@@ -8,6 +8,7 @@
 //   nyxhip_api.hip       context life cycle, the batch entry points, timing, launch report
 //   nyxhip_neighbors.hip the neighbor entries: column names, the launches over a device-resident batch, nyxhip_neighbors_batch
 //   nyxhip_ih.hip        the intensity-histogram entries: column names, the launches over a device-resident batch, nyxhip_ih_batch
+//   nyxhip_imq.hip       the image-quality entries: column names, the launches over a device-resident batch, nyxhip_imq_batch / _slides
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -31,6 +32,7 @@
 #include "roi_circle.h"
 #include "roi_neighbors.h"
 #include "roi_ih.h"
+#include "roi_imq.h"
 
 // One hipMalloc allocation, grow-only.  hipFree waits for the device's work by itself; the stream handed to reserve() states which
 // work the site knows to be using the old block.
@@ -162,6 +164,7 @@ struct nyxhip_ctx {
     DeferredBufs d_caliper;            // roi_caliper.hip: boxes wider than the LDS column table
     DeferredBufs d_chords;             // roi_chords.hip: plane beyond LDS, or zero-intensity pixels
     DeferredBufs d_erosion;            // roi_erosion.hip: two bit planes beyond the LDS planes
+    DeferredBufs d_imq;                // roi_imq.hip (nyxhip_imq.hip): intensity planes beyond the LDS plane
     // neighbor entries (roi_neighbors.hip): geometry table + candidate counts and offsets | candidate lists, minima, flags
     DevBuf d_nb_geo;
     DevBuf d_nb_cand;
@@ -296,8 +299,14 @@ int neighbors_device(nyxhip_ctx* ctx, const nyxhip_batch* b, const uint32_t* d_o
 // Reads px_offset, inten, min_inten, max_inten of the batch.  max_px: the largest ROI (0: not known).
 int ih_settings_check(nyxhip_ctx* ctx, const nyxhip_settings* s);      // NYXHIP_ERR_UNSUPPORTED beyond kIhMaxBins
 int ih_device(nyxhip_ctx* ctx, const nyxhip_batch* b, const nyxhip_settings* s, double* d_out, size_t ld, uint32_t max_px);
+// nyxhip_imq.hip: the kImqCols image-quality columns of a device-resident batch -> d_out [n_roi x ld] (enqueued on the context's stream; the
+// boxes beyond kImqLdsCells cost one read-back).  max_area: the largest box in cells (0: not known).
+int imq_device(nyxhip_ctx* ctx, const nyxhip_batch* b, const nyxhip_settings* s, double* d_out, size_t ld, uint32_t max_area);
+int imq_check_status(nyxhip_ctx* ctx);                                 // check_status with this class's reading of NYXHIP_ERR_UNSUPPORTED
+extern const char* const kImqWidthMessage;
 // the tile path's reducers besides the family kernels (the neighbor_distance slot of tiles_run / tiles_chunk): > 0 the neighbor class at that
-// distance, kTilesReducerIh the intensity-histogram class
+// distance, kTilesReducerIh the intensity-histogram class, kTilesReducerImq the image-quality classes
 constexpr int32_t kTilesReducerIh = -1;
+constexpr int32_t kTilesReducerImq = -2;
 
 } // namespace nyxhip
