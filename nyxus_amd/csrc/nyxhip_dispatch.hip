@@ -1327,7 +1327,6 @@ int make_layout(uint32_t mask, const nyxhip_settings* s, int n_cols, uint32_t ma
     L.out = off;                               // (the kernel writes its output row in place: no staging copy)
     L.red = off; off = align16(off + 8u * kWaves * 8);
     L.stat = off; off = align16(off + 8u * 16);
-    L.lb100 = off; off = align16(off + 4u * 104);
     uint32_t n_hist = (uint32_t)abs(s->grey_depth);
     L.lbc = off; off = align16(off + 4u * (do_int ? n_hist + 8 : 8));
     const uint32_t fixed = off;               // everything that does not scale with the ROI
@@ -1394,6 +1393,7 @@ int make_layout(uint32_t mask, const nyxhip_settings* s, int n_cols, uint32_t ma
         if (8ull * L.sort_cap > cap) { why = "ROI pixel count " + std::to_string(max_px) + " exceeds the LDS-resident sort buffers"; return NYXHIP_ERR_ROI_TOO_LARGE; }
         L.radix = off; off = align16(off + (L.radix_k16 ? 0u : 4u * L.sort_cap) + 4u * (kWaves * 256 + kWaves) + 16);
     }
+    const uint32_t cnt_end = off;                         // (the first-moment prefixes go here once the GLCM regions are known: below)
     if (do_glcm && L.g16) {
         const uint32_t ng = (uint32_t)s->grey_depth, cellsw = ((ng + 1) * ((ng + 3) & ~1u)) / 2;     // rows 0..ng of an even pitch (roi_features.hip, G16 block)
         L.ng_cap = ng; L.app = 4;
@@ -1438,11 +1438,28 @@ int make_layout(uint32_t mask, const nyxhip_settings* s, int n_cols, uint32_t ma
         L.gscr = goff; goff = align16(goff + 8u * (25u * ng + 128));
         if (goff > off) off = goff;
     }
+    if (L.cnt16 && !spill) {
+        // First-moment prefixes of the counting table (roi_features_body: the robust statistics are read off the count and the
+        // first-moment prefix tables), behind the table: one word per G = 2^fm_shift entries, G = 8 .. 512 (the engine scans 512
+        // entries per wave and step, eight per lane; a lookup walks the G / 8 lane chunks of its word).  The smallest G that costs
+        // the launch no workgroup per CU (eight at the most: 64-VGPR builds of four waves) -- the benchmark ROI, a 4096-entry
+        // table: G = 8, 2 KiB, 20 192 B of the 20 480 B that eight workgroups leave each; a 16384-entry table next to a small
+        // ROI: G = 16.  Like [val | cnt] the words are dead after the intensity block: the GLCM regions may lie over them.
+        const uint32_t lds_cu = (uint32_t)roi_features_max_lds();
+        auto wgs = [&](uint32_t total) -> uint32_t { return std::min<uint32_t>(8u, lds_cu / (total ? total : 1u)); };
+        uint32_t sh = 3, with = off;
+        for (;; sh++) {
+            with = std::max(off, align16(cnt_end + 4u * ((L.count_cap + (1u << sh) - 1u) >> sh)));
+            if (sh == 9 || wgs(with) >= wgs(off)) break;
+        }
+        L.fm = cnt_end; L.fm_shift = sh;
+        off = with;
+    }
     if (L.dense8) {
         // 8-bit plane launches keep the plane at the START of the carve-out (the kernel then needs no base add per store):
         // [fixed | plane | ...] becomes [plane | fixed | ...], everything behind the two stays where it is
         const uint32_t dsz = align16(plane_bytes);            // the plane's bytes (dense8 implies GLCM; L.dense is 16-byte aligned)
-        L.out += dsz; L.red += dsz; L.stat += dsz; L.lb100 += dsz; L.lbc += dsz;
+        L.out += dsz; L.red += dsz; L.stat += dsz; L.lbc += dsz;
         L.dense = 0;
         if (L.g16) L.gscr = 0;
     }

@@ -861,7 +861,6 @@ __device__ __forceinline__ void roi_features_body(const RoiArgs& A, const uint64
     auto reg = [&](uint32_t o) -> unsigned char* { return (GS && o < A.L.gs_lds_bytes) ? lds_raw + o : lds + o; };
     double* s_red = (double*)reg(A.L.red);
     double* s_stat = (double*)reg(A.L.stat);
-    uint32_t* s_lb100 = (uint32_t*)reg(A.L.lb100);
     uint32_t* s_lbc = (uint32_t*)reg(A.L.lbc);
     uint32_t* s_val = (uint32_t*)(lds + A.L.val);
     using dense_t = typename std::conditional<D8, uint8_t, uint16_t>::type;
@@ -1306,6 +1305,16 @@ __device__ __forceinline__ void roi_features_body(const RoiArgs& A, const uint64
         const uint32_t Q = ((range + 1 + NW * 512 - 1) / (NW * 512)) * 512;
         uint32_t* const s_woff = (uint32_t*)(s_stat + 8);   // [4] prefix offsets of the waves' table quarters (kept in LDS: as
                                                             // registers they were live across the whole intensity block and spilled)
+        // FUSED: the central sums are taken in one sweep behind the percentiles, and the robust statistics need no sweep at all:
+        // they are read off two prefix tables over the value domain, the counts C(i) and the first moments F(i) = sum_{j <= i} j c_j,
+        // which the counting engine leaves behind (see the lookups behind the percentiles).  C16 LDS launches only.
+#ifdef NYX_NO_FUSED      // diagnostic builds (A/B timing)
+        constexpr bool FUSED = false;
+#else
+        constexpr bool FUSED = C16 && !GS;
+#endif
+        uint32_t* const s_fm = (uint32_t*)(lds + B->L.fm);  // [count_cap >> fm_shift] first-moment prefixes of the table (FUSED; read late: see KView)
+        uint32_t* const s_foff = (uint32_t*)(s_stat + 12);  // [5] first-moment offsets of the waves' table quarters | the whole table's first moment
         if (use_count) {
             // ---- counting engine: per-wave inclusive prefix sums over s_cnt, in place (each
             // lane owns 4 consecutive entries of a 256-entry tile: one 16-byte LDS access each
@@ -1329,6 +1338,13 @@ __device__ __forceinline__ void roi_features_body(const RoiArgs& A, const uint64
                 uint32_t inv = 0xFFFFu - (base + 8u * (uint32_t)lane);
                 uint4* src = (uint4*)((uint16_t*)s_cnt + base + 8u * (uint32_t)lane);
                 uint32_t i = base + 8u * (uint32_t)lane;
+                // FUSED: the first moments ride along.  A lane's share is m = sum_q (i + q) c_q = i T + sum_q q c_q (four 16-bit dot
+                // products on the packed words and one 24-bit multiply-add; below 2^30: n < 65536, index < 16384), scanned like T;
+                // the EXCLUSIVE prefix of a lane's eight entries goes to s_fm, one word per G = 2^fm_shift entries (the lanes whose
+                // first entry is a multiple of G store), relative to the wave's quarter like the counts.
+                typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
+                uint32_t fcarry = 0;
+                const uint32_t fm_sh = FUSED ? B->L.fm_shift : 0u, fm_mask = (1u << fm_sh) - 1u;
                 for (uint32_t t = 0; t < Q; t += 512, i += 512, inv -= 512, src += 64) {
                     uint4 pk = make_uint4(0, 0, 0, 0);
                     const bool live = i <= range;
@@ -1348,7 +1364,20 @@ __device__ __forceinline__ void roi_features_body(const RoiArgs& A, const uint64
                     if (live)
                         *src = make_uint4(o0, o1, o2, o3);
                     carry += readlane63(sc);
+                    if (FUSED) {
+                        uint32_t qc = __builtin_amdgcn_udot2(__builtin_bit_cast(u16x2, pk.x), __builtin_bit_cast(u16x2, 0x00010000u), 0u, false);
+                        qc = __builtin_amdgcn_udot2(__builtin_bit_cast(u16x2, pk.y), __builtin_bit_cast(u16x2, 0x00030002u), qc, false);
+                        qc = __builtin_amdgcn_udot2(__builtin_bit_cast(u16x2, pk.z), __builtin_bit_cast(u16x2, 0x00050004u), qc, false);
+                        qc = __builtin_amdgcn_udot2(__builtin_bit_cast(u16x2, pk.w), __builtin_bit_cast(u16x2, 0x00070006u), qc, false);
+                        const uint32_t m = mad24(i, T, qc);
+                        const uint32_t fs = wave_scan_u32(m);
+                        if (live && (i & fm_mask) == 0)
+                            s_fm[i >> fm_sh] = fcarry + fs - m;
+                        fcarry += readlane63(fs);
+                    }
                 }
+                if (FUSED && lane == 0)
+                    s_red[wave * 8 + 3] = (double)fcarry;
 #pragma unroll
                 for (int q = 1; q < 8; q++) kk[q] -= (uint32_t)q;      // (a key with count 0 never wins: the ROI has a pixel)
                 const uint32_t key = wave_max_u32(max(max(max(kk[0], kk[1]), max(kk[2], kk[3])), max(max(kk[4], kk[5]), max(kk[6], kk[7]))));
@@ -1411,6 +1440,11 @@ __device__ __forceinline__ void roi_features_body(const RoiArgs& A, const uint64
                 }
                 const uint32_t woff1 = (uint32_t)s_red[0], woff2 = woff1 + (NW > 1 ? (uint32_t)s_red[8] : 0u), woff3 = woff2 + (NW > 1 ? (uint32_t)s_red[16] : 0u);
                 s_woff[0] = 0; s_woff[1] = woff1; s_woff[2] = woff2; s_woff[3] = woff3;
+                if (FUSED) {                          // the same for the first moments, and their total: the sum of all offsets x = v - vmin
+                    const uint32_t f1 = (uint32_t)s_red[3], f2 = f1 + (NW > 1 ? (uint32_t)s_red[8 + 3] : 0u), f3 = f2 + (NW > 1 ? (uint32_t)s_red[16 + 3] : 0u);
+                    s_foff[0] = 0; s_foff[1] = f1; s_foff[2] = f2; s_foff[3] = f3;
+                    s_foff[4] = f3 + (NW > 1 ? (uint32_t)s_red[24 + 3] : 0u);
+                }
                 s_stat[S_MODE] = (double)(vmin + mi);
             }
             grp_sync<GS, NW>();
@@ -1434,15 +1468,26 @@ __device__ __forceinline__ void roi_features_body(const RoiArgs& A, const uint64
             const uint32_t wq = (uint32_t)(i >= Q) + (uint32_t)(i >= 2 * Q) + (uint32_t)(i >= 3 * Q);   // i / Q without the division
             return (C16 ? (uint32_t)((const uint16_t*)s_cnt)[i] : s_cnt[i]) + s_woff[wq];
         };
+        // F(p) = sum_{j <= p} j c_j, the first-moment prefix (FUSED; p <= range), by the eight lanes of a group (sub = 0 .. 7; every
+        // lane of the group returns it): the stored prefix in front of p's word of s_fm, the offset of its quarter, and the
+        // entries from the word's first one up to p -- c_j = C(j) - C(j - 1) from the scanned counts of the same quarter (a word's
+        // G entries never straddle two: Q is a multiple of 512) -- lane sub takes the entries sub, sub + 8, ..
+        auto fm_at = [=](uint32_t p, uint32_t sub) -> uint32_t {
+            const uint32_t fm_sh = B->L.fm_shift;
+            const uint32_t wq = (uint32_t)(p >= Q) + (uint32_t)(p >= 2 * Q) + (uint32_t)(p >= 3 * Q);
+            const uint32_t q0 = mul24(wq, Q);                       // first entry of the quarter: nothing of the quarter lies in front of it
+            const uint16_t* const c16 = (const uint16_t*)s_cnt;
+            uint32_t part = 0;
+            for (uint32_t j = ((p >> fm_sh) << fm_sh) + sub; j <= p; j += 8) {
+                const uint32_t cj = c16[j], pj = j == q0 ? 0u : (uint32_t)c16[j == 0 ? 0 : j - 1];
+                part = mad24(j, cj - pj, part);
+            }
+            return grp8_sum(part) + s_fm[p >> fm_sh] + s_foff[wq];
+        };
 
         // central sums over the LDS-resident values (intensity.cpp:102-109, :177-183; M2..M4 of moments.h:53-74 equal the
-        // plain central sums).  C16 launches take them in ONE fused sweep together with the robust statistics, after the
-        // percentiles (see below); a blank ROI (all zeros) has every sum equal to zero and needs no sweep at all.
-#ifdef NYX_NO_FUSED      // diagnostic builds (A/B timing)
-        constexpr bool FUSED = false;
-#else
-        constexpr bool FUSED = C16 && !GS;
-#endif
+        // plain central sums).  FUSED launches take them in one sweep after the percentiles (see below); a blank ROI (all zeros)
+        // has every sum equal to zero and needs no sweep at all.
         double acc[6] = {0, 0, 0, 0, 0, 0};
         if (!FUSED || blank) {
             if (!blank) {
@@ -1601,37 +1646,72 @@ __device__ __forceinline__ void roi_features_body(const RoiArgs& A, const uint64
                 const double p10 = readlane_f64(pv, 8), p90 = readlane_f64(pv, 32);
                 const double p25 = DEFER ? 0.0 : readlane_f64(pv, 16), p75 = DEFER ? 0.0 : readlane_f64(pv, 24);
                 const uint32_t hi_v = (uint32_t)__builtin_amdgcn_readlane((int)xv, 48), lo_v = (uint32_t)__builtin_amdgcn_readlane((int)xv, 56);
+                // median (histogram.h:268-287)
+                const double median = (n & 1) ? (double)hi_v : (double)(uint32_t)(hi_v + lo_v) / 2.0;
                 if (lane == 0) {
                     if (!DEFER)                        // (deferred: derived from the P25 and P75 of the row)
                         close_quartiles(RowColumns{o}, p25, p75);
-                    s_stat[S_P10] = p10;
-                    s_stat[S_P90] = p90;
-                    if (FUSED) {
-                        // bounds of the robust statistics in the offset domain and the populations around them (see the fused sweep):
-                        // derived once, here, instead of by every thread of the workgroup
-                        uint32_t lox = 0x80000000u, span = 0;                   // empty range unless the bounds say otherwise (NaN: empty)
-                        if (p10 <= p90 && p90 >= (double)vmin && p10 <= (double)vmax) {
-                            const double cl = ceil(p10), fl = floor(p90);
-                            const uint32_t lo_b = cl <= (double)vmin ? vmin : (uint32_t)cl, hi_b = fl >= (double)vmax ? vmax : (uint32_t)fl;
-                            if (lo_b <= hi_b) { lox = lo_b - vmin; span = hi_b - lo_b; }
-                        }
-                        const bool empty = span == 0 && lox == 0x80000000u;
-                        uint32_t* const s_rob = (uint32_t*)(s_stat + 6);
-                        s_rob[0] = lox;
-                        s_rob[1] = span;
-                        s_rob[2] = (empty || lox == 0) ? 0u : cum(lox - 1);       // values below the range
-                        s_rob[3] = empty ? 0u : cum(lox + span);                  // values up to its upper end
-                    }
-                    // median (histogram.h:268-287)
-                    double median = (n & 1) ? (double)hi_v : (double)(uint32_t)(hi_v + lo_v) / 2.0;
                     o[I_MEDIAN] = median;
                     o[I_MODE] = s_stat[S_MODE];
-                    s_stat[S_MEDIAN] = median;
-                    if (FUSED) {   // 2 (median - vmin) as an integer, and #(x <= floor(median)) for the half-integer correction of the MAD
-                        const uint32_t m2x = (uint32_t)((median - (double)vmin) * 2.0);
-                        uint32_t* const s_med = (uint32_t*)(s_stat + 10);
-                        s_med[0] = m2x;
-                        s_med[1] = (m2x & 1u) ? cum(m2x >> 1) : 0u;
+                    if (!FUSED) {                      // (read by the sweeps of the other engines)
+                        s_stat[S_P10] = p10;
+                        s_stat[S_P90] = p90;
+                        s_stat[S_MEDIAN] = median;
+                    }
+                }
+                if (FUSED) {
+                    // ---- ROBUST_MEAN, MEDIAN_ABSOLUTE_DEVIATION and ROBUST_MEAN_ABSOLUTE_DEVIATION (intensity.cpp:139-149,
+                    // histogram.h:90-112) without a pass over the values: exact integers from the two prefix tables, in offsets
+                    // x = v - vmin.  With lox = ceil(p10) - vmin, hix = floor(p90) - vmin (a value is an integer:
+                    // p10 <= a <= p90  <=>  lox <= x <= hix), kmed = floor(median) - vmin and F(-1) = C(-1) = 0:
+                    //   K  = C(hix) - C(lox - 1)  values lie inside the range,  Sx = F(hix) - F(lox - 1)  is their sum;
+                    //   sum |x - kmed| over ALL values = [kmed C(kmed) - F(kmed)] + [(Xtot - F(kmed)) - kmed (n - C(kmed))],
+                    //     Xtot = F(range); both brackets are >= 0 (the values up to kmed, the values above it);
+                    //   sum over the range of |K x - Sx| = 2 (Sx n1 - K S1),  n1 = C(t) - C(lox - 1), S1 = F(t) - F(lox - 1),
+                    //     t = floor(Sx / K) in [lox, hix]: the terms up to t are Sx - K x >= 0, and the signed sum over the whole range is 0.
+                    // n < 65536 and x < 16384: F < 2^30 and the first two lines fit 32 bits; Sx n1 and K S1 are below 2^46.
+                    // The range is empty unless the bounds say otherwise (NaN: empty).
+                    uint32_t lox = 0x80000000u, span = 0;
+                    if (p10 <= p90 && p90 >= (double)vmin && p10 <= (double)vmax) {
+                        const double cl = ceil(p10), fl = floor(p90);
+                        const uint32_t lo_b = cl <= (double)vmin ? vmin : (uint32_t)cl, hi_b = fl >= (double)vmax ? vmax : (uint32_t)fl;
+                        if (lo_b <= hi_b) { lox = lo_b - vmin; span = hi_b - lo_b; }
+                    }
+                    const bool empty = span == 0 && lox == 0x80000000u, has_lo = !empty && lox != 0;
+                    const uint32_t hix = lox + span;
+                    const uint32_t m2x = (uint32_t)((median - (double)vmin) * 2.0), kmed = m2x >> 1;   // the median is kmed or kmed + 1/2
+                    // eight lanes per point: group 0 looks up lox - 1, group 1 hix, the others kmed
+                    const uint32_t pt = g == 0 ? (has_lo ? lox - 1 : 0u) : g == 1 ? (empty ? 0u : hix) : kmed;
+                    const uint32_t fv = fm_at(pt, (uint32_t)sub), cv = cum(pt);
+                    const uint32_t n_below = has_lo ? (uint32_t)__builtin_amdgcn_readlane((int)cv, 0) : 0u;       // values below the range
+                    const uint32_t F_lo = has_lo ? (uint32_t)__builtin_amdgcn_readlane((int)fv, 0) : 0u;
+                    const uint32_t n_upto = empty ? 0u : (uint32_t)__builtin_amdgcn_readlane((int)cv, 8);       // values up to its upper end
+                    const uint32_t F_hi = empty ? 0u : (uint32_t)__builtin_amdgcn_readlane((int)fv, 8);
+                    const uint32_t Ck = (uint32_t)__builtin_amdgcn_readlane((int)cv, 16), Fk = (uint32_t)__builtin_amdgcn_readlane((int)fv, 16);
+                    const uint32_t K = n_upto - n_below, n_above = n - n_upto, Sxu = F_hi - F_lo;
+                    const uint32_t sadk_u = (kmed * Ck - Fk) + ((s_foff[4] - Fk) - kmed * (n - Ck));
+                    unsigned long long adin_u = 0;
+                    if (K != 0) {
+                        // (one IEEE division of two integers below 2^30: a quotient that is no integer is at least 1 / K away from one)
+                        const uint32_t t = min((uint32_t)((double)Sxu / (double)K), range);
+                        const uint32_t ft = (uint32_t)__builtin_amdgcn_readfirstlane((int)fm_at(t, (uint32_t)sub));
+                        const uint32_t n1 = (uint32_t)__builtin_amdgcn_readfirstlane((int)cum(t)) - n_below, S1 = ft - F_lo;
+                        adin_u = 2ull * ((unsigned long long)Sxu * n1 - (unsigned long long)K * S1);
+                    }
+                    if (lane == 0) {
+                        const uint32_t cle = (m2x & 1u) ? Ck : 0u;         // #(x <= floor(median)): the half-integer correction of the MAD
+                        const double sadk = (double)sadk_u, adin = (double)adin_u, Sx = (double)Sxu;
+                        if (DEFER) {
+                            uint32_t* const rw = (uint32_t*)rec;
+                            rec[CR_SADK] = sadk;
+                            rec[CR_ADIN] = adin;
+                            rw[CR_W_FAST32] = 0u;
+                            *(uint4*)(rw + CR_W_NBELOW) = make_uint4(n_below, n_above, K, Sxu);
+                            *(uint4*)(rw + CR_W_LOX) = make_uint4(lox, hix, m2x, cle);
+                        } else {
+                            close_robust_mad(RowColumns{o}, sadk, m2x, cle, K, Sx, vmin, dn);
+                            close_robust_rmad(RowColumns{o}, adin, false, K, Sx, lox, hix, n_below, n_above);
+                        }
                     }
                 }
             }
@@ -1658,25 +1738,9 @@ __device__ __forceinline__ void roi_features_body(const RoiArgs& A, const uint64
             grp_sync<GS, NW>();
             STAMP(7);
 
-            // robust mean over p10..p90 (intensity.cpp:139-149 == histogram.h:90-101)
-            const double p10 = s_stat[S_P10], p90 = s_stat[S_P90], median = s_stat[S_MEDIAN];
             if (FUSED) {
-                // ---- one sweep over the resident values: central sums (fp64, fused multiply-adds: the sums are tolerance-class,
-                // DESIGN 4.6) + the robust statistics in exact integer arithmetic on the 16-bit offsets x = v - vmin:
-                //   a >= p10 && a <= p90  <=>  lox <= x <= hix  with  lox = ceil(p10) - vmin, hix = floor(p90) - vmin  (a is an integer)
-                //   sum |a - median| = sum |2x - m2x| / 2,  m2x = 2 (median - vmin)  (an integer: the median is k or k + 1/2)
-                // Every partial sum fits 32 bits: n < 65536 and x < 16384 in a C16 launch.
-                const uint32_t* const s_rob = (const uint32_t*)(s_stat + 6);     // written by the percentile / median lanes above
-                const uint32_t lox = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_rob[0]), span = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_rob[1]);
-                const uint32_t hix = lox + span;
-                const uint32_t m2x = (uint32_t)__builtin_amdgcn_readfirstlane((int)((const uint32_t*)(s_stat + 10))[0]);
-                const uint32_t kmed = m2x >> 1;                 // floor(median) - vmin; the median is kmed or kmed + 1/2
-                // The in-range tests cost nothing per value: x is CLAMPED to [lox, hix] (one v_med3_u32) and summed as it is; the
-                // values below / above the range contribute lox / hix each, and how many there are is in the cumulative table:
-                //   sum over [p10, p90] of x  =  sum of clamp(x)  -  #below * lox  -  #above * hix.
-                // Likewise sum |x - median| = sum |x - kmed| (one v_sad_u32, accumulating) + the half-integer correction
-                //   (#(x <= kmed) - #(x > kmed)) / 2  when the median is kmed + 1/2.
-                uint32_t sx = 0, sad = 0;
+                // ---- the one sweep over the resident values (16-bit offsets x = v - vmin): the six central sums (fp64, fused
+                // multiply-adds: the sums are tolerance-class).  The robust statistics came from the prefix tables above.
                 const double meanx = mean - (double)vmin;       // deviations are taken in the offset domain: d = x - (mean - vmin)
                 auto px1 = [&](uint32_t x) {
                     const double d = (double)x - meanx;
@@ -1688,8 +1752,6 @@ __device__ __forceinline__ void roi_features_body(const RoiArgs& A, const uint64
                     const double d4 = d2 * d2;
                     acc[4] = __builtin_fma(d4, d, acc[4]);
                     acc[5] = __builtin_fma(d4, d2, acc[5]);
-                    sx += med3_u32_ss(x, lox, hix);
-                    asm("v_sad_u32 %0, %1, %2, %0" : "+v"(sad) : "v"(x), "s"(kmed));
                 };
                 // the trip count is wave-uniform (n / 256 full trips, then the lanes below n % 256 once more): the loop control
                 // runs on the scalar unit and costs no vector instruction per value
@@ -1702,15 +1764,7 @@ __device__ __forceinline__ void roi_features_body(const RoiArgs& A, const uint64
                 }
                 if ((uint32_t)tid < n_rem)
                     px1(pv[n_full * BS]);
-                // workgroup totals: the two integer sums through 32-bit DPP wave sums (slots 6, 7 of the exchange area), the six
-                // fp64 sums through the transposed wave sum (slots 0..5); one barrier pair for all eight
-                {
-                    const uint32_t wsx = wave_sum_t<uint32_t>(sx), wsad = wave_sum_t<uint32_t>(sad);
-                    if (lane == 0) {
-                        s_red[wave * 8 + 6] = (double)wsx;
-                        s_red[wave * 8 + 7] = (double)wsad;
-                    }
-                }
+                // workgroup totals: the six fp64 sums through the transposed wave sum (slots 0..5 of the exchange area)
                 {
                     double t[8];
 #pragma unroll
@@ -1720,84 +1774,28 @@ __device__ __forceinline__ void roi_features_body(const RoiArgs& A, const uint64
                         s_red[wave * 8 + (lane >> 3)] = tot;
                 }
                 grp_sync<GS, NW>();
-                // every thread needs the in-range sum (sweep 2) and the population of [p10, p90] (read off the cumulative table);
-                // the other totals are read by the one lane that derives the outputs -- no barrier follows: the next exchange
-                // (sweep 2's) goes through its own scratch (the percentile bounds, dead by now)
-                const uint32_t n_below = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_rob[2]);
-                const uint32_t n_upto = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_rob[3]);
-                const uint32_t K = n_upto - n_below, n_above = n - n_upto;                 // (wave-uniform: the products below run on the scalar unit)
-                const uint32_t Sx_all = (uint32_t)xw_pairs<NW>(s_red, 6);
-                const uint32_t Sxu = (uint32_t)__builtin_amdgcn_readfirstlane((int)(Sx_all - n_below * lox - n_above * hix));   // < 2^30
-                const double Sx = (double)Sxu;
+                // the totals are read by the lanes that derive the outputs (deferring builds: a lane per total, into the record; the
+                // robust scalars are in it already, so the flag may rise)
                 if (DEFER) {
-                    // the totals of the eight exchange slots leave on a lane each (slots 6 and 7 hold integers: exact in either order),
-                    // the scalars of the robust statistics on lane 0
-                    if (tid < 8)
+                    if (tid < 6)
                         rec[CR_ACC + tid] = xw_chain<NW>(s_red, tid);
-                    if (tid == 0) {
-                        uint32_t* const rw = (uint32_t*)rec;
-                        *(uint4*)(rw + CR_W_NBELOW) = make_uint4(n_below, n_above, K, Sxu);
-                        *(uint4*)(rw + CR_W_LOX) = make_uint4(lox, hix, m2x, ((const uint32_t*)(s_stat + 10))[1]);
-                    }
-                } else
-                if (tid == 0) {
-                    double a6[6];
-#pragma unroll
-                    for (int k = 0; k < 6; k++) {
-                        a6[k] = xw_chain<NW>(s_red, k);
-                        asm volatile("" : "+v"(a6[k]) :: "memory");   // one total at a time: 28 reads in flight (or their adds sunk into the output code) would spill
-                    }
-                    const double sadk = xw_pairs<NW>(s_red, 7);
-                    const uint32_t cle = ((const uint32_t*)(s_stat + 10))[1];
-                    close_central<CovDiv::ieee>(RowColumns{o}, a6, n, dn, mean, blank);
-                    close_robust_mad(RowColumns{o}, sadk, m2x, cle, K, Sx, vmin, dn);
-                }
-                // sweep 2: robust MAD about mean1090 = S / K (histogram.h:102-112): sum |a - S/K| = sum |K x - Sx| / K, exact in integers.
-                // The clamp again: sum over ALL values of |K clamp(x) - Sx|, minus what the values outside contribute
-                // (#below |K lox - Sx| + #above |K hix - Sx|) -- three instructions per value.  32-bit lane sums need
-                // trips * K * span < 2^32 (|K x - Sx| <= K span inside the range); otherwise the masked 64-bit form.
-                const uint32_t Ku = K;
-                const bool fast32 = (unsigned long long)(n_full + 1) * Ku * (span + 1ull) < (1ull << 32);
-                double ad1[1];
-                if (fast32) {
-                    uint32_t ad = 0;
-                    auto px2 = [&](uint32_t x) {
-                        const uint32_t t = mul_u24_su(med3_u32_ss(x, lox, hix), Ku);      // < 2^30
-                        asm("v_sad_u32 %0, %1, %2, %0" : "+v"(ad) : "v"(t), "s"(Sxu));
-                    };
-                    {
-                        uint32_t k = 0;
-                        for (; k + 1 < n_full; k += 2) { px2(pv[k * BS]); px2(pv[(k + 1) * BS]); }
-                        if (k < n_full) px2(pv[k * BS]);
-                    }
-                    if ((uint32_t)tid < n_rem)
-                        px2(pv[n_full * BS]);
-                    ad1[0] = (double)ad;
-                } else {
-                    unsigned long long ad = 0;
-                    auto px2 = [&](uint32_t x) {
-                        const uint32_t t = (uint32_t)__umul24(Ku, x);            // < 2^30
-                        uint32_t dlt;
-                        asm("v_sad_u32 %0, %1, %2, 0" : "=v"(dlt) : "v"(t), "s"(Sxu));   // |t - Sx| in one instruction
-                        ad += (x - lox) <= span ? dlt : 0u;
-                    };
-                    for (uint32_t k = 0; k < n_full; k++)
-                        px2(pv[k * BS]);
-                    if ((uint32_t)tid < n_rem)
-                        px2(pv[n_full * BS]);
-                    ad1[0] = (double)ad;
-                }
-                block_sum<1, GS, NW>(ad1, (double*)s_lb100, tid);
-                if (DEFER) {
-                    if (tid == 0) {
-                        rec[CR_ADIN] = ad1[0];
-                        ((uint32_t*)rec)[CR_W_FAST32] = fast32 ? 1u : 0u;
+                    if (tid == 0)
                         B->close_flag[roi] = 1u;
+                } else {
+                    if (tid == 0) {
+                        double a6[6];
+#pragma unroll
+                        for (int k = 0; k < 6; k++) {
+                            a6[k] = xw_chain<NW>(s_red, k);
+                            asm volatile("" : "+v"(a6[k]) :: "memory");   // one total at a time: 28 reads in flight (or their adds sunk into the output code) would spill
+                        }
+                        close_central<CovDiv::ieee>(RowColumns{o}, a6, n, dn, mean, blank);
                     }
-                } else
-                if (tid == 0)
-                    close_robust_rmad(RowColumns{o}, ad1[0], fast32, K, Sx, lox, hix, n_below, n_above);
+                    grp_sync<GS, NW>();                // (the GLCM block may open with an exchange through s_red)
+                }
             } else {
+            // robust mean over p10..p90 (intensity.cpp:139-149 == histogram.h:90-101)
+            const double p10 = s_stat[S_P10], p90 = s_stat[S_P90], median = s_stat[S_MEDIAN];
             // sweep 1: sum and count inside [p10, p90], and the median absolute deviation (it only needs the median)
             double rb[3] = {0, 0, 0};
             for (uint32_t i = tid; i < n; i += BS) {

@@ -81,7 +81,8 @@ struct LdsLayout {
     uint32_t out;      // double[n_cols]       staged output row
     uint32_t red;      // double[kWaves*8]     cross-wave reduction scratch
     uint32_t stat;     // double[16]           block-wide scalars
-    uint32_t lb100;    // uint32[104]          lower bounds of the 100 percentile bins
+    uint32_t fm;       // uint32[count_cap >> fm_shift]  first-moment prefixes of the counting table, one per 2^fm_shift entries
+                       //                      (16-bit-table LDS launches: the robust statistics of roi_features_body; else unused)
     uint32_t lbc;      // uint32[n_hist+8]     lower bounds of the n-bin histogram
     uint32_t val;      // uint32[sort_cap]     intensities (sorted in place by the sort engine)
     uint32_t cnt;      // uint32[count_cap]    counting table over [min, max] -> prefix sums
@@ -93,6 +94,7 @@ struct LdsLayout {
     uint32_t sort_cap;   // >= max_px (a power of two when the sort engine may run)
     uint32_t count_cap;  // intensity ranges below this use the counting engine (0 = never)
     uint32_t cnt16;      // 1: 16-bit counting table (every ROI of the launch has < 65536 pixels)
+    uint32_t fm_shift;   // log2 of the table entries per word of `fm` (3 .. 9; make_layout)
     uint32_t dense8;     // 1: 8-bit binned plane (grey depth <= 254; only together with cnt16 and the split GLCM launch)
     uint32_t dense_cap;  // >= max bbox area
     uint32_t ng_cap;     // max GLCM matrix order held in LDS
@@ -132,9 +134,10 @@ constexpr int kCloseRec = 16;           // doubles per record (128 B)
 enum {
     CR_TOT = 0, CR_TOTSQ,               // sum and sum of squares of the intensities
     CR_ACC,                             // [6] central sums: sum |d|, d^2 .. d^6
-    CR_SADK = 9,                        // sum |x - kmed| over all values (slot 8: the clamped sum, not used)
-    CR_ADIN,                            // sweep 2: sum |K clamp(x) - Sx| before the out-of-range correction
-    CR_W_FAST32 = 22,                   // 32-bit words from here on: sweep 2 ran in its 32-bit form (the correction applies)
+    CR_SADK = 9,                        // sum |x - kmed| over all values (slot 8: not used)
+    CR_ADIN,                            // sum |K x - Sx| over the values inside [lox, hix]
+    CR_W_FAST32 = 22,                   // 32-bit words from here on: CR_ADIN runs over ALL values clamped to the range (the correction
+                                        // of close_robust_rmad applies); the feature kernel writes 0
     CR_W_NBELOW = 24, CR_W_NABOVE, CR_W_K, CR_W_SXU,
     CR_W_LOX, CR_W_HIX, CR_W_M2X, CR_W_CLE
 };
