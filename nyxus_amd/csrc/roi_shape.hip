@@ -1150,6 +1150,8 @@ __global__ __launch_bounds__(NW * 64) void roi_zernike_kernel(const ShapeArgs A)
     // The same sweep stages the cloud in LDS (when it fits), so that the moment sweep below is not one HBM round trip per
     // pixel and lane.
     const bool staged = npx <= A.L.zern_px_cap;
+    // Range of the 64-bit sums: a term (x + 1) v is below 2^16 * 2^32 = 2^48, so sum (x + 1) v passes 2^64 only beyond about 2^16 pixels
+    // of 32-bit data at coordinates near 65535 (sum v: beyond 2^32 pixels).  Equal to the reference's double sums while below 2^53.
     unsigned long long m00 = 0, m10 = 0, m01 = 0;
     for_each_cloud_pixel<kBlk>(A.inten + off, A.x + off, A.y + off, npx, tid, [&](uint32_t i, uint32_t vi, uint32_t xi, uint32_t yi) {
         if (staged) { s_xy[i] = xi | (yi << 16); s_v[i] = vi; }
@@ -1179,8 +1181,8 @@ __global__ __launch_bounds__(NW * 64) void roi_zernike_kernel(const ShapeArgs A)
     // combinations of the 30 complex sums  T[m][j] = sum_pixels f / r * (r^2)^j * (x - i y)^(m + 1),  j = 0 .. (9 - m) / 2:
     // per pixel one complex power recurrence (4 operations per m), five weights and two multiply-adds per sum -- ~125 vector
     // instructions instead of ~290 (the radial recurrence, a product and two multiply-adds per (n, m)).  The combination runs once
-    // per ROI; its cancellation (coefficients up to 630) costs three of fp64's sixteen digits: 1e-13 against the per-pixel recurrence, the moments
-    // carry a 1e-5 tolerance (the reference's regression vector: 1e-9 absolute).
+    // per ROI; its cancellation (coefficients up to 630) is what the unit of tests/zernike_ref.py measures: 2^-52 (n + 1) / pi sum |coefficient|.
+    // Held to 32 + ceil(npx / 256) such units of the exact value (tests/test_zernike_gpu.py; observed: below one unit).
     constexpr int kZT = 30;                             // pairs (m, j): m = 0 .. 9, j = 0 .. (9 - m) / 2
     double TR[kZT], TI[kZT];
 #pragma unroll
