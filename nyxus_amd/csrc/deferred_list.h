@@ -7,6 +7,7 @@
 // (no device code crosses a unit) | in a host unit (behind nyxhip_ctx.h): the steps build / count / chunks.
 #pragma once
 #include <stdint.h>
+#include "knobs.h"
 
 namespace nyxhip {
 
@@ -71,7 +72,7 @@ template <class Launch>
 int deferred_chunks(nyxhip_ctx* ctx, const char* site, const DeferredList& dl, uint64_t stride_bytes, size_t budget, DevBuf& ws, hipStream_t st,
                     Launch&& launch)
 {
-    const uint64_t n = dl.hdr[0], chunk = deferred_chunk(n, stride_bytes, large_budget(budget));
+    const uint64_t n = dl.hdr[0], chunk = deferred_chunk(n, stride_bytes, knob::large_budget(budget));
     if (chunk == 0) return fail(ctx, NYXHIP_ERR_HIP, std::string(site) + ": listed ROIs with an empty workspace");
     HIP_TRY(ctx, ws.reserve((size_t)(stride_bytes * chunk), st));
     for (uint64_t o = 0; o < n; o += chunk)

@@ -32,6 +32,7 @@ int nyxhip_init(int device, nyxhip_ctx** out_ctx)
 {
     if (!out_ctx) return NYXHIP_ERR_INVALID_ARG;
     *out_ctx = nullptr;
+    (void)knob::at_start();   // the per-process knobs are what the environment says now, at the first context (knobs.h)
     int n = 0;
     hipError_t e = hipGetDeviceCount(&n);
     if (e != hipSuccess || n <= 0)
@@ -45,7 +46,7 @@ int nyxhip_init(int device, nyxhip_ctx** out_ctx)
         delete ctx;
         return fail(nullptr, NYXHIP_ERR_HIP, "failed to create the device context");
     }
-    if (getenv("NYXHIP_STAMPS")) { // diagnostic builds only; never set in production
+    if (knob::stamps()) { // diagnostic builds only; never set in production
         if (ctx->d_stamps.reserve(32 * sizeof(unsigned long long), nullptr) == hipSuccess)
             (void)hipMemset(ctx->d_stamps.p, 0, 32 * sizeof(unsigned long long));
     }

@@ -223,9 +223,8 @@ int nyxhip::launch_contour_families(nyxhip_ctx* ctx, const nyxhip_batch* b, uint
     // A batch with boxes beyond the LDS plane sends those to a wave per ROI over a global workspace (a few hundred waves, ~10 ms of
     // latency for the heavy-tailed batch): with other families in the call the whole moments chain goes to a lane of its own and
     // runs beside them (enqueued last, dependent only on the batch).  Its scratch is the lane's, not the main stream's.
-    static const bool no_mom_lane = [] { const char* e = getenv("NYXHIP_NO_MOM_LANE"); return e && *e && *e != '0'; }();   // A/B knob
     const bool big_boxes = (uint64_t)kContourWaves * (((uint64_t)max_area + 4ull * max_side + 4 + 15) & ~15ull) > (uint64_t)roi_features_max_lds();
-    const bool on_lane = allow_lane && !no_mom_lane && big_boxes && (mask & ~kTailFams) && ctx->lane_fork;
+    const bool on_lane = allow_lane && !knob::no_mom_lane() && big_boxes && (mask & ~kTailFams) && ctx->lane_fork;
     if (on_lane)
         if (int lrc = use_lane(ctx, nyxhip_ctx::kMomLane, &st)) return lrc;
     DevBuf& spill = on_lane ? ctx->lane_buf[nyxhip_ctx::kMomLane] : ctx->d_spill;

@@ -23,6 +23,7 @@
 #include <utility>
 
 #include "../../include/nyxhip.h"
+#include "knobs.h"
 #include "roi_kernel.h"
 #include "roi_radial.h"
 #include "roi_outline.h"
@@ -271,7 +272,6 @@ int fail(nyxhip_ctx* ctx, int code, const std::string& msg);   // records msg (c
 bool settings_ok(const nyxhip_settings* s, uint32_t mask, std::string& why);
 // nyxhip_dispatch.hip
 int use_lane(nyxhip_ctx* ctx, int lane, hipStream_t* st);   // the stream of workspace lane `lane`, forked from the call's stream on first use
-size_t large_budget(size_t dflt);                           // NYXHIP_LARGE_BUDGET_MB when set, else dflt
 uint32_t pow2ceil(uint32_t v);
 int make_layout(uint32_t mask, const nyxhip_settings* s, int n_cols, uint32_t max_px, uint32_t max_area, uint32_t max_range, LdsLayout& L,
                 std::string& why, size_t cap = 0, uint32_t vmax = 0, bool wide_only = false);

@@ -101,7 +101,7 @@ int ensure_gabor_bank(nyxhip_ctx* ctx, const nyxhip_settings* s)
             for (int i = 0; i < 16; i++) ctx->bank_lp_B[i] = (float)B[i];
             for (int j = 0; j < 16; j++) { ctx->bank_lp_C[2 * (j + 3)] = (float)t[(j * 16 + i0) * 2]; ctx->bank_lp_C[2 * (j + 3) + 1] = (float)t[(j * 16 + i0) * 2 + 1]; }
         }
-        if (getenv("NYXHIP_DEBUG")) fprintf(stderr, "[nyxhip] gabor low-pass: separable %u (residual %.3g of %.3g)\n", ctx->bank_lp_sep, resid, l1);
+        if (knob::debug()) fprintf(stderr, "[nyxhip] gabor low-pass: separable %u (residual %.3g of %.3g)\n", ctx->bank_lp_sep, resid, l1);
     }
     if (ctx->d_bank) HIP_TRY(ctx, hipStreamSynchronize(ctx->stream()));
     ctx->d_bank.release(); ctx->d_bank32.release(); ctx->d_bank16.release();      // (a new bank is a new block, whatever its size)
@@ -296,7 +296,7 @@ int make_dep_layout(uint32_t mask, const nyxhip_settings* s, uint32_t max_area, 
     size_t need = (size_t)4 * 9 * (L.ng_cap + 1);                       // GLDM / NGLDM matrices
     if (mask & NYXHIP_FAM_GLDZM)                                     // union-find parents + matrix
         need = std::max<size_t>(need, 4ull * L.dense_cap + 4ull * (size_t)L.ng_cap * L.nd_cap + 64);
-    if (cap == roi_features_max_lds() && L.ng_cap <= 65 && !getenv("NYXHIP_DEP_SEQ")) {   // (NYXHIP_DEP_SEQ: A/B knob, sequential tails)
+    if (cap == roi_features_max_lds() && L.ng_cap <= 65 && !knob::dep_seq()) {   // (NYXHIP_DEP_SEQ: A/B knob, sequential tails)
         // small matrices: GLDM's and NGLDM's sit side by side at the start of `work` -- where GLDZM keeps its union-find parents,
         // which are dead once its own matrix (behind them) is built -- so the three tails can run in parallel at the end without
         // a byte of extra LDS (the carve-out of the benchmark ROI sits 400 B below the five-workgroups-per-CU line)
@@ -419,10 +419,10 @@ int build_args(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t mask, const nyxh
         g.col_zernike = g.col_gabor + ((mask3 & NYXHIP_FAM_GABOR) ? s->gabor_n_filters : 0) + ((mask & NYXHIP_FAM_RADIAL) ? 2 * kRadialBins : 0);
         g.soft_nan = s->soft_nan;
         g.small_rois = (E.px <= kClassPx[0] && E.side <= kClassSide[0]) ? 1 : 0;   // the smallest size class (a function of the ROI: roi_class)
-        g.gabor_bank = ctx->d_bank.as<double>(); g.gabor_bank32 = ctx->d_bank32.as<float>(); g.gabor_bank16 = ctx->d_bank16.p; { static const int dbg_phase_env = [] { const char* e = getenv("NYXHIP_DBG_PHASE"); return e ? atoi(e) : 0; }(); g.dbg_phase = dbg_phase_env; } g.gabor_nf = s->gabor_n_filters; g.gabor_n = s->gabor_kersize; g.gabor_thr = s->gabor_graythr;
+        g.gabor_bank = ctx->d_bank.as<double>(); g.gabor_bank32 = ctx->d_bank32.as<float>(); g.gabor_bank16 = ctx->d_bank16.p; g.dbg_phase = (int)knob::dbg_phase(); g.gabor_nf = s->gabor_n_filters; g.gabor_n = s->gabor_kersize; g.gabor_thr = s->gabor_graythr;
         for (int f = 0; f <= NYXHIP_MAX_GABOR_FILTERS; f++) g.gabor_zero_rows[f] = ctx->bank_zero_rows[f];
         g.gabor_box_mask = ctx->bank_box_mask;
-        { static const bool no_lpsep = getenv("NYXHIP_GABOR_NO_LPSEP") != nullptr; g.gabor_lp_sep = ctx->bank_lp_sep && !no_lpsep; }
+        g.gabor_lp_sep = ctx->bank_lp_sep && !knob::gabor_no_lpsep();
         memcpy(g.gabor_lp_B, ctx->bank_lp_B, sizeof(g.gabor_lp_B)); memcpy(g.gabor_lp_C, ctx->bank_lp_C, sizeof(g.gabor_lp_C));
     }
     return NYXHIP_OK;
@@ -547,7 +547,7 @@ static int run_large(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t mask, cons
     a.glcm_offset = s->glcm_offset; a.glcm_na = s->glcm_n_angles; a.glcm_symmetric = s->glcm_symmetric;
     for (int i = 0; i < kMaxAngles; i++) a.glcm_angles[i] = s->glcm_angles[i];
     a.n_hist = abs(s->grey_depth);
-    if (const char* e = getenv("NYXHIP_LARGE_DBG")) a.dbg = (uint32_t)atoi(e);
+    a.dbg = (uint32_t)knob::large_dbg();
     a.dense = ctx->dense_next.inten; a.dense_dt = (uint32_t)ctx->dense_next.dt;   // whole-slide mode: the members are dense images (launch_dense_slides)
     a.vec_ok = (((uintptr_t)b->inten & 15u) == 0 && ((uintptr_t)b->x & 7u) == 0 && ((uintptr_t)b->y & 7u) == 0) ? 1u : 0u;
     const bool do_int = mask1 & NYXHIP_FAM_INTENSITY, do_glcm = mask1 & NYXHIP_FAM_GLCM;
@@ -586,7 +586,7 @@ static int run_large(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t mask, cons
     }
     // ---- workspace: the members' blocks back to back (offsets handed out by the prep kernel) when the class fits the budget, else
     // chunks of the list with room for the class's largest block each
-    const size_t budget = large_budget((size_t)8 << 30);
+    const size_t budget = knob::large_budget((size_t)8 << 30);
     const LargeWs Lmax = large_ws_layout(r_max, E.area, ng_max, lvl_cap, na, a.plane16 != 0, do_int, do_glcm);
     const LargeWs Lfix = large_ws_layout(0, 0, ng_max, lvl_cap, na, a.plane16 != 0, do_int, do_glcm);   // what every block holds whatever its ROI
     const uint64_t all_bytes = (uint64_t)count * (Lfix.total + 1024) + (do_int ? 4ull * tot.range1 : 0ull) + (do_glcm ? (a.plane16 ? 2ull : 1ull) * tot.area : 0ull);
@@ -633,8 +633,8 @@ static int run_large_gabor(nyxhip_ctx* ctx, const nyxhip_batch* b, const nyxhip_
                            const uint32_t* list, uint32_t grid, hipStream_t st, DevBuf& buf, bool* served)
 {
     *served = false;
-    const bool no_coop_gabor = [] { const char* e = getenv("NYXHIP_NO_COOP_GABOR"); return e && *e && *e != '0'; }();   // A/B knob (read per call: the tests compare both paths in one process)
-    if (no_coop_gabor || !list || grid == 0 || E.side > kLgabMaxSide || (uint32_t)s->gabor_kersize > kLgabMaxN) return NYXHIP_OK;
+    // (no_coop_gabor: A/B knob, read per call -- the tests compare both paths in one process)
+    if (knob::no_coop_gabor() || !list || grid == 0 || E.side > kLgabMaxSide || (uint32_t)s->gabor_kersize > kLgabMaxN) return NYXHIP_OK;
     LgabArgs ga;
     memset(&ga, 0, sizeof(ga));
     ga.n_roi = b->n_roi; ga.px_offset = b->px_offset; ga.x = b->x; ga.y = b->y; ga.inten = b->inten;
@@ -726,7 +726,7 @@ static int run_large_tex(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t full, 
     const uint64_t fin_fixed = al16(8ull * a.n_cols) + al16(2ull * (ng + 2)) + al16(4ull * (ng + 2)) + al16(16ull * (std::min<uint32_t>(ng, 256) + 2));
     const uint64_t fin_work = std::max<uint64_t>(16ull * (ng + 2), std::min<uint64_t>(16 * slot_max, 64 * 1024));
     const uint64_t lds_fin = fin_fixed + al16(fin_work) + 64;
-    if (getenv("NYXHIP_DEBUG")) fprintf(stderr, "[nyxhip] large texture: count %u ng %u side %u area %u lds strip %llu zone %llu fin %llu\n", count, ng, E.side, E.area,
+    if (knob::debug()) fprintf(stderr, "[nyxhip] large texture: count %u ng %u side %u area %u lds strip %llu zone %llu fin %llu\n", count, ng, E.side, E.area,
                                         (unsigned long long)lds_strip, (unsigned long long)lds_zone, (unsigned long long)lds_fin);
     if (lds_strip > 144 * 1024 || lds_zone > 128 * 1024 || lds_fin > 144 * 1024) return NYXHIP_OK;
     a.lds_strip_bytes = (uint32_t)lds_strip; a.lds_zone_bytes = (uint32_t)lds_zone; a.lds_fin_bytes = (uint32_t)lds_fin;
@@ -738,7 +738,7 @@ static int run_large_tex(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t full, 
     auto var_bytes = [&](uint64_t area, uint64_t members) {
         return cb * area + 64 * members + 8 * (area + 2 * members) + 4 * (area / (S + 1) + 8 * members) + 28 * (area / rmin + members * side_w) + 64 * members;
     };
-    const size_t budget = large_budget((size_t)2 << 30);   // per slot, kept until nyxhip_destroy (nine slots: 8 GiB each could pin 72 GiB of a context)
+    const size_t budget = knob::large_budget((size_t)2 << 30);   // per slot, kept until nyxhip_destroy (nine slots: 8 GiB each could pin 72 GiB of a context)
     const uint64_t all_bytes = (uint64_t)count * fixed + var_bytes(tot.area, count);
     const uint64_t one_max = fixed + var_bytes(area_e, 1);
     uint32_t chunk = count;
@@ -776,7 +776,7 @@ static int run_large_tex(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t full, 
             return fail(ctx, NYXHIP_ERR_HIP, std::string("large-ROI texture kernel launch failed: ") + hipGetErrorString((hipError_t)rc));
     }
     *served = (E.side <= kLtexMaxW && (uint64_t)E.area < (1ull << 20)) ? 1 : 2;
-    if (getenv("NYXHIP_DEBUG")) fprintf(stderr, "[nyxhip] large texture: served %d, workspace %llu MiB, chunk %u, caps %llu / %llu\n", *served, (unsigned long long)(ws_need >> 20), chunk,
+    if (knob::debug()) fprintf(stderr, "[nyxhip] large texture: served %d, workspace %llu MiB, chunk %u, caps %llu / %llu\n", *served, (unsigned long long)(ws_need >> 20), chunk,
                                         (unsigned long long)cap_load, (unsigned long long)cap_strip);
     return NYXHIP_OK;
 }
@@ -844,17 +844,14 @@ int run_class(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t mask, const nyxhi
     // one class's grid beside the next class's launches).  Measured on the mixed batch with the config-4 families: 3.51 ms against
     // 3.28 ms on one stream -- the chip is busy either way, and the interleaved classes evict each other's L2 lines.  Off unless asked
     // for (NYXHIP_LDS_LANES=1, A/B knob).
-    static const bool lds_lanes = [] { const char* e = getenv("NYXHIP_LDS_LANES"); return e && *e && *e != '0'; }();
-    const bool on_lds_lane = lds && !gs && lds_lanes && list && cls >= 0 && cls / 2 < kFirstLargeSizeClass && !ctx->win_next.inten;
+    const bool on_lds_lane = lds && !gs && knob::lds_lanes() && list && cls >= 0 && cls / 2 < kFirstLargeSizeClass && !ctx->win_next.inten;
     if (on_lds_lane)
         if (int lrc = enter_lane(4 + cls / 2)) return lrc;
     // Size class 2 (boxes up to 128 x 128, up to 16384 pixels) fits LDS, but its texture kernel is one workgroup walking 16 k cells through
     // a dozen passes and a serial zone sweep: ~0.3 ms per ROI whatever the batch, and a class of two thousand such ROIs is a round and
     // a tail of them (0.7-0.9 ms of the mixed batch's 3.3).  Its GLRLM / GLSZM / NGTDM go through the several-workgroups-per-ROI path
     // as well (roi_large_tex.hip), on a lane beside the main stream.  A function of the class, i.e. of the ROI.
-    static const bool no_sc2_tex = [] { const char* e = getenv("NYXHIP_NO_COOP_TEX_SC2"); const char* f = getenv("NYXHIP_NO_COOP_TEX"); const char* g0 = getenv("NYXHIP_NO_COOP");
-                                        return (e && *e && *e != '0') || (f && *f && *f != '0') || (g0 && *g0 && *g0 != '0'); }();   // A/B knob
-    if (list && cls / 2 == 2 && (lds & 2) && tot && !no_sc2_tex) {
+    if (list && cls / 2 == 2 && (lds & 2) && tot && !knob::no_sc2_tex()) {   // A/B knob
         // (a function of the class alone: a window-mode chunk -- INTENSITY / GLCM only by construction, so never here with texture families --
         //  would come back with its clouds rather than take the other texture kernel)
         if (!b->inten) return NYXHIP_INTERNAL_NEEDS_CLOUDS;
@@ -893,7 +890,7 @@ int run_class(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t mask, const nyxhi
         // block of columns.
         auto launch_features_main = [&]() -> int {
             const uint32_t both = NYXHIP_FAM_INTENSITY | NYXHIP_FAM_GLCM;
-            if ((a.mask & both) == both && a.L.g16 && !getenv("NYXHIP_G16_FUSED")) {
+            if ((a.mask & both) == both && a.L.g16 && !knob::g16_fused()) {
                 RoiArgs ai = a, ag = a;
                 std::string w2;
                 const int ncol_g = a.n_cols - a.col_glcm;              // (col_glcm: behind the intensity block and the outline columns)
@@ -910,13 +907,12 @@ int run_class(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t mask, const nyxhi
         };
         // Wide-range classes whose ranges fit 16 bits (16-bit microscopy data): the first-order features from a presence bitmap and a
         // duplicate list instead of a sort (roi_wide.hip), the GLCM columns from the GLCM-only build.  (The sort engine inside the
-        // fused kernel cost 43 ns per 2821-pixel ROI against 12.5 ns on 12-bit data.)
-        static const bool no_wide = [] { const char* e = getenv("NYXHIP_NO_WIDE"); return e && *e && *e != '0'; }();   // A/B knob
+        // fused kernel cost 43 ns per 2821-pixel ROI against 12.5 ns on 12-bit data.)  A/B knob: no_wide.
         // Which engine serves a member is decided by ITS range (<= 0xFFFF: roi_wide + the GLCM-only build; beyond: the fused sort
         // kernel), never by the class's observed extrema: both launches run over the class and each skips the other's members.
         auto launch_features_wide = [&](bool& done) -> int {
             done = false;
-            if (no_wide || !list || !(cls & 1) || !(a.mask & NYXHIP_FAM_INTENSITY)) return 0;
+            if (knob::no_wide() || !list || !(cls & 1) || !(a.mask & NYXHIP_FAM_INTENSITY)) return 0;
             WideArgs wa;
             memset(&wa, 0, sizeof(wa));
             if (!make_wide_layout(E.px, (uint32_t)abs(s->grey_depth), wa)) return 0;
@@ -958,9 +954,8 @@ int run_class(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t mask, const nyxhi
             // Size class 2 and Gabor: boxes of 65..128 px hold 87 KB of LDS in the tiled kernel -- one workgroup per CU, ~11 ms for the
             // 2 031 such ROIs of the heavy-tailed batch, with three quarters of every CU's wave slots idle.  On a lane of its own the
             // smaller classes' launches (and this class's other families) run beside it instead of behind it.
-            static const bool no_gabor_lane = [] { const char* e = getenv("NYXHIP_NO_GABOR_LANE"); return e && *e && *e != '0'; }();   // A/B knob
             hipStream_t gst = st;
-            if (!no_gabor_lane && list && cls / 2 == 2 && (mask & NYXHIP_FAM_GABOR) && !on_lds_lane && !ctx->win_next.inten)
+            if (!knob::no_gabor_lane() && list && cls / 2 == 2 && (mask & NYXHIP_FAM_GABOR) && !on_lds_lane && !ctx->win_next.inten)
                 if (int lrc = use_lane(ctx, nyxhip_ctx::kGaborLane, &gst)) return lrc;
             rc = launch_roi_shape(g, gst, grid);
         }
@@ -977,7 +972,7 @@ int run_class(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t mask, const nyxhi
     }
 
     // ---- INTENSITY + GLCM of the class by several workgroups per ROI (every member whose intensity range the histogram holds) ------
-    static const bool no_coop = [] { const char* e = getenv("NYXHIP_NO_COOP"); return e && *e && *e != '0'; }();   // A/B knob: the one-workgroup path
+    const bool no_coop = knob::no_coop();   // A/B knob: the one-workgroup path
     bool coop = false;
     if ((gs & 1) && tot && !no_coop) {
         if (int lrc = run_large(ctx, b, full, s, d_out, ld, E, *tot, list, grid, &coop)) return lrc;
@@ -989,8 +984,7 @@ int run_class(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t mask, const nyxhi
     }
 
     // the lane of this class (nyxhip_ctx::lane_stream): large classes only -- the workspace fallback of an LDS class stays on the main stream
-    static const bool no_lanes = [] { const char* e = getenv("NYXHIP_NO_LANES"); return e && *e && *e != '0'; }();   // A/B knob
-    const int lane = (!no_lanes && cls / 2 >= kFirstLargeSizeClass) ? (cls - 2 * kFirstLargeSizeClass) % 4 : -1;
+    const int lane = (!knob::no_lanes() && cls / 2 >= kFirstLargeSizeClass) ? (cls - 2 * kFirstLargeSizeClass) % 4 : -1;
     if (lane >= 0)
         if (int lrc2 = enter_lane(lane)) return lrc2;
     auto lane_stamp = [&]() -> int {
@@ -1002,9 +996,8 @@ int run_class(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t mask, const nyxhi
     };
 
     // ---- GLRLM + GLSZM + NGTDM of the class by several workgroups per ROI (roi_large_tex.hip) ---------------------------------------
-    static const bool no_coop_tex = [] { const char* e = getenv("NYXHIP_NO_COOP_TEX"); return e && *e && *e != '0'; }();   // A/B knob
     int tex_served = 0;
-    if ((gs & 2) && tot && !no_coop && !no_coop_tex && cls / 2 >= kFirstLargeSizeClass) {
+    if ((gs & 2) && tot && !no_coop && !knob::no_coop_tex() && cls / 2 >= kFirstLargeSizeClass) {
         if (int lrc = run_large_tex(ctx, b, full, s, d_out, ld, E, *tot, list, grid, st, lane >= 0 ? lane : nyxhip_ctx::kLanes, &tex_served)) return lrc;
         if (tex_served && report) report->cooperative |= 2;
         if (tex_served == 1) gs &= ~2u;
@@ -1043,8 +1036,7 @@ int run_class(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t mask, const nyxhi
     }
     // The dependence trio of a large class (one workgroup per ROI over the workspace: a few hundred workgroups, ~11 ms for the heavy-tailed
     // batch) on a lane and a scratch buffer of its own: it runs beside the class's other chains instead of behind them.
-    static const bool no_dep_lane = [] { const char* e = getenv("NYXHIP_NO_DEP_LANE"); return e && *e && *e != '0'; }();   // A/B knob
-    if ((gs & 8) && lane >= 0 && !no_dep_lane && gs != 8u) {
+    if ((gs & 8) && lane >= 0 && !knob::no_dep_lane() && gs != 8u) {
         hipStream_t dst = st;
         if (int lrc2 = use_lane(ctx, nyxhip_ctx::kDepLane, &dst)) return lrc2;
         const size_t dstride = (d2.L.total + 255) & ~(size_t)255;
@@ -1140,20 +1132,17 @@ int launch_device_all(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t mask, con
     };
     if ((mask & ~kTailFams) || !hinted) {               // (a batch without stated extrema gets them from the class headers)
         bool done = false;
-        static const bool force_exact = [] { const char* e = getenv("NYXHIP_CLASS_SYNC"); return e && *e && *e != '0'; }();   // A/B knob
         // (IBSI co-occurrence matrices are as large as the largest intensity, which a statement about the batch does not carry)
         const bool need_vmax = s->ibsi && (mask & (NYXHIP_FAM_GLCM | kTexture | kDependence));
         // (a stated range that allows wide-range ROIs takes the exact path as well: a whole-batch launch per table width would
         //  carve 43 KB for a class that 16-bit data leaves empty -- 100 k workgroups that only return, three per CU)
         const bool wide_possible = max_range >= 16384u && (mask & NYXHIP_FAM_INTENSITY);
         const bool has_m1 = !(max_px <= kClassPx[0] && max_side <= kClassSide[0]);
-        static const bool no_small = [] { const char* e = getenv("NYXHIP_NO_SMALL"); return e && *e && *e != '0'; }();   // A/B knob
-        static const bool no_adapt = [] { const char* e = getenv("NYXHIP_NO_ADAPT"); return e && *e && *e != '0'; }();   // A/B knob
-        const bool small_fits = !no_small && ((mask & NYXHIP_FAM_INTENSITY) || (!s->ibsi && s->grey_depth > 0 && s->grey_depth <= 64));
+        const bool small_fits = !knob::no_small() && ((mask & NYXHIP_FAM_INTENSITY) || (!s->ibsi && s->grey_depth > 0 && s->grey_depth <= 64));
         const bool two_filtered = (mask & (NYXHIP_FAM_INTENSITY | NYXHIP_FAM_GLCM)) && has_m1 && small_fits;
         // (the recent calls held the smallest class in numbers: exact lists beat two launches that each skip the other's slots)
-        const bool prefer_lists = two_filtered && !no_adapt && ctx->census_total != 0 && 4 * ctx->census_small >= ctx->census_total;
-        if (hinted && !force_exact && !need_vmax && !wide_possible && !prefer_lists && max_px <= kClassPx[1] && max_side <= kClassSide[1]) {
+        const bool prefer_lists = two_filtered && !knob::no_adapt() && ctx->census_total != 0 && 4 * ctx->census_small >= ctx->census_total;
+        if (hinted && !knob::class_sync() && !need_vmax && !wide_possible && !prefer_lists && max_px <= kClassPx[1] && max_side <= kClassSide[1]) {
             // ---- whole-batch launches, nothing counted -----------------------------------------------------------------------
             if (two_filtered) ctx->census_pending += n_roi;
             const Extrema Eall{max_px, max_area, max_range, max_side};
@@ -1224,16 +1213,14 @@ int launch_device_all(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t mask, con
             // classes the bitmap kernel serves -- goes back for them BEFORE anything is launched: raised from inside the class loop it
             // made the caller run the whole chunk again, every LDS class computed twice (16-bit tiles: on every chunk).
             if (ctx->win_next.inten && !b->inten && (mask & ~kTailFams)) {
-                static const bool no_wide_pre = [] { const char* e = getenv("NYXHIP_NO_WIDE"); return e && *e && *e != '0'; }();
                 for (int cls = 0; cls < kClasses; cls++) {
                     if (H[cls * H_WORDS + H_COUNT] == 0) continue;
-                    if (cls / 2 >= kFirstLargeSizeClass || ((cls & 1) && (mask & NYXHIP_FAM_INTENSITY) && !no_wide_pre))
+                    if (cls / 2 >= kFirstLargeSizeClass || ((cls & 1) && (mask & NYXHIP_FAM_INTENSITY) && !knob::no_wide()))
                         return NYXHIP_INTERNAL_NEEDS_CLOUDS;
                 }
             }
-            static const bool no_merge = [] { const char* e = getenv("NYXHIP_NO_MERGE_LARGE"); return e && *e && *e != '0'; }();   // A/B knob
             int first_cls = kClasses - 1;
-            if (!no_merge && (mask & ~kTailFams)) {
+            if (!knob::no_merge_large() && (mask & ~kTailFams)) {
                 uint32_t cnt = 0; int top = -1;
                 Extrema Em{0, 0, 0, 0, 0, false};
                 ClassTotals tm{0, 0, 0};
@@ -1284,9 +1271,8 @@ namespace nyxhip {
 int use_lane(nyxhip_ctx* ctx, int lane, hipStream_t* st)
 {
     if (!ctx->lane_stream[lane]) {
-        static const bool no_prio = [] { const char* e = getenv("NYXHIP_NO_LANE_PRIORITY"); return e && *e && *e != '0'; }();   // A/B knob
         int lo = 0, hi = 0;
-        if (no_prio || hipDeviceGetStreamPriorityRange(&lo, &hi) != hipSuccess) lo = hi = 0;
+        if (knob::no_lane_priority() || hipDeviceGetStreamPriorityRange(&lo, &hi) != hipSuccess) lo = hi = 0;
         HIP_TRY(ctx, hipStreamCreateWithPriority(&ctx->lane_stream[lane], hipStreamNonBlocking, hi));
         HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->lane_done[lane], hipEventDisableTiming));
     }
@@ -1298,13 +1284,6 @@ int use_lane(nyxhip_ctx* ctx, int lane, hipStream_t* st)
     return NYXHIP_OK;
 }
 
-// Workspace budget of a large-ROI path or a deferred list (deferred_list.h): NYXHIP_LARGE_BUDGET_MB when set (tests: a small budget
-// sends a class, or a list, through the chunked form; read per call), else the path's default.
-size_t large_budget(size_t dflt)
-{
-    const char* const be = getenv("NYXHIP_LARGE_BUDGET_MB");
-    return be && atoll(be) > 0 ? (size_t)atoll(be) << 20 : dflt;
-}
 
 uint32_t pow2ceil(uint32_t v)
 {

@@ -29,7 +29,7 @@ int ih_device(nyxhip_ctx* ctx, const nyxhip_batch* b, const nyxhip_settings* s, 
     if (b->n_roi == 0) return NYXHIP_OK;
     if (int rc = ih_settings_check(ctx, s)) return rc;
     // A/B knob of tools/ih_probe.py: every ROI through the workgroup form
-    static const bool one_form = [] { const char* e = getenv("NYXHIP_IH_ONE_FORM"); return e && *e && *e != '0'; }();
+    const bool one_form = knob::ih_one_form();
     IhArgs a;
     memset(&a, 0, sizeof(a));
     a.n_roi = b->n_roi; a.px_offset = b->px_offset; a.inten = b->inten; a.vmin = b->min_inten; a.vmax = b->max_inten;

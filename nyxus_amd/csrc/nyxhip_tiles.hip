@@ -113,8 +113,7 @@ static int tiles_chunk(nyxhip_ctx* ctx, const void* d_inten, int dtI, const void
     const uint64_t npx = ((uint64_t)meta[2] << 32) | meta[1];
     // INTENSITY / GLCM alone, every ROI LDS-sized: the feature kernel reads the ROIs' windows of the tiles itself and no cloud is
     // materialised (8 B per ROI pixel written and read back otherwise).  Any other family, or ROIs beyond LDS: clouds.
-    static const bool no_window = [] { const char* e = getenv("NYXHIP_NO_WINDOW"); return e && *e && *e != '0'; }();   // A/B and tests
-    bool window = !no_window && !neighbor_distance && (family_mask & ~(uint32_t)(NYXHIP_FAM_INTENSITY | NYXHIP_FAM_GLCM)) == 0;
+    bool window = !knob::no_window() && !neighbor_distance && (family_mask & ~(uint32_t)(NYXHIP_FAM_INTENSITY | NYXHIP_FAM_GLCM)) == 0;   // (no_window: A/B and tests)
     if (window) {
         LdsLayout Lt; std::string why_t;
         window = make_layout(family_mask, s, nyxhip_n_columns(family_mask, s), meta[3], meta[4], meta[5], Lt, why_t) == NYXHIP_OK;
@@ -147,8 +146,7 @@ static int tiles_chunk(nyxhip_ctx* ctx, const void* d_inten, int dtI, const void
     }
     if (window)
     {
-        static const bool no_swz = [] { const char* e = getenv("NYXHIP_NO_XCD_SWIZZLE"); return e && *e && *e != '0'; }();   // A/B
-        ctx->win_next = WindowSrc{d_inten, d_label, dtI, dtL, W, H, R.tile, R.label, R.bbox_x0, R.bbox_y0, no_swz ? 0u : 1u};
+        ctx->win_next = WindowSrc{d_inten, d_label, dtI, dtL, W, H, R.tile, R.label, R.bbox_x0, R.bbox_y0, knob::no_xcd_swizzle() ? 0u : 1u};   // (A/B knob)
     }
     // the box origins inside the tile: one tile is one image, so they are the reference's coordinates (the caliper classes read them)
     if (neighbor_distance == kTilesReducerIh)
@@ -238,8 +236,8 @@ static void parallel_copy(void* dst, const void* src, size_t n)
 }
 hipError_t staged_h2d(nyxhip_ctx* ctx, void* dst, const void* src, size_t bytes, hipStream_t st)
 {
-    static const bool no_stage = [] { const char* e = getenv("NYXHIP_NO_STAGING"); return e && *e && *e != '0'; }();   // A/B knob: the runtime's own pageable path
-    if (no_stage || bytes < ((size_t)1 << 20)) return hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st);
+    // (no_staging: A/B knob, the runtime's own pageable path)
+    if (knob::no_staging() || bytes < ((size_t)1 << 20)) return hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st);
     for (size_t o = 0; o < bytes; o += nyxhip_ctx::kStageSlotBytes) {
         const size_t len = std::min(nyxhip_ctx::kStageSlotBytes, bytes - o);
         const int k = ctx->h_stage_next;
@@ -292,8 +290,7 @@ struct HostPin {
     static constexpr uintptr_t kPage = 4096;
     void pin(int k, const void* ptr, size_t bytes)
     {
-        static const bool no_pin = [] { const char* e = getenv("NYXHIP_NO_PIN"); return e && *e && *e != '0'; }();   // A/B knob
-        if (no_pin || !ptr) return;
+        if (knob::no_pin() || !ptr) return;   // (A/B knob)
         const uintptr_t a = ((uintptr_t)ptr + kPage - 1) & ~(kPage - 1), z = ((uintptr_t)ptr + bytes) & ~(kPage - 1);
         if (z <= a) return;                                   // no whole page inside the array
         if (hipHostRegister((void*)a, z - a, hipHostRegisterDefault) == hipSuccess) { p[k] = (void*)a; lo[k] = a; hi[k] = z; } else (void)hipGetLastError();
@@ -316,7 +313,7 @@ struct HostPin {
         for (void* q : p)
             if (q && hipHostUnregister(q) != hipSuccess) {
                 (void)hipGetLastError();
-                if (getenv("NYXHIP_DEBUG")) fprintf(stderr, "[nyxhip] hipHostUnregister(%p) failed\n", q);
+                if (knob::debug()) fprintf(stderr, "[nyxhip] hipHostUnregister(%p) failed\n", q);
             }
     }
 };

@@ -26,8 +26,8 @@
 #include <hip/hip_runtime.h>
 #include <type_traits>
 #include <algorithm>
-#include <cstdlib>
 #include <cstdio>
+#include "knobs.h"
 #include "device_math.h"
 #include "roi_kernel.h"
 #include "launch_util.h"
@@ -2956,7 +2956,7 @@ int launch_lds_variant(const RoiArgs& a, hipStream_t st, uint32_t grid, bool& de
     int occ = 4;
     for (int o = fam_ok ? 8 : 7; o > 4; o--)
         if ((size_t)o * a.L.total <= lds) { occ = o; break; }
-    if (const char* e = getenv("NYXHIP_MAX_OCC")) occ = occ < atoi(e) ? occ : (atoi(e) < 4 ? 4 : atoi(e));   // tuning knob (bench experiments)
+    occ = knob::cap_occ(occ);   // tuning knob (bench experiments)
     const bool win = a.win.inten != nullptr;
     if (win && a.win.xcd_swz) grid = (grid + 7u) & ~7u;               // (xcd_slot: every XCD walks its own eighth of the slots)
     // the 64-VGPR builds with the intensity block leave their closing math to intensity_close_kernel (launch_roi_features)
@@ -3010,10 +3010,10 @@ int launch_roi_features(const RoiArgs& a, void* stream, uint32_t grid)
         else hipLaunchKernelGGL((roi_features_kernel<true, false, false, false>), dim3(grid), dim3(kBlock), a.L.gs_lds_bytes, st, a);
         return (int)hipGetLastError();
     }
-    if (getenv("NYXHIP_DEBUG")) fprintf(stderr, "[nyxhip] features launch: g16 %u dense8 %u cnt16 %u ng_cap %u app %u total %u mask %u gd %d\n", a.L.g16, a.L.dense8, a.L.cnt16, a.L.ng_cap, a.L.app, a.L.total, a.mask, a.grey_depth);
+    if (knob::debug()) fprintf(stderr, "[nyxhip] features launch: g16 %u dense8 %u cnt16 %u ng_cap %u app %u total %u mask %u gd %d\n", a.L.g16, a.L.dense8, a.L.cnt16, a.L.ng_cap, a.L.app, a.L.total, a.mask, a.grey_depth);
     // the smallest size class on its own kernel: a wave per ROI (roi_small.hip).  small_class: 1 = a list / filtered launch of class 0,
     // 2 = a whole-batch launch whose stated extrema promise class 0 only
-    static const bool no_small = [] { const char* e = getenv("NYXHIP_NO_SMALL"); return e && *e && *e != '0'; }();   // A/B knob
+    const bool no_small = knob::no_small();   // A/B knob
     if (a.L.g16) {
         if (a.small_class && !no_small && roi_small_supported(a)) return launch_roi_small(a, st, grid, a.small_class == 2);
         static DeviceOnce optin;
@@ -3028,10 +3028,9 @@ int launch_roi_features(const RoiArgs& a, void* stream, uint32_t grid)
                 return 0;
             }))
             return orc;
-        static const bool w4 = [] { const char* e = getenv("NYXHIP_G16_W4"); return e && *e && *e != '0'; }();   // A/B knob: four waves per ROI
-        static const uint32_t g16_w8_min = [] { const char* e = getenv("NYXHIP_G16_W8_MIN"); return e && *e ? (uint32_t)atoi(e) : 48u * 48u; }();   // tuning knob: smallest class box for eight waves
+        // g16_w4: A/B knob, four waves per ROI | g16_w8_min: tuning knob, smallest class box for eight waves
         // (eight waves pay where the load and the sweep are long: 2821-px ROIs 23.0 -> 22.1 ns, 1009-px ROIs 18.5 -> 18.8: by the class's largest box)
-        if (!(a.mask & NYXHIP_FAM_INTENSITY) && !w4 && a.L.dense_cap >= g16_w8_min) {
+        if (!(a.mask & NYXHIP_FAM_INTENSITY) && !knob::g16_w4() && a.L.dense_cap >= (uint32_t)knob::g16_w8_min()) {
             if (a.win.inten != nullptr) hipLaunchKernelGGL(roi_features_kernel_g16w8<1>, dim3(a.win.xcd_swz ? (grid + 7u) & ~7u : grid), dim3(512), a.L.total, st, a);
             else hipLaunchKernelGGL(roi_features_kernel_g16w8<0>, dim3(grid), dim3(512), a.L.total, st, a);
         } else
@@ -3055,10 +3054,9 @@ int launch_roi_features(const RoiArgs& a, void* stream, uint32_t grid)
         rc = (int)hipGetLastError();
     }
     if (rc == 0 && split && a.glcm_feats != 1) {
-        static const bool no_pairs = [] { const char* e = getenv("NYXHIP_GLCM_NO_PAIRS"); return e && *e && *e != '0'; }();   // A/B knob
         RoiArgs af = a;
         if (a.glcm_feats == 2) af.sp.class_mask = 0;          // (the class-0 group of this call left its counts for this launch: everybody with a matrix order is derived)
-        if (a.L.ng_cap <= 8 && !no_pairs)         // eight lanes per angle, two ROIs per wave
+        if (a.L.ng_cap <= 8 && !knob::glcm_no_pairs())   // eight lanes per angle, two ROIs per wave (A/B knob)
             hipLaunchKernelGGL(glcm_features_kernel8, dim3((grid + 2 * kWaves - 1) / (2 * kWaves)), dim3(kBlock), glcm_features8_lds(a.L.ng_cap), st, af);
         else
             hipLaunchKernelGGL(glcm_features_kernel, dim3((grid + kWaves - 1) / kWaves), dim3(kBlock), glcm_features_lds(a.L.ng_cap), st, af);

@@ -21,7 +21,7 @@
 // Built with -ffp-contract=off (device_math.h).
 #include <hip/hip_runtime.h>
 #include <cstdio>
-#include <cstdlib>
+#include "knobs.h"
 #include "device_math.h"
 #include "roi_kernel.h"
 #include "launch_util.h"
@@ -1305,14 +1305,7 @@ int launch_roi_shape(const ShapeArgs& a, void* stream, uint32_t grid)
         // 2 (default): fused taps with the reference's decisions; NYXHIP_GABOR_EXACT=1 -> 0: the reference's arithmetic throughout (A/B);
         // NYXHIP_GABOR_FUSED=1 -> 1: fused taps, decisions unchecked (changes results on tie-laden inputs: INTEGRATION.md)
         // 3 (default): packed-fp32 screening with the reference's decisions; NYXHIP_GABOR_MODE=2: the fp64 fused taps of round 3 (A/B)
-        static const int mode = [] {
-            const char* e = getenv("NYXHIP_GABOR_FUSED");
-            if (e && *e && *e != '0') return 1;
-            e = getenv("NYXHIP_GABOR_EXACT");
-            if (e && *e && *e != '0') return 0;
-            e = getenv("NYXHIP_GABOR_MODE");
-            return (e && *e == '2') ? 2 : (e && *e == '3') ? 3 : 4;
-        }();
+        const int mode = knob::gabor_mode();
         // worth its registers (the build with the row tests needs ~25 more: one wave per SIMD less) when at least 4 % of the
         // bank's arithmetic falls away: the reference's default bank (f0 = 0 in its first filter) saves 10.6 %, the 8-orientation
         // bank of BASELINE.json configs[4] one row in 288
@@ -1322,7 +1315,7 @@ int launch_roi_shape(const ShapeArgs& a, void* stream, uint32_t grid)
             zero_halves += __builtin_popcount(im) + __builtin_popcount(both);
         }
         const bool zr = 25 * zero_halves >= 32 * (a.gabor_nf + 1);
-        if (getenv("NYXHIP_DEBUG")) fprintf(stderr, "[nyxhip] gabor launch: nf %d box_mask %x zero_halves %d zr %d mode %d total %u small %d\n", a.gabor_nf, a.gabor_box_mask, zero_halves, (int)zr, mode, a.L.total, (int)small);
+        if (knob::debug()) fprintf(stderr, "[nyxhip] gabor launch: nf %d box_mask %x zero_halves %d zr %d mode %d total %u small %d\n", a.gabor_nf, a.gabor_box_mask, zero_halves, (int)zr, mode, a.L.total, (int)small);
 #define NYX_GABOR_LAUNCH(M, Z)                                                                                                         \
         do {                                                                                                                           \
             if (small) hipLaunchKernelGGL((roi_gabor_tiled_kernel<4, 1, M, Z>), dim3(grid), dim3(64), a.L.total, st, a);               \

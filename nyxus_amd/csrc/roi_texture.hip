@@ -22,7 +22,7 @@
 // Built with -ffp-contract=off (device_math.h).
 #include <hip/hip_runtime.h>
 #include <cstdio>
-#include <cstdlib>
+#include "knobs.h"
 #include "device_math.h"
 #include "roi_kernel.h"
 #include "launch_util.h"
@@ -1045,12 +1045,6 @@ __global__ __launch_bounds__(kBlock, OCC) void roi_texture_kernel(const TexArgs 
         out_row[gcol(c)] = s_out[c];
 }
 
-static int tex_max_occ()   // diagnostic knob: NYXHIP_TEX_OCC=4 keeps the 106-register build
-{
-    static const int v = [] { const char* e = getenv("NYXHIP_TEX_OCC"); return e && *e ? atoi(e) : 8; }();
-    return v;
-}
-
 int launch_roi_texture(const TexArgs& a, void* stream, uint32_t grid)
 {
     static DeviceOnce optin;
@@ -1074,17 +1068,18 @@ int launch_roi_texture(const TexArgs& a, void* stream, uint32_t grid)
         return orc;
     if (grid == 0)
         return 0;
-    if (getenv("NYXHIP_DEBUG")) fprintf(stderr, "[nyxhip] texture launch: dense8 %u ng_cap %u total %u work %u ngt_rep %u mask %u\n", a.L.dense8, a.L.ng_cap, a.L.total, a.L.work_bytes, a.L.ngt_rep, a.mask);
+    const long long max_occ = knob::tex_occ();   // diagnostic knob: NYXHIP_TEX_OCC=4 keeps the 106-register build
+    if (knob::debug()) fprintf(stderr, "[nyxhip] texture launch: dense8 %u ng_cap %u total %u work %u ngt_rep %u mask %u\n", a.L.dense8, a.L.ng_cap, a.L.total, a.L.work_bytes, a.L.ngt_rep, a.mask);
     if (a.sp.scratch)
         hipLaunchKernelGGL((roi_texture_kernel<true, 2>), dim3(grid), dim3(kBlock), a.L.gs_lds_bytes, (hipStream_t)stream, a);
     // (LDS is handed out in 1280-byte granules: k workgroups share a CU when k rounded-up carve-outs fit)
-    else if (a.L.dense8 && tex_max_occ() >= 8 && 8ull * (((size_t)a.L.total + 1279) / 1280 * 1280) <= roi_features_max_lds())
+    else if (a.L.dense8 && max_occ >= 8 && 8ull * (((size_t)a.L.total + 1279) / 1280 * 1280) <= roi_features_max_lds())
         hipLaunchKernelGGL((roi_texture_kernel<false, 8, true>), dim3(grid), dim3(kBlock), a.L.total, (hipStream_t)stream, a);
     else if (a.L.dense8)
         hipLaunchKernelGGL((roi_texture_kernel<false, 7, true>), dim3(grid), dim3(kBlock), a.L.total, (hipStream_t)stream, a);
-    else if (tex_max_occ() >= 7 && 7ull * (((size_t)a.L.total + 1279) / 1280 * 1280) <= roi_features_max_lds())
+    else if (max_occ >= 7 && 7ull * (((size_t)a.L.total + 1279) / 1280 * 1280) <= roi_features_max_lds())
         hipLaunchKernelGGL((roi_texture_kernel<false, 7>), dim3(grid), dim3(kBlock), a.L.total, (hipStream_t)stream, a);
-    else if (tex_max_occ() >= 6 && 6ull * (a.L.total + 256) <= roi_features_max_lds())
+    else if (max_occ >= 6 && 6ull * (a.L.total + 256) <= roi_features_max_lds())
         hipLaunchKernelGGL((roi_texture_kernel<false, 6>), dim3(grid), dim3(kBlock), a.L.total, (hipStream_t)stream, a);
     else
         hipLaunchKernelGGL((roi_texture_kernel<false, 4>), dim3(grid), dim3(kBlock), a.L.total, (hipStream_t)stream, a);
