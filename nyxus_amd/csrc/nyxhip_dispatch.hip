@@ -1442,6 +1442,16 @@ int make_layout(uint32_t mask, const nyxhip_settings* s, int n_cols, uint32_t ma
         L.dense = 0;
         if (L.g16) L.gscr = 0;
     }
+#ifndef NYX_NO_OVERLAP      // (diagnostic builds: every launch in the serial order)
+    if (do_int && do_glcm && L.cnt16 && L.dense8 && !L.g16 && !spill) {
+        // The overlapped builds of roi_features_body (INTENSITY + GLCM at <= 16 levels) count co-occurrences while wave 0 and wave 1
+        // still read the counting table and the first-moment prefixes behind it.  The matrices lie over the value buffer, dead by
+        // then: up to kMaxAngles of them with a skip row and column each, from L.P on.  Where they would run on into the table --
+        // small ROIs beside a large matrix order -- the launch keeps the serial order.
+        const uint32_t p_end = L.P + 4u * (uint32_t)kMaxAngles * (L.ng_cap + 1u) * (L.ng_cap + 1u);
+        L.overlap = (L.P == L.val && p_end <= L.cnt) ? 1u : 0u;
+    }
+#endif
     if (spill) {
         // ---- workspace launches: the ROI-sized buffers (values, binned plane) live in global memory, but everything small and
         // atomics-heavy stays in LDS when it fits 60 KiB -- the fixed scratch always, then the co-occurrence matrices with their

@@ -1240,6 +1240,199 @@ __device__ __forceinline__ void roi_features_body(const RoiArgs& A, const uint64
     //  four to six waves per SIMD, came out with MORE spills under the late view and keep the plain one -- KView)
     const KView<FAM != 0 || G16> B(A);
     double* const out_row_l = B->out + roi * B->ld;
+    // OVL: INTENSITY + GLCM at <= 16 levels on 16-bit tables (FAM 1: every tier of the compact family set).  Nothing behind the counting
+    // engine reads what the order-statistics chain (wave 0) and the n-bin bounds with the entropy (wave 1) produce, and the central-sum
+    // sweep needs only the mean.  So these builds take the sweep in front of the engine and run chain, entropy and the co-occurrence
+    // sweep in ONE barrier interval, the rows divided so that the four waves finish together (glcm_row_bounds, roi_kernel.h).  The
+    // interval is legal only where the matrices (over the dead value buffer) end in front of the counting table, which the chain
+    // still reads: a fact of the launch's carve-out (LdsLayout::overlap).  Launches without it keep the serial order.
+    // Barriers of a workgroup, every one reached by all four waves (what decides a path is a fact of the ROI or of the launch):
+    //   phase 0 (1) | window loader only: its trips + 1, or 1 (the generic loader) | sums (2) | sweep (1, not for a blank ROI) |
+    //   engine (2) | serial only: chain (1, not for a blank ROI) | unless the ROI is degenerate (a blank one is; its waves all
+    //   leave in front of what follows): serial only: the zeroing pair (2); the co-occurrence sweep's end (1).
+    // Boundaries (STAMP / NYX_EXIT_AT) of these builds: 0 LDS cleared | 1 load pass | 2 mean published | 3 central-sum sweep, (overlapped:
+    // matrices zeroed,) counting engine | 4 (a blank ROI's sums closed) | 5, 6 nothing | 7 chain (wave 0), n-bin bounds and entropy
+    // (wave 1); serial: and their barrier | 8, 9 nothing | 10 serial: matrices zeroed between two barriers | 11 co-occurrence
+    // sweep and its barrier (overlapped: the barrier that also ends the chain's interval) | 12 counts exported.
+    // (Every other build: the legend of tools/headline_phase_libs.sh.)
+#ifdef NYX_NO_FUSED
+    constexpr bool OVL = false;
+#else
+    constexpr bool OVL = C16 && !GS && FAM == 1;
+#endif
+#ifdef NYX_NO_DEFER
+    constexpr bool OVL_DEFER = false;
+#else
+    constexpr bool OVL_DEFER = OVL && DEFER_P;     // (the builds that leave the closing math to intensity_close_kernel: the record's flag)
+#endif
+    const bool ovl = OVL && B->L.overlap != 0;
+
+    // ---- the pieces of the <= 16-level co-occurrence block (FAST, see the GLCM section) as callables: the overlapped launches zero the
+    // matrices from inside the intensity block.  (The sweep keeps ONE call site, in the GLCM block: a second inlined copy behind the
+    // chain came out with six more scalar-register spills and cost more than the overlap returns, profiles/r29_overlap_order.txt.)
+    struct FastGlcm {
+        int na, Ng, NG1, NN, cells, slot0, slot1, slot2, slot3;
+        bool symmetric, usual, dpp2, dpp;
+    };
+    auto fast_cfg = [&]() -> FastGlcm {
+        FastGlcm G;
+        G.na = B->glcm_na;
+        G.Ng = greyInfo; G.NG1 = G.Ng + 1; G.NN = G.Ng * G.Ng; G.cells = G.NG1 * G.NG1;
+        G.symmetric = B->glcm_symmetric != 0;
+        G.slot0 = -1; G.slot1 = -1; G.slot2 = -1; G.slot3 = -1;
+#pragma unroll
+        for (int q = 0; q < kMaxAngles; q++)
+            if (q < G.na) {
+                const int ang = B->glcm_angles[q];
+                if (ang == 0) G.slot0 = q; else if (ang == 45) G.slot1 = q; else if (ang == 90) G.slot2 = q; else G.slot3 = q;
+            }
+        G.usual = G.slot0 >= 0 && G.slot1 >= 0 && G.slot2 >= 0 && G.slot3 >= 0 && !G.symmetric;   // four angles, asymmetric counts
+        // lane-per-column sweeps (skip-column matrices): boxes up to a wave wide, and -- for the usual request -- boxes up to
+        // two waves wide with two columns per lane
+        G.dpp2 = B->glcm_offset == 1 && w > 64 && w <= 128 && G.usual;
+        G.dpp = (B->glcm_offset == 1 && w <= 64) || G.dpp2;
+        return G;
+    };
+    auto fast_zero = [&](const FastGlcm& G) {
+        for (int i = tid; i < G.na * (G.dpp ? G.cells : G.NN); i += BS)
+            s_P[i] = 0;
+    };
+    // shared: the sweep runs beside the chain (wave 0) and the entropy (wave 1) -- the row blocks of glcm_row_bounds; else equal blocks
+    auto fast_sweep = [&](const FastGlcm& G, const bool shared) {
+        const int na = G.na, Ng = G.Ng, NG1 = G.NG1, NN = G.NN, cells = G.cells;
+        const int slot0 = G.slot0, slot1 = G.slot1, slot2 = G.slot2, slot3 = G.slot3;
+        const bool symmetric = G.symmetric, usual = G.usual;
+        // the wave's contiguous block of rows (the two lane-per-column forms)
+        int r_begin, r_end;
+        if (shared) {
+            r_begin = (int)glcm_row_bounds(h, (uint32_t)wave);
+            r_end = (int)glcm_row_bounds(h, (uint32_t)wave + 1u);
+        } else {
+            r_begin = (int)glcm_row_bounds_even(h, (uint32_t)wave);
+            r_end = (int)glcm_row_bounds_even(h, (uint32_t)wave + 1u);
+        }
+        if (G.dpp2) {
+            // ---- boxes 65 .. 128 wide: lane = column and column + 64.  What crosses the boundary is wave-uniform (v_readlane):
+            // the E / SE neighbours of column 63 are column 64's, the SW neighbour of column 64 is column 63's.  Lanes whose second
+            // column lies beyond the box read a zero byte behind the plane (stride 0), like the lanes beyond a narrow box; the row
+            // below the last row is tested (the zero row behind the plane is 64 bytes, not 128).  (The per-pixel loop below
+            // made the co-occurrence sweep of a 65-wide box three times as expensive as a 63-wide one.)
+            const uint32_t ng1 = (uint32_t)NG1;
+            char* const T0 = (char*)(s_P + slot0 * cells);
+            char* const T1 = (char*)(s_P + slot1 * cells);
+            char* const T2 = (char*)(s_P + slot2 * cells);
+            char* const T3 = (char*)(s_P + slot3 * cells);
+            const bool in1 = (uint32_t)lane + 64u < w;
+            uint32_t adr0 = (uint32_t)r_begin * w + (uint32_t)lane;
+            uint32_t adr1 = in1 ? adr0 + 64u : area + (uint32_t)lane;
+            const uint32_t stride1 = in1 ? w : 0u;
+            uint32_t c0 = 0, c1 = 0;
+            if (r_begin < r_end) { c0 = (uint32_t)(*(const lds_u8_t*)adr0) << 2; c1 = (uint32_t)(*(const lds_u8_t*)adr1) << 2; }
+            auto pairs2 = [&](uint32_t c4, uint32_t e, uint32_t se, uint32_t sth, uint32_t sw) {
+                if (c4 != 0) {
+                    const uint32_t rowb = mul_u24_su(c4, ng1);
+                    atomicAdd((uint32_t*)(T0 + rowb + e), 1u);
+                    atomicAdd((uint32_t*)(T1 + rowb + se), 1u);
+                    atomicAdd((uint32_t*)(T2 + rowb + sth), 1u);
+                    atomicAdd((uint32_t*)(T3 + rowb + sw), 1u);
+                }
+            };
+            for (int row = r_begin; row < r_end; row++) {
+                adr0 += w; adr1 += stride1;
+                const bool below = row + 1 < (int)h;                                   // (wave-uniform)
+                const uint32_t n0 = (uint32_t)(*(const lds_u8_t*)adr0) << 2;           // row h reads the zero row behind the plane
+                const uint32_t r1 = (uint32_t)(*(const lds_u8_t*)adr1) << 2;
+                const uint32_t n1 = below ? r1 : 0u;
+                const uint32_t c1_0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)c1), n1_0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)n1);
+                const uint32_t n0_63 = readlane63(n0);
+                pairs2(c0, lane_plus1(c0, c1_0), lane_plus1(n0, n1_0), n0, lane_minus1_z(n0));
+                pairs2(c1, lane_plus1_z(c1), lane_plus1_z(n1), n1, lane_minus1(n1, n0_63));
+                c0 = n0; c1 = n1;
+            }
+        } else
+        if (G.dpp) {
+            const bool in_col = lane < (int)w;
+            const uint32_t ng1 = (uint32_t)NG1;
+            char* const T0 = (char*)(s_P + (slot0 >= 0 ? slot0 : 0) * cells);
+            char* const T1 = (char*)(s_P + (slot1 >= 0 ? slot1 : 0) * cells);
+            char* const T2 = (char*)(s_P + (slot2 >= 0 ? slot2 : 0) * cells);
+            char* const T3 = (char*)(s_P + (slot3 >= 0 ? slot3 : 0) * cells);
+            // a lane of the box walks its column of the plane (stride w), a lane beyond the box keeps reading one of the 64 zero
+            // bytes behind the last row (stride 0), and the row below the last row is that zero row: the read needs no test
+            uint32_t adr = in_col ? (uint32_t)r_begin * w + (uint32_t)lane : area + (uint32_t)lane - w;
+            const uint32_t stride = in_col ? w : 0u;
+            uint32_t cur4 = r_begin < r_end ? (uint32_t)(*(const lds_u8_t*)adr) << 2 : 0u;
+            adr += stride;
+            if (usual) {
+                // the usual request -- four angles, asymmetric: nothing but the four adds per row
+                auto pairs = [&](uint32_t c4, uint32_t n4) {
+                    const uint32_t nb_e = lane_plus1_z(c4), nb_se = lane_plus1_z(n4), nb_sw = lane_minus1_z(n4);
+                    if (c4 != 0) {        // skipped centres (a third of a disk's box) stay out: piled on one cell their adds serialise
+                        const uint32_t rowb = mul_u24_su(c4, ng1);
+                        atomicAdd((uint32_t*)(T0 + rowb + nb_e), 1u);
+                        atomicAdd((uint32_t*)(T1 + rowb + nb_se), 1u);
+                        atomicAdd((uint32_t*)(T2 + rowb + n4), 1u);
+                        atomicAdd((uint32_t*)(T3 + rowb + nb_sw), 1u);
+                    }
+                };
+                int row = r_begin;
+                for (; row + 1 < r_end; row += 2) {   // two rows per trip: the row below becomes the centre row without a move
+                    const uint32_t n4a = (uint32_t)(*(const lds_u8_t*)adr) << 2;
+                    pairs(cur4, n4a);
+                    const uint32_t n4b = (uint32_t)(*(const lds_u8_t*)(adr + stride)) << 2;
+                    pairs(n4a, n4b);
+                    cur4 = n4b;
+                    adr += 2 * stride;
+                }
+                if (row < r_end)
+                    pairs(cur4, (uint32_t)(*(const lds_u8_t*)adr) << 2);
+            } else {
+                const int has0 = slot0 >= 0, has1 = slot1 >= 0, has2 = slot2 >= 0, has3 = slot3 >= 0;
+                for (int row = r_begin; row < r_end; row++, adr += stride) {
+                    const uint32_t nxt4 = (uint32_t)(*(const lds_u8_t*)adr) << 2;
+                    const uint32_t nb_e = lane_plus1_z(cur4), nb_se = lane_plus1_z(nxt4), nb_sw = lane_minus1_z(nxt4);
+                    if (cur4 != 0) {
+                        const uint32_t rowb = mul_u24_su(cur4, ng1);
+                        if (has0) atomicAdd((uint32_t*)(T0 + rowb + nb_e), 1u);
+                        if (has1) atomicAdd((uint32_t*)(T1 + rowb + nb_se), 1u);
+                        if (has2) atomicAdd((uint32_t*)(T2 + rowb + nxt4), 1u);
+                        if (has3) atomicAdd((uint32_t*)(T3 + rowb + nb_sw), 1u);
+                        if (symmetric) {
+                            if (has0) atomicAdd((uint32_t*)(T0 + mul_u24_su(nb_e, ng1) + cur4), 1u);
+                            if (has1) atomicAdd((uint32_t*)(T1 + mul_u24_su(nb_se, ng1) + cur4), 1u);
+                            if (has2) atomicAdd((uint32_t*)(T2 + mul_u24_su(nxt4, ng1) + cur4), 1u);
+                            if (has3) atomicAdd((uint32_t*)(T3 + mul_u24_su(nb_sw, ng1) + cur4), 1u);
+                        }
+                    }
+                    cur4 = nxt4;
+                }
+            }
+        } else {
+            // any offset / boxes wider than a wave: rows dealt to waves, columns to lanes, plain Ng x Ng matrices (glcm.cpp:431-478)
+            for (int row = wave; row < (int)h; row += NW)
+                for (int col = lane; col < (int)w; col += 64) {
+                    const uint32_t lb = s_dense[(uint32_t)row * w + (uint32_t)col];
+                    if (lb == 0)
+                        continue;
+#pragma unroll
+                    for (int q = 0; q < kMaxAngles; q++) {
+                        if (q >= na)
+                            break;
+                        const int ang = B->glcm_angles[q];                 // glcm.cpp:234-255
+                        const int dx = ang == 90 ? 0 : ang == 135 ? -B->glcm_offset : B->glcm_offset, dy = ang == 0 ? 0 : B->glcm_offset;
+                        const int r2 = row + dy, c2 = col + dx;
+                        if (r2 < 0 || r2 >= (int)h || c2 < 0 || c2 >= (int)w)
+                            continue;
+                        const uint32_t la = s_dense[(uint32_t)r2 * w + (uint32_t)c2];
+                        if (la == 0)
+                            continue;
+                        atomicAdd(&s_P[q * NN + ((int)lb - 1) * Ng + (int)la - 1], 1u);
+                        if (symmetric)
+                            atomicAdd(&s_P[q * NN + ((int)la - 1) * Ng + (int)lb - 1], 1u);
+                    }
+                }
+        }
+    };
     // =====================================================================================
     // first-order intensity
     // =====================================================================================
@@ -1315,6 +1508,87 @@ __device__ __forceinline__ void roi_features_body(const RoiArgs& A, const uint64
 #endif
         uint32_t* const s_fm = (uint32_t*)(lds + B->L.fm);  // [count_cap >> fm_shift] first-moment prefixes of the table (FUSED; read late: see KView)
         uint32_t* const s_foff = (uint32_t*)(s_stat + 12);  // [5] first-moment offsets of the waves' table quarters | the whole table's first moment
+        // What the waves exchange at the end of the engine's scan (0: count total, 1: largest count, 2: its index, 3: first-moment total of
+        // the wave's quarter): slots 0..3 of the wave's exchange area -- but the overlapped builds run the engine straight behind the
+        // central-sum sweep, whose totals (slots 0..5 of every wave) lanes 0..5 of wave 0 may still be reading: there the four words
+        // go to slots 6 and 7 as 32-bit integers, and no barrier is needed between the two.
+        auto eng_put = [&](int k, uint32_t v) {
+            if (OVL) ((uint32_t*)(s_red + wave * 8 + 6))[k] = v;
+            else s_red[wave * 8 + k] = (double)v;
+        };
+        auto eng_get = [&](int wv, int k) -> uint32_t {
+            return OVL ? ((const uint32_t*)(s_red + wv * 8 + 6))[k] : (uint32_t)s_red[wv * 8 + k];
+        };
+        // central sums over the LDS-resident values (intensity.cpp:102-109, :177-183; M2..M4 of moments.h:53-74 equal the
+        // plain central sums).  FUSED launches take them in one sweep (behind the percentiles, or -- the overlapped builds -- in front of the
+        // engine: it needs only the mean); a blank ROI (all zeros) has every sum equal to zero and needs no sweep at all.
+        double acc[6] = {0, 0, 0, 0, 0, 0};
+        auto central_sweep = [&]() {
+            // ---- the one sweep over the resident values (16-bit offsets x = v - vmin): the six central sums (fp64, fused
+            // multiply-adds: the sums are tolerance-class).  The robust statistics come from the prefix tables.
+            const double meanx = mean - (double)vmin;       // deviations are taken in the offset domain: d = x - (mean - vmin)
+            auto px1 = [&](uint32_t x) {
+                const double d = (double)x - meanx;
+                const double d2 = d * d;
+                acc[0] += fabs(d);
+                acc[1] = __builtin_fma(d, d, acc[1]);
+                acc[2] = __builtin_fma(d2, d, acc[2]);
+                acc[3] = __builtin_fma(d2, d2, acc[3]);
+                const double d4 = d2 * d2;
+                acc[4] = __builtin_fma(d4, d, acc[4]);
+                acc[5] = __builtin_fma(d4, d2, acc[5]);
+            };
+            // the trip count is wave-uniform (n / 256 full trips, then the lanes below n % 256 once more): the loop control
+            // runs on the scalar unit and costs no vector instruction per value
+            const uint16_t* const pv = (const uint16_t*)s_val + tid;
+            const uint32_t n_full = (uint32_t)__builtin_amdgcn_readfirstlane((int)(n / BS)), n_rem = n - n_full * BS;
+            {   // (two values per trip: the second read sits at an immediate offset of the first, one address update per pair)
+                uint32_t k = 0;
+                for (; k + 1 < n_full; k += 2) { px1(pv[k * BS]); px1(pv[(k + 1) * BS]); }
+                if (k < n_full) px1(pv[k * BS]);
+            }
+            if ((uint32_t)tid < n_rem)
+                px1(pv[n_full * BS]);
+            // workgroup totals: the six fp64 sums through the transposed wave sum (slots 0..5 of the exchange area)
+            {
+                double t[8];
+#pragma unroll
+                for (int k = 0; k < 8; k++) t[k] = k < 6 ? acc[k] : 0.0;
+                const double tot = wave_transpose_sum8(t, lane);
+                if ((lane & 7) == 0 && (lane >> 3) < 6)
+                    s_red[wave * 8 + (lane >> 3)] = tot;
+            }
+            grp_sync<GS, NW>();
+            // the totals are read by the lanes that derive the outputs (deferring builds: a lane per total, into the record; the
+            // flag rises once the robust scalars are in it too: here when the sweep runs behind the chain, else behind the
+            // ROI's last barrier, in the GLCM block)
+            if (DEFER) {
+                if (tid < 6)
+                    rec[CR_ACC + tid] = xw_chain<NW>(s_red, tid);
+                if (!OVL && tid == 0)
+                    B->close_flag[roi] = 1u;
+            } else {
+                if (tid == 0) {
+                    double a6[6];
+#pragma unroll
+                    for (int k = 0; k < 6; k++) {
+                        a6[k] = xw_chain<NW>(s_red, k);
+                        asm volatile("" : "+v"(a6[k]) :: "memory");   // one total at a time: 28 reads in flight (or their adds sunk into the output code) would spill
+                    }
+                    close_central<CovDiv::ieee>(RowColumns{o}, a6, n, dn, mean, blank);
+                }
+                if (!OVL)
+                    grp_sync<GS, NW>();                // (the GLCM block may open with an exchange through s_red; the overlapped builds write none of the slots 0..5 again)
+            }
+        };
+        if (OVL) {
+            if (!blank)
+                central_sweep();
+            // the values are dead (a blank ROI's were never read): the matrices may take their place -- zeroed here, two barriers
+            // (the engine's) in front of the first count
+            if (ovl)
+                fast_zero(fast_cfg());
+        }
         if (use_count) {
             // ---- counting engine: per-wave inclusive prefix sums over s_cnt, in place (each
             // lane owns 4 consecutive entries of a 256-entry tile: one 16-byte LDS access each
@@ -1377,7 +1651,7 @@ __device__ __forceinline__ void roi_features_body(const RoiArgs& A, const uint64
                     }
                 }
                 if (FUSED && lane == 0)
-                    s_red[wave * 8 + 3] = (double)fcarry;
+                    eng_put(3, fcarry);
 #pragma unroll
                 for (int q = 1; q < 8; q++) kk[q] -= (uint32_t)q;      // (a key with count 0 never wins: the ROI has a pixel)
                 const uint32_t key = wave_max_u32(max(max(max(kk[0], kk[1]), max(kk[2], kk[3])), max(max(kk[4], kk[5]), max(kk[6], kk[7]))));
@@ -1427,23 +1701,23 @@ __device__ __forceinline__ void roi_features_body(const RoiArgs& A, const uint64
                 best_c = mc_w;
             }
             if (lane == 0) {
-                s_red[wave * 8 + 0] = (double)carry;
-                s_red[wave * 8 + 1] = (double)best_c;
-                s_red[wave * 8 + 2] = (double)best_i;
+                eng_put(0, carry);
+                eng_put(1, best_c);
+                eng_put(2, best_i);
             }
             grp_sync<GS, NW>();
             if (tid == 0) {
                 uint32_t mc = 0, mi = 0;
                 for (int wv = 0; wv < NW; wv++) {
-                    uint32_t c = (uint32_t)s_red[wv * 8 + 1], i = (uint32_t)s_red[wv * 8 + 2];
+                    uint32_t c = eng_get(wv, 1), i = eng_get(wv, 2);
                     if (c > mc) { mc = c; mi = i; } // waves cover ascending value ranges
                 }
-                const uint32_t woff1 = (uint32_t)s_red[0], woff2 = woff1 + (NW > 1 ? (uint32_t)s_red[8] : 0u), woff3 = woff2 + (NW > 1 ? (uint32_t)s_red[16] : 0u);
+                const uint32_t woff1 = eng_get(0, 0), woff2 = woff1 + (NW > 1 ? eng_get(1, 0) : 0u), woff3 = woff2 + (NW > 1 ? eng_get(2, 0) : 0u);
                 s_woff[0] = 0; s_woff[1] = woff1; s_woff[2] = woff2; s_woff[3] = woff3;
                 if (FUSED) {                          // the same for the first moments, and their total: the sum of all offsets x = v - vmin
-                    const uint32_t f1 = (uint32_t)s_red[3], f2 = f1 + (NW > 1 ? (uint32_t)s_red[8 + 3] : 0u), f3 = f2 + (NW > 1 ? (uint32_t)s_red[16 + 3] : 0u);
+                    const uint32_t f1 = eng_get(0, 3), f2 = f1 + (NW > 1 ? eng_get(1, 3) : 0u), f3 = f2 + (NW > 1 ? eng_get(2, 3) : 0u);
                     s_foff[0] = 0; s_foff[1] = f1; s_foff[2] = f2; s_foff[3] = f3;
-                    s_foff[4] = f3 + (NW > 1 ? (uint32_t)s_red[24 + 3] : 0u);
+                    s_foff[4] = f3 + (NW > 1 ? eng_get(3, 3) : 0u);
                 }
                 s_stat[S_MODE] = (double)(vmin + mi);
             }
@@ -1485,10 +1759,7 @@ __device__ __forceinline__ void roi_features_body(const RoiArgs& A, const uint64
             return grp8_sum(part) + s_fm[p >> fm_sh] + s_foff[wq];
         };
 
-        // central sums over the LDS-resident values (intensity.cpp:102-109, :177-183; M2..M4 of moments.h:53-74 equal the
-        // plain central sums).  FUSED launches take them in one sweep after the percentiles (see below); a blank ROI (all zeros)
-        // has every sum equal to zero and needs no sweep at all.
-        double acc[6] = {0, 0, 0, 0, 0, 0};
+        // (the central sums of the sort engines' builds, and the zero sums of a blank ROI; FUSED launches: central_sweep above)
         if (!FUSED || blank) {
             if (!blank) {
                 for (uint32_t i = tid; i < n; i += BS) {
@@ -1735,64 +2006,13 @@ __device__ __forceinline__ void roi_features_body(const RoiArgs& A, const uint64
                     o[I_UNIFORMITY] = u;
                 }
             }
-            grp_sync<GS, NW>();
+            if (!ovl)
+                grp_sync<GS, NW>();                    // (overlapped launches: the waves go on to their rows of the co-occurrence sweep, the GLCM block)
             STAMP(7);
 
             if (FUSED) {
-                // ---- the one sweep over the resident values (16-bit offsets x = v - vmin): the six central sums (fp64, fused
-                // multiply-adds: the sums are tolerance-class).  The robust statistics came from the prefix tables above.
-                const double meanx = mean - (double)vmin;       // deviations are taken in the offset domain: d = x - (mean - vmin)
-                auto px1 = [&](uint32_t x) {
-                    const double d = (double)x - meanx;
-                    const double d2 = d * d;
-                    acc[0] += fabs(d);
-                    acc[1] = __builtin_fma(d, d, acc[1]);
-                    acc[2] = __builtin_fma(d2, d, acc[2]);
-                    acc[3] = __builtin_fma(d2, d2, acc[3]);
-                    const double d4 = d2 * d2;
-                    acc[4] = __builtin_fma(d4, d, acc[4]);
-                    acc[5] = __builtin_fma(d4, d2, acc[5]);
-                };
-                // the trip count is wave-uniform (n / 256 full trips, then the lanes below n % 256 once more): the loop control
-                // runs on the scalar unit and costs no vector instruction per value
-                const uint16_t* const pv = (const uint16_t*)s_val + tid;
-                const uint32_t n_full = (uint32_t)__builtin_amdgcn_readfirstlane((int)(n / BS)), n_rem = n - n_full * BS;
-                {   // (two values per trip: the second read sits at an immediate offset of the first, one address update per pair)
-                    uint32_t k = 0;
-                    for (; k + 1 < n_full; k += 2) { px1(pv[k * BS]); px1(pv[(k + 1) * BS]); }
-                    if (k < n_full) px1(pv[k * BS]);
-                }
-                if ((uint32_t)tid < n_rem)
-                    px1(pv[n_full * BS]);
-                // workgroup totals: the six fp64 sums through the transposed wave sum (slots 0..5 of the exchange area)
-                {
-                    double t[8];
-#pragma unroll
-                    for (int k = 0; k < 8; k++) t[k] = k < 6 ? acc[k] : 0.0;
-                    const double tot = wave_transpose_sum8(t, lane);
-                    if ((lane & 7) == 0 && (lane >> 3) < 6)
-                        s_red[wave * 8 + (lane >> 3)] = tot;
-                }
-                grp_sync<GS, NW>();
-                // the totals are read by the lanes that derive the outputs (deferring builds: a lane per total, into the record; the
-                // robust scalars are in it already, so the flag may rise)
-                if (DEFER) {
-                    if (tid < 6)
-                        rec[CR_ACC + tid] = xw_chain<NW>(s_red, tid);
-                    if (tid == 0)
-                        B->close_flag[roi] = 1u;
-                } else {
-                    if (tid == 0) {
-                        double a6[6];
-#pragma unroll
-                        for (int k = 0; k < 6; k++) {
-                            a6[k] = xw_chain<NW>(s_red, k);
-                            asm volatile("" : "+v"(a6[k]) :: "memory");   // one total at a time: 28 reads in flight (or their adds sunk into the output code) would spill
-                        }
-                        close_central<CovDiv::ieee>(RowColumns{o}, a6, n, dn, mean, blank);
-                    }
-                    grp_sync<GS, NW>();                // (the GLCM block may open with an exchange through s_red)
-                }
+                if (!OVL)
+                    central_sweep();                   // (the overlapped builds took it in front of the engine)
             } else {
             // robust mean over p10..p90 (intensity.cpp:139-149 == histogram.h:90-101)
             const double p10 = s_stat[S_P10], p90 = s_stat[S_P90], median = s_stat[S_MEDIAN];
@@ -1823,6 +2043,8 @@ __device__ __forceinline__ void roi_features_body(const RoiArgs& A, const uint64
             }
             }
         }
+        // (overlapped builds: the record's flag rises in the GLCM block, behind the barrier that ends the interval the chain shares with the
+        //  co-occurrence sweep)
 
         STAMP(8);
     }
@@ -1837,163 +2059,36 @@ __device__ __forceinline__ void roi_features_body(const RoiArgs& A, const uint64
         // skip-column matrices).  Kept apart because the general block's loop structure and run-time cases cost this build
         // ~60 scalar-register spills per wave (each a vector instruction).
         double* o = out_row_l + B->col_glcm;
-        const int na = B->glcm_na;
-        const int Ng = greyInfo, NG1 = Ng + 1, NN = Ng * Ng, cells = NG1 * NG1;
+        const FastGlcm G = fast_cfg();
+        const int na = G.na, Ng = G.Ng, NG1 = G.NG1, NN = G.NN, cells = G.cells;
+        const bool dpp = G.dpp;
         // (the guard of glcm.cpp:27-95 on GLCM_GREYDEPTH: taken beside the mean when the intensity block runs, here when it does not)
         const bool degenerate = FAM == 3 ? bin_pixel(vmin, vmin, vmax, B->glcm_grey_depth) == bin_pixel(vmax, vmin, vmax, B->glcm_grey_depth) : s_stat[S_NG] != 0.0;
         if (tid == 0)
             B->glcm_ng[roi] = degenerate ? 0u : (uint32_t)Ng;
+        // (overlapped builds: wave 0 has filled the ROI's record -- sums beside the mean, central sums behind the sweep, robust scalars in
+        //  the chain -- and its first lane raises the flag behind the ROI's last barrier)
+        const bool raise = OVL_DEFER && !(vmin == 0 && vmax == 0) && tid == 0;
         if (degenerate) {                             // 0.0, not soft_nan: save_value() undoes the guard's assignments (glcm.cpp:210-215)
             for (int c = tid; c < kGlcmAngled * na + kGlcmAve; c += BS)
                 o[c] = 0.0;
-            return;
+            if (raise)
+                B->close_flag[roi] = 1u;
+            return;                                   // (a fact of the ROI: all four waves leave here, in front of the same barriers)
         }
-        const bool symmetric = B->glcm_symmetric != 0;
-        int slot0 = -1, slot1 = -1, slot2 = -1, slot3 = -1;
-#pragma unroll
-        for (int q = 0; q < kMaxAngles; q++)
-            if (q < na) {
-                const int ang = B->glcm_angles[q];
-                if (ang == 0) slot0 = q; else if (ang == 45) slot1 = q; else if (ang == 90) slot2 = q; else slot3 = q;
-            }
-        const bool usual = slot0 >= 0 && slot1 >= 0 && slot2 >= 0 && slot3 >= 0 && !symmetric;   // four angles, asymmetric counts
-        // lane-per-column sweeps (skip-column matrices): boxes up to a wave wide, and -- for the usual request -- boxes up to
-        // two waves wide with two columns per lane
-        const bool dpp2 = B->glcm_offset == 1 && w > 64 && w <= 128 && usual;
-        const bool dpp = (B->glcm_offset == 1 && w <= 64) || dpp2;
-        grp_sync<GS, NW>();
-        for (int i = tid; i < na * (dpp ? cells : NN); i += BS)
-            s_P[i] = 0;
-        grp_sync<GS, NW>();
+        if (!ovl) {
+            grp_sync<GS, NW>();
+            fast_zero(G);
+            grp_sync<GS, NW>();
+        }                                             // (overlapped launches: zeroed in front of the engine, two barriers back)
         STAMP(10);
-        if (dpp2) {
-            // ---- boxes 65 .. 128 wide: lane = column and column + 64.  What crosses the boundary is wave-uniform (v_readlane):
-            // the E / SE neighbours of column 63 are column 64's, the SW neighbour of column 64 is column 63's.  Lanes whose second
-            // column lies beyond the box read a zero byte behind the plane (stride 0), like the lanes beyond a narrow box; the row
-            // below the last row is tested (the zero row behind the plane is 64 bytes, not 128).  (The per-pixel loop below
-            // made the co-occurrence sweep of a 65-wide box three times as expensive as a 63-wide one.)
-            const int rows_per_wave = ((int)h + NW - 1) / NW;
-            const int r_begin = wave * rows_per_wave;
-            const int r_end = (r_begin + rows_per_wave) < (int)h ? (r_begin + rows_per_wave) : (int)h;
-            const uint32_t ng1 = (uint32_t)NG1;
-            char* const T0 = (char*)(s_P + slot0 * cells);
-            char* const T1 = (char*)(s_P + slot1 * cells);
-            char* const T2 = (char*)(s_P + slot2 * cells);
-            char* const T3 = (char*)(s_P + slot3 * cells);
-            const bool in1 = (uint32_t)lane + 64u < w;
-            uint32_t adr0 = (uint32_t)r_begin * w + (uint32_t)lane;
-            uint32_t adr1 = in1 ? adr0 + 64u : area + (uint32_t)lane;
-            const uint32_t stride1 = in1 ? w : 0u;
-            uint32_t c0 = 0, c1 = 0;
-            if (r_begin < r_end) { c0 = (uint32_t)(*(const lds_u8_t*)adr0) << 2; c1 = (uint32_t)(*(const lds_u8_t*)adr1) << 2; }
-            auto pairs2 = [&](uint32_t c4, uint32_t e, uint32_t se, uint32_t sth, uint32_t sw) {
-                if (c4 != 0) {
-                    const uint32_t rowb = mul_u24_su(c4, ng1);
-                    atomicAdd((uint32_t*)(T0 + rowb + e), 1u);
-                    atomicAdd((uint32_t*)(T1 + rowb + se), 1u);
-                    atomicAdd((uint32_t*)(T2 + rowb + sth), 1u);
-                    atomicAdd((uint32_t*)(T3 + rowb + sw), 1u);
-                }
-            };
-            for (int row = r_begin; row < r_end; row++) {
-                adr0 += w; adr1 += stride1;
-                const bool below = row + 1 < (int)h;                                   // (wave-uniform)
-                const uint32_t n0 = (uint32_t)(*(const lds_u8_t*)adr0) << 2;           // row h reads the zero row behind the plane
-                const uint32_t r1 = (uint32_t)(*(const lds_u8_t*)adr1) << 2;
-                const uint32_t n1 = below ? r1 : 0u;
-                const uint32_t c1_0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)c1), n1_0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)n1);
-                const uint32_t n0_63 = readlane63(n0);
-                pairs2(c0, lane_plus1(c0, c1_0), lane_plus1(n0, n1_0), n0, lane_minus1_z(n0));
-                pairs2(c1, lane_plus1_z(c1), lane_plus1_z(n1), n1, lane_minus1(n1, n0_63));
-                c0 = n0; c1 = n1;
-            }
-        } else
-        if (dpp) {
-            const int rows_per_wave = ((int)h + NW - 1) / NW;
-            const int r_begin = wave * rows_per_wave;
-            const int r_end = (r_begin + rows_per_wave) < (int)h ? (r_begin + rows_per_wave) : (int)h;
-            const bool in_col = lane < (int)w;
-            const uint32_t ng1 = (uint32_t)NG1;
-            char* const T0 = (char*)(s_P + (slot0 >= 0 ? slot0 : 0) * cells);
-            char* const T1 = (char*)(s_P + (slot1 >= 0 ? slot1 : 0) * cells);
-            char* const T2 = (char*)(s_P + (slot2 >= 0 ? slot2 : 0) * cells);
-            char* const T3 = (char*)(s_P + (slot3 >= 0 ? slot3 : 0) * cells);
-            // a lane of the box walks its column of the plane (stride w), a lane beyond the box keeps reading one of the 64 zero
-            // bytes behind the last row (stride 0), and the row below the last row is that zero row: the read needs no test
-            uint32_t adr = in_col ? (uint32_t)r_begin * w + (uint32_t)lane : area + (uint32_t)lane - w;
-            const uint32_t stride = in_col ? w : 0u;
-            uint32_t cur4 = r_begin < r_end ? (uint32_t)(*(const lds_u8_t*)adr) << 2 : 0u;
-            adr += stride;
-            if (usual) {
-                // the usual request -- four angles, asymmetric: nothing but the four adds per row
-                auto pairs = [&](uint32_t c4, uint32_t n4) {
-                    const uint32_t nb_e = lane_plus1_z(c4), nb_se = lane_plus1_z(n4), nb_sw = lane_minus1_z(n4);
-                    if (c4 != 0) {        // skipped centres (a third of a disk's box) stay out: piled on one cell their adds serialise
-                        const uint32_t rowb = mul_u24_su(c4, ng1);
-                        atomicAdd((uint32_t*)(T0 + rowb + nb_e), 1u);
-                        atomicAdd((uint32_t*)(T1 + rowb + nb_se), 1u);
-                        atomicAdd((uint32_t*)(T2 + rowb + n4), 1u);
-                        atomicAdd((uint32_t*)(T3 + rowb + nb_sw), 1u);
-                    }
-                };
-                int row = r_begin;
-                for (; row + 1 < r_end; row += 2) {   // two rows per trip: the row below becomes the centre row without a move
-                    const uint32_t n4a = (uint32_t)(*(const lds_u8_t*)adr) << 2;
-                    pairs(cur4, n4a);
-                    const uint32_t n4b = (uint32_t)(*(const lds_u8_t*)(adr + stride)) << 2;
-                    pairs(n4a, n4b);
-                    cur4 = n4b;
-                    adr += 2 * stride;
-                }
-                if (row < r_end)
-                    pairs(cur4, (uint32_t)(*(const lds_u8_t*)adr) << 2);
-            } else {
-                const int has0 = slot0 >= 0, has1 = slot1 >= 0, has2 = slot2 >= 0, has3 = slot3 >= 0;
-                for (int row = r_begin; row < r_end; row++, adr += stride) {
-                    const uint32_t nxt4 = (uint32_t)(*(const lds_u8_t*)adr) << 2;
-                    const uint32_t nb_e = lane_plus1_z(cur4), nb_se = lane_plus1_z(nxt4), nb_sw = lane_minus1_z(nxt4);
-                    if (cur4 != 0) {
-                        const uint32_t rowb = mul_u24_su(cur4, ng1);
-                        if (has0) atomicAdd((uint32_t*)(T0 + rowb + nb_e), 1u);
-                        if (has1) atomicAdd((uint32_t*)(T1 + rowb + nb_se), 1u);
-                        if (has2) atomicAdd((uint32_t*)(T2 + rowb + nxt4), 1u);
-                        if (has3) atomicAdd((uint32_t*)(T3 + rowb + nb_sw), 1u);
-                        if (symmetric) {
-                            if (has0) atomicAdd((uint32_t*)(T0 + mul_u24_su(nb_e, ng1) + cur4), 1u);
-                            if (has1) atomicAdd((uint32_t*)(T1 + mul_u24_su(nb_se, ng1) + cur4), 1u);
-                            if (has2) atomicAdd((uint32_t*)(T2 + mul_u24_su(nxt4, ng1) + cur4), 1u);
-                            if (has3) atomicAdd((uint32_t*)(T3 + mul_u24_su(nb_sw, ng1) + cur4), 1u);
-                        }
-                    }
-                    cur4 = nxt4;
-                }
-            }
-        } else {
-            // any offset / boxes wider than a wave: rows dealt to waves, columns to lanes, plain Ng x Ng matrices (glcm.cpp:431-478)
-            for (int row = wave; row < (int)h; row += NW)
-                for (int col = lane; col < (int)w; col += 64) {
-                    const uint32_t lb = s_dense[(uint32_t)row * w + (uint32_t)col];
-                    if (lb == 0)
-                        continue;
-#pragma unroll
-                    for (int q = 0; q < kMaxAngles; q++) {
-                        if (q >= na)
-                            break;
-                        const int ang = B->glcm_angles[q];                 // glcm.cpp:234-255
-                        const int dx = ang == 90 ? 0 : ang == 135 ? -B->glcm_offset : B->glcm_offset, dy = ang == 0 ? 0 : B->glcm_offset;
-                        const int r2 = row + dy, c2 = col + dx;
-                        if (r2 < 0 || r2 >= (int)h || c2 < 0 || c2 >= (int)w)
-                            continue;
-                        const uint32_t la = s_dense[(uint32_t)r2 * w + (uint32_t)c2];
-                        if (la == 0)
-                            continue;
-                        atomicAdd(&s_P[q * NN + ((int)lb - 1) * Ng + (int)la - 1], 1u);
-                        if (symmetric)
-                            atomicAdd(&s_P[q * NN + ((int)la - 1) * Ng + (int)lb - 1], 1u);
-                    }
-                }
-        }
+        // overlapped launches: no barrier since the engine's -- wave 0 arrives here behind the chain, wave 1 behind the entropy, waves 2
+        // and 3 at once, and the chain reads the counting table and the first-moment prefixes while the counts go into the matrices in
+        // front of them (LdsLayout::overlap)
+        fast_sweep(G, ovl);
         grp_sync<GS, NW>();
+        if (raise)
+            B->close_flag[roi] = 1u;
         STAMP(11);
         {
             uint32_t* dst = B->glcm_ws + roi * B->glcm_ws_stride;
@@ -3010,7 +3105,7 @@ int launch_roi_features(const RoiArgs& a, void* stream, uint32_t grid)
         else hipLaunchKernelGGL((roi_features_kernel<true, false, false, false>), dim3(grid), dim3(kBlock), a.L.gs_lds_bytes, st, a);
         return (int)hipGetLastError();
     }
-    if (knob::debug()) fprintf(stderr, "[nyxhip] features launch: g16 %u dense8 %u cnt16 %u ng_cap %u app %u total %u mask %u gd %d\n", a.L.g16, a.L.dense8, a.L.cnt16, a.L.ng_cap, a.L.app, a.L.total, a.mask, a.grey_depth);
+    if (knob::debug()) fprintf(stderr, "[nyxhip] features launch: g16 %u dense8 %u cnt16 %u ng_cap %u app %u total %u mask %u gd %d overlap %u\n", a.L.g16, a.L.dense8, a.L.cnt16, a.L.ng_cap, a.L.app, a.L.total, a.mask, a.grey_depth, a.L.overlap);
     // the smallest size class on its own kernel: a wave per ROI (roi_small.hip).  small_class: 1 = a list / filtered launch of class 0,
     // 2 = a whole-batch launch whose stated extrema promise class 0 only
     const bool no_small = knob::no_small();   // A/B knob

@@ -109,7 +109,35 @@ struct LdsLayout {
                          // buffer [sort_cap] and digit counts [4 * 256 + 4]; no counting table, no power-of-two padding of the values
     uint32_t radix_k16;  // 1: every range of the launch fits 16 bits -- the keys are 16-bit offsets from the ROI minimum, BOTH key buffers
                          // live in the value region ([2][sort_cap rounded up to 8] u16) and `radix` holds the digit counts only
+    uint32_t overlap;    // 1: the co-occurrence matrices of a <= 16-level launch (over the value buffer, from `P` on) end at or in front of
+                         // `cnt`, so the co-occurrence sweep may run while the order-statistics chain still reads the counting table and
+                         // the first-moment prefixes (roi_features_body, the overlapped builds); 0: the serial order
 };
+
+// ---- row blocks of the co-occurrence sweep (the lane-per-column forms of roi_features_body) ---------------------------------------
+// Wave k of the four takes rows [bounds(h, k), bounds(h, k + 1)) of a box h rows high; bounds(h, 0) = 0, bounds(h, 4) = h, monotone.
+// Equal blocks where the sweep has a barrier interval of its own.  In the overlapped builds wave 0 reaches the sweep behind the
+// order-statistics chain (about 270 vector instructions), wave 1 behind the n-bin bounds and the entropy (about 190), waves 2 and 3
+// at once, a row costs about 12.8: at the benchmark's 61 rows the four finish together when (780 + 270 + 190) / 4 = 310 instructions
+// fall to each -- 40, 120, 310 and 310 of them rows, the shares 1 : 3 : 8 : 8 of twenty (measured against 3 : 4 : 6 : 7 and equal
+// shares: profiles/r29_overlap_order.txt).
+#ifndef NYX_ROW_SHARES                  // (diagnostic builds: -DNYX_ROW_SHARES=a,b,c,d)
+#define NYX_ROW_SHARES 1, 3, 8, 8
+#endif
+constexpr uint32_t kGlcmRowShare[kWaves] = {NYX_ROW_SHARES};
+constexpr uint32_t kGlcmRowShareSum = kGlcmRowShare[0] + kGlcmRowShare[1] + kGlcmRowShare[2] + kGlcmRowShare[3];
+static_assert(kWaves == 4 && kGlcmRowShare[2] > 0 && kGlcmRowShare[3] > 0 && kGlcmRowShareSum <= 64, "the shares of waves 2 and 3 are positive; h * sum stays below 2^32");
+__host__ __device__ inline uint32_t glcm_row_bounds(uint32_t h, uint32_t k)
+{
+    constexpr uint32_t c1 = kGlcmRowShare[0], c2 = c1 + kGlcmRowShare[1], c3 = c2 + kGlcmRowShare[2];
+    const uint32_t cum = k == 0 ? 0u : k == 1 ? c1 : k == 2 ? c2 : k == 3 ? c3 : kGlcmRowShareSum;
+    return (h * cum) / kGlcmRowShareSum;
+}
+__host__ __device__ inline uint32_t glcm_row_bounds_even(uint32_t h, uint32_t k)
+{
+    const uint32_t per = (h + (uint32_t)kWaves - 1u) / (uint32_t)kWaves, b = k * per;
+    return b < h ? b : h;
+}
 
 // Window source of the fused tile path: when `inten` is set the feature kernel reads an ROI's pixels from its bounding-box
 // window of the tile stack (label match) instead of from x / y / inten clouds.

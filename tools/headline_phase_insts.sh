@@ -1,6 +1,8 @@
 #!/bin/bash
 # Vector / scalar / LDS instructions per wave of the metric kernel up to each phase boundary (tools/headline_phase_libs.sh builds the
 # libraries): one rocprofv3 --pmc pass per library, counters alone.  Output: gpurun_out/headline_phases.txt
+# The legend of the boundaries is in tools/headline_phase_libs.sh.  Since round 29 the chain, the entropy and the co-occurrence rows
+# share one barrier interval, so the steps 6 -> 7 and 10 -> 11 average over waves that do different work.
 export TMPDIR=/tmp
 OUT=$PWD/gpurun_out/headline_phases; rm -rf $OUT; mkdir -p $OUT
 for lib in $(ls $PWD/gpurun_scratch/libexit_*.so | sort -t_ -k2 -n) ""; do
