@@ -1,10 +1,12 @@
 """GLCM settings fuzz: angle subsets in any order, symmetric flag, offsets 1..4, grey depths around the split / 8-bit-plane
-thresholds, boxes narrower and wider than a wave -- against the oracle (INTENSITY + GLCM and GLCM alone)."""
+thresholds, boxes narrower and wider than a wave -- against the oracle (INTENSITY + GLCM and GLCM alone) and, in the
+columns that are rational in the integer matrix, against exact values (tests/glcm_exact_ref.py)."""
 import sys
 import numpy as np
 sys.path.insert(0, ".")
 from nyxus_amd import _abi, _lib
 from oracle import pyoracle as po
+from tests import glcm_exact_ref as gx
 from tests import parity, synth
 
 ctx = _lib.Context(0)
@@ -39,7 +41,9 @@ for rnd in range(rounds):
     except _lib.NyxHipError as e:
         print("round", rnd, "error", str(e)[:100]); bad_total += 1; continue
     O = po.oracle_featurize(b, mask, s)
-    bad = parity.compare_tables(G, O, _lib.column_names(mask, s))
+    names = _lib.column_names(mask, s)
+    bad = parity.compare_tables(G, O, names)
+    bad += [m for r in range(b.n_roi) for e in [gx.exact_glcm(b, r, s)] for m in gx.compare_glcm_exact(G[r], e, e.Ng, names, k, tag="roi %d " % r)]
     if bad:
         bad_total += 1
         print("round", rnd, "gd", gd, "ibsi", ibsi, "angles", angs, "off", s.glcm_offset, "sym", s.glcm_symmetric, "mask", mask, len(bad), bad[:2], flush=True)
