@@ -463,6 +463,80 @@ int nyxhip_imq_tiles(nyxhip_ctx* ctx, const nyxhip_tiles* tiles, const nyxhip_se
 int nyxhip_imq_slides(nyxhip_ctx* ctx, const nyxhip_tiles* slides, const nyxhip_settings* s,
                       double* out_table, size_t out_ld);
 
+/* ---- volumes (3-D): voxel intensity and 3-D GLCM -------------------------------
+ * The first two classes of the reference's `Feature3D` enum (featureset.h:643-797), behind entries and a family mask of their own:
+ * the 2-D mask, nyxhip_n_columns and nyxhip_column_name do not know them.
+ *   NYXHIP_VFAM_INTENSITY   D3_VoxelIntensityFeatures (features/3d_intensity.cpp:45-183): the 36 codes 3COV .. 3UNIFORMITY_PIU
+ *   NYXHIP_VFAM_GLCM        D3_GLCM_feature (features/3d_glcm.cpp): 30 angled codes over the 13 directions of shifts[] (:16-31) and
+ *                           the 29 _AVE codes save_value assigns (:147-175)
+ * Any other bit of a volume mask is NYXHIP_ERR_INVALID_ARG.
+ *
+ * COLUMNS.  The intensity block first (36 columns, Feature3D order, the reference's user-facing names: "3COV" ..), then the GLCM block:
+ * every angled code in Feature3D order (3GLCM_ACOR, 3GLCM_ASM, 3GLCM_CLUPROM ..) as 13 columns "<name>_<k>", k = 0 .. 12 the index
+ * into shifts[] = (dx, dy, dz): (1,1,1) (1,1,0) (1,1,-1) (1,0,1) (1,0,0) (1,0,-1) (1,-1,1) (1,-1,0) (1,-1,-1) (0,1,1) (0,1,0) (0,1,-1)
+ * (0,0,1); then the 29 _AVE codes in Feature3D order (3GLCM_ASM_AVE .. 3GLCM_SUMVARIANCE_AVE), one column each.  3GLCM_HOM2 has no _AVE
+ * code in the enum; every _AVE code the enum holds is assigned (the line 3d_glcm.cpp:176 repeats, commented out, what :170 assigns).
+ * An _AVE value is std::reduce over the 13 directional values / 13 (texture_feature.h:121-130), blank directions (soft_nan) included.
+ *
+ * SETTINGS, read with the meaning the 3-D classes give them:
+ *   grey_depth       |grey_depth| = bin count of the intensity block's histogram (3d_intensity.cpp:115)
+ *   ibsi             GLCM: no binning, levels are the intensities
+ *   glcm_grey_depth  GLCM binning (3d_glcm.cpp:51): > 0 matlab binning with that many levels, < 0 radiomics binning with |n| bins
+ *   glcm_offset      D3_GLCM_feature::offset, the class static (3d_glcm.cpp:8).  The reference's GLCM_OFFSET setting does not reach the
+ *                    3-D class (nothing assigns the static from it): a caller that mirrors the reference passes 1.  Must be >= 1.
+ *   glcm_symmetric   D3_GLCM_feature::symmetric_glcm, the class static (:9, read at :368); radiomics and IBSI binning count
+ *                    symmetrically whatever it says
+ *   soft_nan         the 30 values of a direction whose matrix is blank (:184-218), and every value of an ROI without voxels
+ *   glcm_n_angles / glcm_angles, tiny and the Gabor fields are not read.
+ * LIMITS.  A box side is at most 65534; a box holds at most NYXHIP_VOL_MAX_CELLS = 2^24 cells (256^3: the pair counts and the exact
+ * integer numerators of the closing formulas are 32-bit) and an ROI at most 2^32 - 1 voxels: beyond, NYXHIP_ERR_ROI_TOO_LARGE.  The
+ * co-occurrence matrix lives in LDS: more than NYXHIP_VOL_GLCM_MAX_LEVELS levels (|glcm_grey_depth|, or the largest intensity in IBSI
+ * mode) is NYXHIP_ERR_UNSUPPORTED, never a wrong row.  A voxel outside its box is never stored: NYXHIP_ERR_INVALID_ARG.
+ * Every row has the same bits whatever shares its call, chunk, memory kind or batch order. */
+enum {
+    NYXHIP_VFAM_INTENSITY = 1u << 0,
+    NYXHIP_VFAM_GLCM = 1u << 1,
+    NYXHIP_VFAM_ALL = 0x3
+};
+#define NYXHIP_VOL_GLCM_DIRECTIONS 13
+#define NYXHIP_VOL_GLCM_MAX_LEVELS 128
+#define NYXHIP_VOL_MAX_CELLS (1u << 24)
+
+/* SoA restatement of LR::raw_pixels_3D + LR::aux_image_cube, shaped like nyxhip_batch.  ROI r owns voxels
+ * [px_offset[r], px_offset[r+1]); coordinates are relative to the origin of the ROI's box. */
+typedef struct nyxhip_batch3d {
+    uint64_t n_roi;
+    const uint32_t* roi_label;   /* [n_roi]   LR::label (informational, may be NULL) */
+    const uint64_t* px_offset;   /* [n_roi+1] CSR offsets into x/y/z/inten     */
+    const uint16_t* x;           /* [n_px]    Pixel3::x - box origin           */
+    const uint16_t* y;
+    const uint16_t* z;
+    const uint32_t* inten;       /* [n_px]    Pixel3::inten                    */
+    const uint32_t* bbox_w;      /* [n_roi]   aux_image_cube width  (x)        */
+    const uint32_t* bbox_h;      /* [n_roi]   ... height (y)                   */
+    const uint32_t* bbox_d;      /* [n_roi]   ... depth  (z)                   */
+    const uint32_t* min_inten;   /* [n_roi]   LR::aux_min                      */
+    const uint32_t* max_inten;   /* [n_roi]   LR::aux_max                      */
+    const double* slide_min;     /* [n_roi] or NULL: slide_idx < 0, 3COVERED_IMAGE_INTENSITY_RANGE = 1 (3d_intensity.cpp:58-65) */
+    const double* slide_max;     /* [n_roi] or NULL                            */
+    int32_t memory;              /* NYXHIP_MEM_HOST | NYXHIP_MEM_DEVICE: where ALL pointers live */
+    /* Stated extrema; all three are derived when max_px == 0 (a device batch then costs one device->host copy of the boxes). */
+    uint32_t max_px;             /* max over ROIs of the voxel count           */
+    uint32_t max_bbox_cells;     /* max over ROIs of bbox_w * bbox_h * bbox_d  */
+    uint32_t max_inten_range;    /* max over ROIs of max_inten - min_inten     */
+    uint64_t max_device_bytes;   /* device workspace budget of the call (binned boxes, sort buffers); the ROIs run in chunks that
+                                    fit it.  0 = half of the free device memory.  One ROI that does not fit: NYXHIP_ERR_ROI_TOO_LARGE. */
+} nyxhip_batch3d;
+
+/* Column catalogue of a volume mask: the count (< 0: invalid mask) and the name of column `col`. */
+int nyxhip_vol_n_columns(uint32_t vol_mask, const nyxhip_settings* s);
+int nyxhip_vol_column_name(uint32_t vol_mask, const nyxhip_settings* s, int col, char* buf, size_t buf_len);
+
+/* One row of nyxhip_vol_n_columns(vol_mask, s) values per ROI.  Host batch: host table.  Device batch: device table.  Synchronous.
+ * NaN / inf are not replaced (nyxhip_finalize_table). */
+int nyxhip_featurize_volumes(nyxhip_ctx* ctx, const nyxhip_batch3d* batch, uint32_t vol_mask, const nyxhip_settings* s,
+                             double* out_table, size_t out_ld);
+
 /* ---- measurement hooks -------------------------------------------------------
  * Average device time (ms) per featurize call since the last nyxhip_timing_reset(),
  * measured with hipEvents recorded on the launch stream around EVERYTHING the call

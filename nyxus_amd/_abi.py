@@ -276,3 +276,141 @@ def batch_from_rois(rois: Sequence[dict]) -> HostBatch:
     else:
         hb.origin_unrepresentable = bool(rois)
     return hb
+
+
+# ---- volumes (3-D): nyxhip_batch3d, the volume mask (a mask space of its own) ------------------------------------------------------
+VFAM_INTENSITY = 1 << 0      # D3_VoxelIntensityFeatures: 3COV .. 3UNIFORMITY_PIU
+VFAM_GLCM = 1 << 1           # D3_GLCM_feature: 30 angled codes x 13 directions, 29 _AVE codes
+VFAM_ALL = 0x3
+VOL_GLCM_DIRECTIONS = 13
+VOL_GLCM_MAX_LEVELS = 128    # NYXHIP_VOL_GLCM_MAX_LEVELS: the co-occurrence matrix lives in LDS
+VOL_MAX_CELLS = 1 << 24      # NYXHIP_VOL_MAX_CELLS: the largest box (256^3 cells)
+
+
+class Batch3D(C.Structure):
+    """``nyxhip_batch3d`` (include/nyxhip.h)."""
+
+    _fields_ = [
+        ("n_roi", C.c_uint64),
+        ("roi_label", C.c_void_p),
+        ("px_offset", C.c_void_p),
+        ("x", C.c_void_p),
+        ("y", C.c_void_p),
+        ("z", C.c_void_p),
+        ("inten", C.c_void_p),
+        ("bbox_w", C.c_void_p),
+        ("bbox_h", C.c_void_p),
+        ("bbox_d", C.c_void_p),
+        ("min_inten", C.c_void_p),
+        ("max_inten", C.c_void_p),
+        ("slide_min", C.c_void_p),
+        ("slide_max", C.c_void_p),
+        ("memory", C.c_int32),
+        ("max_px", C.c_uint32),
+        ("max_bbox_cells", C.c_uint32),
+        ("max_inten_range", C.c_uint32),
+        ("max_device_bytes", C.c_uint64),
+    ]
+
+
+@dataclass
+class HostBatch3D:
+    """A host-memory batch of volumetric ROIs: keeps the NumPy arrays alive next to the C struct."""
+
+    roi_label: np.ndarray
+    px_offset: np.ndarray
+    x: np.ndarray
+    y: np.ndarray
+    z: np.ndarray
+    inten: np.ndarray
+    bbox_w: np.ndarray
+    bbox_h: np.ndarray
+    bbox_d: np.ndarray
+    min_inten: np.ndarray
+    max_inten: np.ndarray
+    slide_min: Optional[np.ndarray] = None
+    slide_max: Optional[np.ndarray] = None
+
+    def __post_init__(self):
+        self.roi_label = np.ascontiguousarray(self.roi_label, np.uint32)
+        self.px_offset = np.ascontiguousarray(self.px_offset, np.uint64)
+        for name in ("x", "y", "z"):
+            setattr(self, name, np.ascontiguousarray(getattr(self, name), np.uint16))
+        for name in ("inten", "bbox_w", "bbox_h", "bbox_d", "min_inten", "max_inten"):
+            setattr(self, name, np.ascontiguousarray(getattr(self, name), np.uint32))
+        if self.slide_min is not None:
+            self.slide_min = np.ascontiguousarray(self.slide_min, np.float64)
+            self.slide_max = np.ascontiguousarray(self.slide_max, np.float64)
+        if len(self.px_offset) != len(self.roi_label) + 1:
+            raise ValueError("px_offset must have n_roi+1 entries")
+        if int(self.px_offset[-1]) != len(self.inten) or not (len(self.x) == len(self.y) == len(self.z) == len(self.inten)):
+            raise ValueError("x / y / z / inten length must equal px_offset[-1]")
+
+    @property
+    def n_roi(self) -> int:
+        return len(self.roi_label)
+
+    def counts(self) -> np.ndarray:
+        return np.diff(self.px_offset.astype(np.int64))
+
+    def cells(self) -> np.ndarray:
+        return self.bbox_w.astype(np.int64) * self.bbox_h.astype(np.int64) * self.bbox_d.astype(np.int64)
+
+    def c_struct(self, stated: bool = False, max_device_bytes: int = 0) -> Batch3D:
+        """stated: fill the batch extrema (max_px, max_bbox_cells, max_inten_range); otherwise the library derives them."""
+        b = Batch3D()
+        b.n_roi = self.n_roi
+        for name in ("roi_label", "px_offset", "x", "y", "z", "inten", "bbox_w", "bbox_h", "bbox_d", "min_inten", "max_inten"):
+            setattr(b, name, getattr(self, name).ctypes.data)
+        b.slide_min = self.slide_min.ctypes.data if self.slide_min is not None else None
+        b.slide_max = self.slide_max.ctypes.data if self.slide_max is not None else None
+        b.memory = MEM_HOST
+        if stated and self.n_roi:
+            live = self.counts() > 0
+            b.max_px = int(self.counts().max())
+            b.max_bbox_cells = int(self.cells()[live].max()) if live.any() else 1
+            b.max_inten_range = int((self.max_inten.astype(np.int64) - self.min_inten.astype(np.int64)).max())
+        b.max_device_bytes = int(max_device_bytes)
+        return b
+
+    def select(self, idx) -> "HostBatch3D":
+        """The ROIs `idx` (any order) as a batch of their own."""
+        idx = [int(i) for i in idx]
+        off = self.px_offset.astype(np.int64)
+        sl = [slice(off[i], off[i + 1]) for i in idx]
+        cat = lambda a: np.concatenate([a[s] for s in sl]) if sl else a[:0]
+        pick = lambda a: a[idx] if idx else a[:0]
+        return HostBatch3D(pick(self.roi_label), np.concatenate([[0], np.cumsum([s.stop - s.start for s in sl])]).astype(np.uint64),
+                           cat(self.x), cat(self.y), cat(self.z), cat(self.inten), pick(self.bbox_w), pick(self.bbox_h), pick(self.bbox_d),
+                           pick(self.min_inten), pick(self.max_inten),
+                           pick(self.slide_min) if self.slide_min is not None else None, pick(self.slide_max) if self.slide_max is not None else None)
+
+
+def batch3d_from_rois(rois: Sequence[dict]) -> HostBatch3D:
+    """Builds a HostBatch3D from dicts with keys x, y, z (any origin), inten and optionally label / box (w, h, d) / origin (x0, y0, z0) /
+    min / max / slide_min / slide_max.  Coordinates are re-based to the box; min / max come from the voxels.  An ROI without voxels needs
+    `box`."""
+    lab, offs, xs, ys, zs, it, bw, bh, bd, mn, mx, s0, s1 = [], [0], [], [], [], [], [], [], [], [], [], [], []
+    for k, r in enumerate(rois):
+        x, y, z = (np.asarray(r[c], np.int64) for c in "xyz")
+        v = np.asarray(r["inten"], np.uint32)
+        if len(v):
+            x0, y0, z0 = r.get("origin", (x.min(), y.min(), z.min()))
+            box = r.get("box", (x.max() - x0 + 1, y.max() - y0 + 1, z.max() - z0 + 1))
+        else:
+            x0 = y0 = z0 = 0
+            box = r["box"]
+        xs.append((x - x0).astype(np.uint16)); ys.append((y - y0).astype(np.uint16)); zs.append((z - z0).astype(np.uint16))
+        it.append(v)
+        bw.append(int(box[0])); bh.append(int(box[1])); bd.append(int(box[2]))
+        mn.append(int(r.get("min", v.min() if len(v) else 0)))
+        mx.append(int(r.get("max", v.max() if len(v) else 0)))
+        lab.append(int(r.get("label", k + 1)))
+        offs.append(offs[-1] + len(v))
+        if "slide_min" in r:
+            s0.append(float(r["slide_min"])); s1.append(float(r["slide_max"]))
+    slide = len(s0) == len(rois) and len(rois) > 0
+    cat = lambda parts, dt: np.concatenate(parts).astype(dt) if parts else np.zeros(0, dt)
+    return HostBatch3D(np.array(lab, np.uint32), np.array(offs, np.uint64), cat(xs, np.uint16), cat(ys, np.uint16), cat(zs, np.uint16), cat(it, np.uint32),
+                       np.array(bw, np.uint32), np.array(bh, np.uint32), np.array(bd, np.uint32), np.array(mn, np.uint32), np.array(mx, np.uint32),
+                       np.array(s0) if slide else None, np.array(s1) if slide else None)

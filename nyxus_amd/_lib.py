@@ -32,6 +32,7 @@ ABI_SYMBOLS = [
     "nyxhip_ih_column_name", "nyxhip_ih_batch", "nyxhip_ih_tiles",
     "nyxhip_featurize_slides",
     "nyxhip_imq_column_name", "nyxhip_imq_batch", "nyxhip_imq_tiles", "nyxhip_imq_slides",
+    "nyxhip_vol_n_columns", "nyxhip_vol_column_name", "nyxhip_featurize_volumes",
 ]
 
 
@@ -141,6 +142,13 @@ def load() -> C.CDLL:
         lib.nyxhip_imq_tiles.restype = C.c_int
         lib.nyxhip_imq_slides.argtypes = [C.c_void_p, P(_abi.Tiles), P(_abi.Settings), C.c_void_p, C.c_size_t]
         lib.nyxhip_imq_slides.restype = C.c_int
+    if hasattr(lib, "nyxhip_featurize_volumes"):  # (absent from older builds of the ABI selected through NYXHIP_LIB for A/B runs)
+        lib.nyxhip_vol_n_columns.argtypes = [C.c_uint32, P(_abi.Settings)]
+        lib.nyxhip_vol_n_columns.restype = C.c_int
+        lib.nyxhip_vol_column_name.argtypes = [C.c_uint32, P(_abi.Settings), C.c_int, C.c_char_p, C.c_size_t]
+        lib.nyxhip_vol_column_name.restype = C.c_int
+        lib.nyxhip_featurize_volumes.argtypes = [C.c_void_p, P(_abi.Batch3D), C.c_uint32, P(_abi.Settings), C.c_void_p, C.c_size_t]
+        lib.nyxhip_featurize_volumes.restype = C.c_int
     if hasattr(lib, "nyxhip_featurize_slides"):  # (absent from older builds of the ABI selected through NYXHIP_LIB for A/B runs)
         lib.nyxhip_featurize_slides.argtypes = [C.c_void_p, P(_abi.Tiles), C.c_uint32, P(_abi.Settings), C.c_void_p, C.c_size_t]
         lib.nyxhip_featurize_slides.restype = C.c_int
@@ -199,6 +207,22 @@ def imq_column_names() -> List[str]:
         rc = lib.nyxhip_imq_column_name(i, buf, 128)
         if rc != 0:
             raise NyxHipError(rc, f"image-quality column {i}")
+        out.append(buf.value.decode())
+    return out
+
+
+def vol_column_names(vmask: int, s: _abi.Settings) -> List[str]:
+    """The columns of nyxhip_featurize_volumes for a volume mask (_abi.VFAM_*)."""
+    lib = load()
+    n = lib.nyxhip_vol_n_columns(vmask, C.byref(s))
+    if n < 0:
+        raise NyxHipError(1, f"bad volume mask {vmask:#x}")
+    buf = C.create_string_buffer(128)
+    out = []
+    for i in range(n):
+        rc = lib.nyxhip_vol_column_name(vmask, C.byref(s), i, buf, 128)
+        if rc != 0:
+            raise NyxHipError(rc, f"volume column {i}")
         out.append(buf.value.decode())
     return out
 
@@ -342,6 +366,20 @@ class Context:
         labels = np.zeros(n.value, np.uint32); tiles = np.zeros(n.value, np.uint32); table = np.empty((n.value, ncol), np.float64)
         self._check(self._lib.nyxhip_fetch_result(self._h, labels.ctypes.data, tiles.ctypes.data, table.ctypes.data, ncol))
         return tiles, labels, table
+
+    def volumes_host(self, batch: _abi.HostBatch3D, vmask: int, s: _abi.Settings, stated: bool = False, max_device_bytes: int = 0) -> np.ndarray:
+        """The volume table [n_roi x nyxhip_vol_n_columns] of a host batch (nyxhip_featurize_volumes); NaN / inf are left in place."""
+        ncol = self._lib.nyxhip_vol_n_columns(vmask, C.byref(s))
+        if ncol < 0:
+            raise NyxHipError(1, f"bad volume mask {vmask:#x}")
+        out = np.empty((batch.n_roi, ncol), np.float64)
+        cb = batch.c_struct(stated=stated, max_device_bytes=max_device_bytes)
+        self._check(self._lib.nyxhip_featurize_volumes(self._h, C.byref(cb), vmask, C.byref(s), out.ctypes.data, ncol))
+        return out
+
+    def volumes_device(self, cb: _abi.Batch3D, vmask: int, s: _abi.Settings, out_ptr: int, ld: int):
+        """Device pointers in ``cb`` and a device table; synchronous (nyxhip_featurize_volumes)."""
+        self._check(self._lib.nyxhip_featurize_volumes(self._h, C.byref(cb), vmask, C.byref(s), C.c_void_p(out_ptr), ld))
 
     def imq_host(self, batch: _abi.HostBatch, s: _abi.Settings) -> np.ndarray:
         """The image-quality columns [n_roi x 4] of a host batch (nyxhip_imq_batch); NaN / inf are left in place."""

@@ -9,6 +9,7 @@
 //   nyxhip_neighbors.hip the neighbor entries: column names, the launches over a device-resident batch, nyxhip_neighbors_batch
 //   nyxhip_ih.hip        the intensity-histogram entries: column names, the launches over a device-resident batch, nyxhip_ih_batch
 //   nyxhip_imq.hip       the image-quality entries: column names, the launches over a device-resident batch, nyxhip_imq_batch / _slides
+//   nyxhip_vol.hip       the volume entries: column catalogue of the volume mask, chunks under the budget, nyxhip_featurize_volumes
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -34,6 +35,7 @@
 #include "roi_neighbors.h"
 #include "roi_ih.h"
 #include "roi_imq.h"
+#include "roi_vol.h"
 
 // One hipMalloc allocation, grow-only.  hipFree waits for the device's work by itself; the stream handed to reserve() states which
 // work the site knows to be using the old block.
@@ -166,6 +168,7 @@ struct nyxhip_ctx {
     DeferredBufs d_chords;             // roi_chords.hip: plane beyond LDS, or zero-intensity pixels
     DeferredBufs d_erosion;            // roi_erosion.hip: two bit planes beyond the LDS planes
     DeferredBufs d_imq;                // roi_imq.hip (nyxhip_imq.hip): intensity planes beyond the LDS plane
+    DevBuf d_vol;                      // roi_vol.hip (nyxhip_vol.hip): binned boxes and sort buffers of a chunk of volumes
     // neighbor entries (roi_neighbors.hip): geometry table + candidate counts and offsets | candidate lists, minima, flags
     DevBuf d_nb_geo;
     DevBuf d_nb_cand;
