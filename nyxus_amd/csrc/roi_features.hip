@@ -915,6 +915,59 @@ __device__ __forceinline__ void roi_features_body(const RoiArgs& A, const uint64
         return;
     }
 
+    // ---- the rotated cloud loader (ROTATE): the compact family sets -- occ8 / fam7 / fam6 -- on cloud launches ----------------
+    // The trips of a ROI (phase 1 below: four pixels per thread, twelve loads, 1024 pixels of the workgroup) do not queue up behind
+    // each other.  `issue` loads pixel u of a trip into its three registers; as soon as `consume` has read pixel u of one trip,
+    // pixel u of the NEXT trip is loaded into the same registers, so a ROI of three trips exposes one HBM round trip instead of
+    // three.  HOIST: the first trip is issued here, behind the last early return, in front of the phase-0 clears and their barrier
+    // (nothing in phase 0 is an input of a load; every LDS write of the pass is in the consume half).
+    // Loads beyond the ROI -- the trip behind a last FULL one -- lie past the descriptors' num_records: they return 0 without a
+    // memory access and are never consumed.  The hoisted trip keeps x and y as the 16-bit values the loads return and is widened
+    // behind the barrier (`first`): widened where it is loaded, the widening is sunk towards its use, as far as the block of the
+    // phase-0 barrier, and waits for the loads there.  Inside a loop of one block the widening stays with its load and is free.
+    // The generic tiers, the workspace launches, the 17..64-level builds and the window loaders keep the serial loop (`trip`).
+    constexpr int kU = 4;
+#ifdef NYX_NO_TRIP_ROTATE
+    constexpr bool ROTATE = false;
+#else
+    constexpr bool ROTATE = (FAM == 1 || FAM == 2 || FAM == 3) && !GS && !G16 && WIN != 1;
+#endif
+    // (an early-exit build that ends at boundary 0 leaves with no load in flight: tools/headline_phase_libs.sh)
+#if defined(NYX_NO_TRIP_HOIST) || (defined(NYX_EXIT_AT) && NYX_EXIT_AT <= 0)
+    constexpr bool HOIST = false;
+#else
+    constexpr bool HOIST = ROTATE;
+#endif
+    struct Trip { uint32_t v[kU], px[kU], py[kU]; };
+    struct Trip16 { uint32_t v[kU]; uint16_t px[kU], py[kU]; };
+    struct Cloud { __amdgpu_buffer_rsrc_t v, x, y; };
+    [[maybe_unused]] Trip rot{};                       // the trip in flight
+    [[maybe_unused]] Trip16 first{};                   // ... the hoisted one, as loaded
+    [[maybe_unused]] Cloud cl;
+    [[maybe_unused]] auto issue_to = [&](auto& t, int u, uint32_t base) {
+        const uint32_t i = base + u * BS + tid;
+        t.v[u] = __builtin_amdgcn_raw_buffer_load_b32(cl.v, (int)(i * 4u), 0, 0);
+        if (do_glcm) {
+            t.px[u] = (uint16_t)__builtin_amdgcn_raw_buffer_load_b16(cl.x, (int)(i * 2u), 0, 0);
+            t.py[u] = (uint16_t)__builtin_amdgcn_raw_buffer_load_b16(cl.y, (int)(i * 2u), 0, 0);
+        }
+        __builtin_amdgcn_sched_barrier(0);             // (the compiler gathers the loads of a trip into one cluster otherwise)
+    };
+    [[maybe_unused]] auto issue = [&](int u, uint32_t base) { issue_to(rot, u, base); };
+    if constexpr (ROTATE) {
+        cl.v = __builtin_amdgcn_make_buffer_rsrc((void*)(A.inten + off), 0, (int)(n * 4u), 0x00020000);
+        cl.x = __builtin_amdgcn_make_buffer_rsrc((void*)(A.x + off), 0, (int)(n * 2u), 0x00020000);
+        cl.y = __builtin_amdgcn_make_buffer_rsrc((void*)(A.y + off), 0, (int)(n * 2u), 0x00020000);
+    }
+    if constexpr (HOIST) {
+        bool cloud = true;                             // WIN == 2: a launch fact, known here
+        if constexpr (WIN != 0) cloud = A.win.inten == nullptr;
+        if (cloud) {
+#pragma unroll
+            for (int u = 0; u < kU; u++) issue_to(first, u, 0u);
+        }
+    }
+
     // grey binning used by the co-occurrence scan (glcm.cpp:354,379-385)
     const int greyInfo = A.ibsi ? 0 : A.grey_depth;
     if (FAST) __builtin_assume(greyInfo > 0 && greyInfo <= 16);
@@ -949,6 +1002,7 @@ __device__ __forceinline__ void roi_features_body(const RoiArgs& A, const uint64
     if (tid < 16)
         s_stat[tid] = 0.0;
     grp_sync<GS, NW>();
+    if constexpr (HOIST) __builtin_amdgcn_sched_barrier(0);   // (the hoisted trip is widened BEHIND the barrier: see `first`)
 
     STAMP(0);
     // ---- phase 1: the only pass over HBM ------------------------------------------------
@@ -958,8 +1012,7 @@ __device__ __forceinline__ void roi_features_body(const RoiArgs& A, const uint64
     // use, so one HBM round trip covers 1024 pixels of the workgroup
     // The cloud is read through buffer descriptors sized to this ROI (raw buffers, num_records in bytes): lanes past the last
     // pixel get 0 from the bounds check of the load itself -- no compare, branch or 64-bit address per load, and the twelve
-    // loads of a trip issue back to back.
-    constexpr int kU = 4;
+    // loads of a trip issue back to back.  (The serial trip: the round trips of a ROI one behind the other.  Not the ROTATE builds.)
     const bool small_v = vmax < (1u << 24);
     const __amdgpu_buffer_rsrc_t rs_v = __builtin_amdgcn_make_buffer_rsrc((void*)(A.inten + off), 0, (int)(n * 4u), 0x00020000);
     const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc((void*)(A.x + off), 0, (int)(n * 2u), 0x00020000);
@@ -969,6 +1022,7 @@ __device__ __forceinline__ void roi_features_body(const RoiArgs& A, const uint64
     //   FULL  every lane of the trip has a pixel (all trips but the last);
     //   NZ    the ROI has no zero intensity (vmin > 0): the co-occurrence scan's "original intensity 0 is skipped" test vanishes;
     //   TINY  vmax < 2^15: the four values / squares of a trip sum in 32 bits, one 64-bit add per trip instead of per pixel.
+    // (`consume` below restates the per-pixel body for the rotated loader: a change to one belongs in the other.)
     auto trip = [&](auto full_c, auto nz_c, auto tiny_c, uint32_t base) {
         constexpr bool FULL = decltype(full_c)::value, NZ = decltype(nz_c)::value, TINY = decltype(tiny_c)::value;
         uint32_t v[kU], px[kU], py[kU];
@@ -1026,6 +1080,51 @@ __device__ __forceinline__ void roi_features_body(const RoiArgs& A, const uint64
             }
         }
         if (TINY) { sum += s32; sumsq += q32; }
+    };
+    // The same per-pixel work for pixel u of the trip in flight (ROTATE: 16-bit tables, 8-bit plane, matlab binning at <= 16 levels
+    // or no co-occurrence plane at all -- what `trip` does in these builds, the LDS writes and the integer sums the same).
+    [[maybe_unused]] auto consume = [&](auto full_c, auto nz_c, auto tiny_c, int u, uint32_t base, uint32_t& s32, uint32_t& q32) {
+        if constexpr (ROTATE) {
+            static_assert(C16 && D8 && (FAM == 2 || FAST), "the rotated loader serves the compact builds only");
+            constexpr bool FULL = decltype(full_c)::value, NZ = decltype(nz_c)::value, TINY = decltype(tiny_c)::value;
+            const uint32_t i = base + u * BS + tid, val = rot.v[u];
+            if (!FULL && i >= n)
+                return;
+            if (do_int) {
+                ((uint16_t*)s_val)[i] = (uint16_t)(val - vmin);
+                const uint32_t sq = (TINY || small_v) ? (uint32_t)__umul24(val, val) : (uint32_t)(val * val);
+                if (TINY) { s32 += val; q32 += sq; }
+                else { sum += val; sumsq += sq; }
+                const uint32_t ci = val - vmin;
+                atomicAdd(cnt16_word(s_cnt, ci), 1u << (16 * (ci & 1u)));
+            }
+            if (do_glcm) {
+                uint32_t lvl = 0;
+                if (NZ || val != 0) {
+                    const uint32_t sc = (uint32_t)(mslope * (double)val + 1.0);
+                    lvl = sc > (uint32_t)greyInfo ? (uint32_t)greyInfo : sc;
+                }
+                const uint32_t cell = __umul24(rot.py[u], w) + rot.px[u];
+                *(lds_u8_t*)(cell < area ? cell : area + 64) = (uint8_t)lvl;
+            }
+        }
+    };
+    // A rotated trip: its loads are in flight; behind the consume of pixel u, `next_c` says whether pixel u of the following trip
+    // is loaded into the registers that just became free.
+    [[maybe_unused]] auto trip_rot = [&](auto full_c, auto nz_c, auto tiny_c, auto next_c, uint32_t base) {
+        uint32_t s32 = 0, q32 = 0;
+#pragma unroll
+        for (int u = 0; u < kU; u++) {
+            consume(full_c, nz_c, tiny_c, u, base, s32, q32);
+            // (the sums take pixel u HERE: gathered into one add at the trip's end, the values outlive their registers, and the
+            //  copies that save them wait for the whole trip in front of the first consume)
+            if (!do_int) { }
+            else if (decltype(tiny_c)::value) asm volatile("" : "+v"(s32), "+v"(q32));
+            else asm volatile("" : "+v"(sum), "+v"(sumsq));
+            __builtin_amdgcn_sched_barrier(0);
+            if (decltype(next_c)::value) issue(u, base + kU * BS);
+        }
+        if (decltype(tiny_c)::value) { sum += s32; sumsq += q32; }
     };
     bool from_window = false;
     if constexpr (WIN != 0 && !GS) {
@@ -1222,6 +1321,33 @@ __device__ __forceinline__ void roi_features_body(const RoiArgs& A, const uint64
         using T = std::true_type; using F = std::false_type;
         const bool nz = vmin > 0, tiny = vmax < (1u << 15);
         uint32_t base = 0;
+        if constexpr (ROTATE) {
+            auto widen = [&] {                         // (each form for itself: see `first`)
+                if constexpr (HOIST) {
+#pragma unroll
+                    for (int u = 0; u < kU; u++) { rot.v[u] = first.v[u]; rot.px[u] = first.px[u]; rot.py[u] = first.py[u]; }
+                } else {
+#pragma unroll
+                    for (int u = 0; u < kU; u++) issue(u, 0u);
+                }
+            };
+            if (nz && tiny) {
+                widen();
+                for (; base + kU * BS <= n; base += kU * BS) trip_rot(T{}, T{}, T{}, T{}, base);
+                if (base < n) trip_rot(F{}, T{}, T{}, F{}, base);
+            } else {
+                // (the trips in the loop are full ones: no per-pixel test, so the loop is one block.  The last trip stands behind
+                //  the loop and issues nothing; a wave that skips one of its consumes skips that consume's wait, and the compiler
+                //  would count those loads as in flight in every later wait, the other form's loop included -- the forms share
+                //  blocks.  s_waitcnt vmcnt(0), nothing else, settles the count.)
+                widen();
+                for (; base + kU * BS < n; base += kU * BS) trip_rot(T{}, F{}, F{}, T{}, base);
+                trip_rot(F{}, F{}, F{}, F{}, base);
+                // gfx9 s_waitcnt immediate: vmcnt = 0 (bits 3:0 and 15:14), expcnt = 7 (6:4) and lgkmcnt = 15 (11:8) at their maxima, i.e. not waited for
+                constexpr int kWaitVmcnt0 = 0x0F70;
+                __builtin_amdgcn_s_waitcnt(kWaitVmcnt0);
+            }
+        } else
         if (nz && tiny) {
             for (; base + kU * BS <= n; base += kU * BS) trip(T{}, T{}, T{}, base);
             if (base < n) trip(F{}, T{}, T{}, base);

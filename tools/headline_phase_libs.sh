@@ -9,6 +9,10 @@
 #   (no barrier: a wave that leaves at 7 has not waited for the others) | 8, 9, 10 nothing | 11 the wave's rows of the co-occurrence
 #   sweep (glcm_row_bounds: 3, 9, 24 and 25 of the benchmark's 61 rows) and the barrier that ends the interval | 12 counts exported.
 # So 6 -> 7 and 10 -> 11 are per-wave figures of waves that do different work: read them per wave role, not as workgroup phases.
+# Since round 32 the cloud launches of these builds issue the first trip's loads IN FRONT of phase 0 and rotate the trips (section 4.1 of
+# DESIGN.md).  The build that ends at boundary 0 issues no loads (the hoist is compiled out for NYX_EXIT_AT <= 0), so libexit_0 is still
+# "prologue, clears, barrier" and leaves with nothing in flight; 0 -> 1 is then the load pass WITH its first round trip, which the full
+# kernel has partly behind it when it reaches boundary 0.  Read 0 -> 1 as an upper bound of the load pass, not as its share.
 # Launches whose carve-out does not allow the overlap (LdsLayout::overlap = 0), and a library built with -DNYX_NO_OVERLAP, keep a
 # barrier at 7 and the zeroing pair in front of 10; every other build of the body keeps the round-6 order.
 cd $(dirname $0)/../nyxus_amd/csrc
