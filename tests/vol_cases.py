@@ -1,6 +1,8 @@
 """Inputs of the volume tests (tests/test_vol_cpu.py, tests/test_vol_gpu.py) and of tests/golden/vol/make_vol_golden.py: batches of
 volumetric ROIs rebuilt from seeds, the settings they run under, and the one rule that takes values out of the comparison with the
-reference.  The shapes are the smallest at which the kernels of roi_vol.hip can go wrong.
+reference.  The cases were chosen for the reference's behaviour (blank directions, the binning modes, the level cap, the LDS-staging seam)
+and are what is recorded; the kernels' own seams (lane-sharing widths, rows per wave, the presence map, tail words, the chunk bound, the
+voxel sort and the mode search) are the cases of tests/vol_edge_cases.py, which are held to exact values and need no recording.
 
 BATCHES
   boxes   1x1x1 (no pair in any direction) | 2x1x1, 1x2x1, 1x1x2 (one direction has pairs) | 2x2x2 full | the slab 7x5x1 (every dz != 0
