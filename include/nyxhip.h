@@ -537,6 +537,50 @@ int nyxhip_vol_column_name(uint32_t vol_mask, const nyxhip_settings* s, int col,
 int nyxhip_featurize_volumes(nyxhip_ctx* ctx, const nyxhip_batch3d* batch, uint32_t vol_mask, const nyxhip_settings* s,
                              double* out_table, size_t out_ld);
 
+/* ---- volumes (3-D): GLDM, NGLDM and NGTDM -----------------------------------
+ * Three more classes of the reference's Feature3D enum on the batch type of the volume entries, behind entries and a mask space of their
+ * own (the volume mask keeps its two bits):
+ *   NYXHIP_VTEX_GLDM    D3_GLDM_feature (features/3d_gldm.cpp): 14 codes 3GLDM_SDE .. 3GLDM_LDHGLE.  26 shifts, a voxel counts itself.
+ *   NYXHIP_VTEX_NGLDM   D3_NGLDM_feature (features/3d_ngldm.cpp): 19 codes 3NGLDM_LDE .. 3NGLDM_DCENE (3NGLDM_DCP before 3NGLDM_GLM, as in
+ *                       the enum).  24 shifts (none straight up or down), over every interior cell of the box, off-ROI cells included.
+ *   NYXHIP_VTEX_NGTDM   D3_NGTDM_feature (features/3d_ngtdm.cpp): 5 codes 3NGTDM_COARSENESS .. 3NGTDM_STRENGTH over the cube of Chebyshev
+ *                       radius ngtdm_radius, background cells summed too.
+ * The blocks of a row stand in that order.  SETTINGS READ.  nyxhip_settings: ibsi, soft_nan, grey_depth (NGLDM: to_grayscale(v, 0,
+ * max_inten, grey_depth) on every cell of the box; the value is read as unsigned, as the reference's parameter is, so a negative one
+ * exceeds the level cap).  nyxhip_voltex_settings: the three slots below; GLDM and NGTDM bin with greyInfo = ibsi ? 0 : <class>_grey_depth
+ * (> 0 matlab levels, < 0 radiomics bins, 0 none).  The reference starts all three at 0 (env_features.cpp:712-736).
+ * soft_nan is written where the classes assign it: a flat ROI (GLDM, NGLDM), no dependence zone (GLDM), fewer than two levels (NGTDM);
+ * and in every column of an ROI without voxels.  Other NaN / inf stay (nyxhip_finalize_table).  ngtdm_radius == 0 is legal: no voxel has
+ * a neighbour, every code is NaN (soft_nan with fewer than two levels), and the level cap does not apply to the NGTDM block.
+ * A cloud names each cell of its box at most once.
+ * LIMITS.  Those of the volume entries (side, NYXHIP_VOL_MAX_CELLS, stated extrema, max_device_bytes, voxels outside their box), and:
+ * the level tables live in LDS, so more than NYXHIP_VOLTEX_MAX_LEVELS levels is NYXHIP_ERR_UNSUPPORTED, never a wrong row --
+ * |gldm_grey_depth|, |ngtdm_grey_depth| and grey_depth are checked on the host, the largest intensity of an ROI (IBSI mode, or a grey
+ * depth of 0) on the device; ngtdm_radius outside 0 .. NYXHIP_VOLTEX_MAX_RADIUS is NYXHIP_ERR_UNSUPPORTED.
+ * Every sum that more than one thread adds to is an integer: a row has the same bits whatever shares its call, chunk, memory kind or
+ * batch order. */
+enum {
+    NYXHIP_VTEX_GLDM = 1u << 0,
+    NYXHIP_VTEX_NGLDM = 1u << 1,
+    NYXHIP_VTEX_NGTDM = 1u << 2,
+    NYXHIP_VTEX_ALL = 0x7
+};
+#define NYXHIP_VOLTEX_MAX_LEVELS 128
+#define NYXHIP_VOLTEX_MAX_RADIUS 3
+typedef struct nyxhip_voltex_settings {
+    int32_t gldm_grey_depth;     /* NyxSetting::GLDM_GREYDEPTH of fsett_D3_GLDM   */
+    int32_t ngtdm_grey_depth;    /* NyxSetting::NGTDM_GREYDEPTH of fsett_D3_NGTDM */
+    int32_t ngtdm_radius;        /* NyxSetting::NGTDM_RADIUS: Chebyshev radius of the cube gather_zones scans */
+} nyxhip_voltex_settings;
+
+/* Column catalogue of a texture mask: the count (< 0: invalid mask, 0 or any foreign bit) and the name of column `col`. */
+int nyxhip_voltex_n_columns(uint32_t tex_mask);
+int nyxhip_voltex_column_name(uint32_t tex_mask, int col, char* buf, size_t buf_len);
+
+/* One row of nyxhip_voltex_n_columns(tex_mask) values per ROI.  Host batch: host table.  Device batch: device table.  Synchronous. */
+int nyxhip_featurize_volumes_tex(nyxhip_ctx* ctx, const nyxhip_batch3d* batch, uint32_t tex_mask, const nyxhip_settings* s,
+                                 const nyxhip_voltex_settings* t, double* out_table, size_t out_ld);
+
 /* ---- measurement hooks -------------------------------------------------------
  * Average device time (ms) per featurize call since the last nyxhip_timing_reset(),
  * measured with hipEvents recorded on the launch stream around EVERYTHING the call

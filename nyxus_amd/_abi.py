@@ -14,6 +14,7 @@ from typing import Optional, Sequence
 import numpy as np
 
 NYXHIP_OK = 0
+ERR_UNSUPPORTED = 4
 ERR_NAMES = {0: "OK", 1: "INVALID_ARG", 2: "NO_DEVICE", 3: "HIP", 4: "UNSUPPORTED", 5: "ROI_TOO_LARGE"}
 
 FAM_INTENSITY = 1 << 0
@@ -285,6 +286,18 @@ VFAM_ALL = 0x3
 VOL_GLCM_DIRECTIONS = 13
 VOL_GLCM_MAX_LEVELS = 128    # NYXHIP_VOL_GLCM_MAX_LEVELS: the co-occurrence matrix lives in LDS
 VOL_MAX_CELLS = 1 << 24      # NYXHIP_VOL_MAX_CELLS: the largest box (256^3 cells)
+# the texture mask of nyxhip_featurize_volumes_tex (a mask space of its own)
+VTEX_GLDM = 1 << 0           # D3_GLDM_feature: 3GLDM_SDE .. 3GLDM_LDHGLE
+VTEX_NGLDM = 1 << 1          # D3_NGLDM_feature: 3NGLDM_LDE .. 3NGLDM_DCENE
+VTEX_NGTDM = 1 << 2          # D3_NGTDM_feature: 3NGTDM_COARSENESS .. 3NGTDM_STRENGTH
+VTEX_ALL = 0x7
+VOLTEX_MAX_LEVELS = 128      # NYXHIP_VOLTEX_MAX_LEVELS: the level tables live in LDS
+VOLTEX_MAX_RADIUS = 3        # NYXHIP_VOLTEX_MAX_RADIUS
+
+
+class VolTexSettings(C.Structure):
+    """``nyxhip_voltex_settings`` (include/nyxhip.h); all three start at 0, as in the reference (env_features.cpp:712-736)."""
+    _fields_ = [("gldm_grey_depth", C.c_int32), ("ngtdm_grey_depth", C.c_int32), ("ngtdm_radius", C.c_int32)]
 
 
 class Batch3D(C.Structure):

@@ -33,6 +33,7 @@ ABI_SYMBOLS = [
     "nyxhip_featurize_slides",
     "nyxhip_imq_column_name", "nyxhip_imq_batch", "nyxhip_imq_tiles", "nyxhip_imq_slides",
     "nyxhip_vol_n_columns", "nyxhip_vol_column_name", "nyxhip_featurize_volumes",
+    "nyxhip_voltex_n_columns", "nyxhip_voltex_column_name", "nyxhip_featurize_volumes_tex",
 ]
 
 
@@ -149,6 +150,13 @@ def load() -> C.CDLL:
         lib.nyxhip_vol_column_name.restype = C.c_int
         lib.nyxhip_featurize_volumes.argtypes = [C.c_void_p, P(_abi.Batch3D), C.c_uint32, P(_abi.Settings), C.c_void_p, C.c_size_t]
         lib.nyxhip_featurize_volumes.restype = C.c_int
+    if hasattr(lib, "nyxhip_featurize_volumes_tex"):
+        lib.nyxhip_voltex_n_columns.argtypes = [C.c_uint32]
+        lib.nyxhip_voltex_n_columns.restype = C.c_int
+        lib.nyxhip_voltex_column_name.argtypes = [C.c_uint32, C.c_int, C.c_char_p, C.c_size_t]
+        lib.nyxhip_voltex_column_name.restype = C.c_int
+        lib.nyxhip_featurize_volumes_tex.argtypes = [C.c_void_p, P(_abi.Batch3D), C.c_uint32, P(_abi.Settings), P(_abi.VolTexSettings), C.c_void_p, C.c_size_t]
+        lib.nyxhip_featurize_volumes_tex.restype = C.c_int
     if hasattr(lib, "nyxhip_featurize_slides"):  # (absent from older builds of the ABI selected through NYXHIP_LIB for A/B runs)
         lib.nyxhip_featurize_slides.argtypes = [C.c_void_p, P(_abi.Tiles), C.c_uint32, P(_abi.Settings), C.c_void_p, C.c_size_t]
         lib.nyxhip_featurize_slides.restype = C.c_int
@@ -223,6 +231,22 @@ def vol_column_names(vmask: int, s: _abi.Settings) -> List[str]:
         rc = lib.nyxhip_vol_column_name(vmask, C.byref(s), i, buf, 128)
         if rc != 0:
             raise NyxHipError(rc, f"volume column {i}")
+        out.append(buf.value.decode())
+    return out
+
+
+def voltex_column_names(tmask: int) -> List[str]:
+    """The columns of nyxhip_featurize_volumes_tex for a texture mask (_abi.VTEX_*)."""
+    lib = load()
+    n = lib.nyxhip_voltex_n_columns(tmask)
+    if n < 0:
+        raise NyxHipError(1, f"bad volume texture mask {tmask:#x}")
+    buf = C.create_string_buffer(128)
+    out = []
+    for i in range(n):
+        rc = lib.nyxhip_voltex_column_name(tmask, i, buf, 128)
+        if rc != 0:
+            raise NyxHipError(rc, f"volume texture column {i}")
         out.append(buf.value.decode())
     return out
 
@@ -380,6 +404,21 @@ class Context:
     def volumes_device(self, cb: _abi.Batch3D, vmask: int, s: _abi.Settings, out_ptr: int, ld: int):
         """Device pointers in ``cb`` and a device table; synchronous (nyxhip_featurize_volumes)."""
         self._check(self._lib.nyxhip_featurize_volumes(self._h, C.byref(cb), vmask, C.byref(s), C.c_void_p(out_ptr), ld))
+
+    def volumes_tex_host(self, batch: _abi.HostBatch3D, tmask: int, s: _abi.Settings, t: _abi.VolTexSettings, stated: bool = False,
+                         max_device_bytes: int = 0) -> np.ndarray:
+        """The texture table [n_roi x nyxhip_voltex_n_columns] of a host batch (nyxhip_featurize_volumes_tex); NaN / inf are left in place."""
+        ncol = self._lib.nyxhip_voltex_n_columns(tmask)
+        if ncol < 0:
+            raise NyxHipError(1, f"bad volume texture mask {tmask:#x}")
+        out = np.empty((batch.n_roi, ncol), np.float64)
+        cb = batch.c_struct(stated=stated, max_device_bytes=max_device_bytes)
+        self._check(self._lib.nyxhip_featurize_volumes_tex(self._h, C.byref(cb), tmask, C.byref(s), C.byref(t), out.ctypes.data, ncol))
+        return out
+
+    def volumes_tex_device(self, cb: _abi.Batch3D, tmask: int, s: _abi.Settings, t: _abi.VolTexSettings, out_ptr: int, ld: int):
+        """Device pointers in ``cb`` and a device table; synchronous (nyxhip_featurize_volumes_tex)."""
+        self._check(self._lib.nyxhip_featurize_volumes_tex(self._h, C.byref(cb), tmask, C.byref(s), C.byref(t), C.c_void_p(out_ptr), ld))
 
     def imq_host(self, batch: _abi.HostBatch, s: _abi.Settings) -> np.ndarray:
         """The image-quality columns [n_roi x 4] of a host batch (nyxhip_imq_batch); NaN / inf are left in place."""

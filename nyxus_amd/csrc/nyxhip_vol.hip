@@ -2,6 +2,7 @@
 // nyxhip_vol_column_name) and nyxhip_featurize_volumes: checks, staging of a host batch, chunks of ROIs under the device budget, the
 // launches of roi_vol.hip.
 #include "nyxhip_ctx.h"
+#include "vol_host.h"
 
 using namespace nyxhip;
 
@@ -67,13 +68,8 @@ int vol_device(nyxhip_ctx* ctx, const nyxhip_batch3d* b, uint32_t vmask, const n
     a.box_stride = glcm ? al256(a.max_cells) : 0;
     a.key_stride = inten ? (al256(4 * (size_t)a.max_px) >> 2) : 0;
     const size_t per_roi = a.box_stride + 8 * (size_t)a.key_stride;
-    size_t budget = (size_t)b->max_device_bytes;
-    if (budget == 0) {
-        size_t fr = 0, tot = 0;
-        HIP_TRY(ctx, hipMemGetInfo(&fr, &tot));
-        const int sharers = std::max(1, g_ctx_on_device[ctx->device & 63].load());
-        budget = (fr + ctx->d_vol.bytes) / 2 / (size_t)sharers;
-    }
+    size_t budget = 0;
+    if (int rc = vol_budget(ctx, b, ctx->d_vol.bytes, budget)) return rc;
     if (per_roi > budget)
         return fail(ctx, NYXHIP_ERR_ROI_TOO_LARGE, "volumes: the workspace of one ROI (" + std::to_string(per_roi) + " bytes) does not fit max_device_bytes");
     const uint64_t chunk = std::min<uint64_t>(std::min<uint64_t>(budget / per_roi, 65535), b->n_roi);   // (a grid dimension counts the ROIs of a chunk)
@@ -90,6 +86,22 @@ int vol_device(nyxhip_ctx* ctx, const nyxhip_batch3d* b, uint32_t vmask, const n
         }
         if (inten)
             if (int rc = launch_vol_intensity(a, st)) return fail(ctx, NYXHIP_ERR_HIP, std::string("voxel-intensity kernel: launch failed: ") + hipGetErrorString((hipError_t)rc));
+    }
+    return NYXHIP_OK;
+}
+
+} // namespace
+
+namespace nyxhip {
+
+int vol_budget(nyxhip_ctx* ctx, const nyxhip_batch3d* b, size_t held, size_t& budget)
+{
+    budget = (size_t)b->max_device_bytes;
+    if (budget == 0) {
+        size_t fr = 0, tot = 0;
+        HIP_TRY(ctx, hipMemGetInfo(&fr, &tot));
+        const int sharers = std::max(1, g_ctx_on_device[ctx->device & 63].load());
+        budget = (fr + held) / 2 / (size_t)sharers;
     }
     return NYXHIP_OK;
 }
@@ -113,53 +125,10 @@ int vol_scan(nyxhip_ctx* ctx, uint64_t nr, const uint64_t* off, const uint32_t* 
     return NYXHIP_OK;
 }
 
-} // namespace
-
-extern "C" {
-
-int nyxhip_vol_n_columns(uint32_t vmask, const nyxhip_settings* s)
+// what both volume entries do behind their own checks: the extrema (stated or derived), the staging of a host batch into one device
+// slab, `body` on the device batch, the copy back, the device status through `check`.  `glcm`: the entry reads coordinates and boxes.
+int vol_run(nyxhip_ctx* ctx, const nyxhip_batch3d* b, bool glcm, size_t ncol, double* out, size_t ld, const VolBody& body, int (*check)(nyxhip_ctx*))
 {
-    (void)s;
-    return vol_mask_ok(vmask) ? vol_cols(vmask) : -1;
-}
-
-int nyxhip_vol_column_name(uint32_t vmask, const nyxhip_settings* s, int col, char* buf, size_t buf_len)
-{
-    (void)s;
-    if (!buf || buf_len == 0 || !vol_mask_ok(vmask) || col < 0 || col >= vol_cols(vmask)) return NYXHIP_ERR_INVALID_ARG;
-    if (vmask & NYXHIP_VFAM_INTENSITY) {
-        if (col < kVolIntensityCols) { snprintf(buf, buf_len, "3%s", kVolIntensityNames[col]); return NYXHIP_OK; }
-        col -= kVolIntensityCols;
-    }
-    if (col < kVolGlcmAngled * kVolDirs) snprintf(buf, buf_len, "3GLCM_%s_%d", kVolGlcmNames[col / kVolDirs], col % kVolDirs);
-    else snprintf(buf, buf_len, "3GLCM_%s_AVE", kVolGlcmAveNames[col - kVolGlcmAngled * kVolDirs]);
-    return NYXHIP_OK;
-}
-
-int nyxhip_featurize_volumes(nyxhip_ctx* ctx, const nyxhip_batch3d* b, uint32_t vmask, const nyxhip_settings* s, double* out, size_t ld)
-{
-    if (!ctx) return NYXHIP_ERR_INVALID_ARG;
-    if (!b || !s || !out) return fail(ctx, NYXHIP_ERR_INVALID_ARG, "null batch / settings / out_table");
-    if (!vol_mask_ok(vmask)) return fail(ctx, NYXHIP_ERR_INVALID_ARG, "bad volume mask: NYXHIP_VFAM_INTENSITY | NYXHIP_VFAM_GLCM are the bits it has");
-    const bool glcm = (vmask & NYXHIP_VFAM_GLCM) != 0, inten = (vmask & NYXHIP_VFAM_INTENSITY) != 0;
-    if (b->n_roi && (!b->px_offset || !b->inten || !b->min_inten || !b->max_inten || (glcm && (!b->x || !b->y || !b->z || !b->bbox_w || !b->bbox_h || !b->bbox_d))))
-        return fail(ctx, NYXHIP_ERR_INVALID_ARG, "batch has null array pointers (px_offset, inten, min_inten, max_inten; for the GLCM block also x, y, z, bbox_w, bbox_h, bbox_d)");
-    if ((b->slide_min == nullptr) != (b->slide_max == nullptr)) return fail(ctx, NYXHIP_ERR_INVALID_ARG, "slide_min and slide_max must both be given or both NULL");
-    const size_t ncol = (size_t)vol_cols(vmask);
-    if (ld < ncol) return fail(ctx, NYXHIP_ERR_INVALID_ARG, "out_ld smaller than the column count");
-    if (b->n_roi > 0x7FFFFFFFull) return fail(ctx, NYXHIP_ERR_INVALID_ARG, "too many ROIs in one batch");
-    if (b->memory != NYXHIP_MEM_DEVICE && b->memory != NYXHIP_MEM_HOST) return fail(ctx, NYXHIP_ERR_INVALID_ARG, "bad batch->memory");
-    if (inten) {
-        if (s->grey_depth == 0) return fail(ctx, NYXHIP_ERR_INVALID_ARG, "grey_depth must be non-zero (histogram bin count)");
-        if ((uint32_t)abs(s->grey_depth) > kVolMaxHistBins)
-            return fail(ctx, NYXHIP_ERR_UNSUPPORTED, "volumes: the intensity histogram takes at most " + std::to_string(kVolMaxHistBins) + " bins");
-    }
-    if (glcm) {
-        if (s->glcm_offset < 1) return fail(ctx, NYXHIP_ERR_INVALID_ARG, "glcm_offset must be >= 1");
-        if (!s->ibsi && (uint32_t)abs(s->glcm_grey_depth) > kVolLevelCap)
-            return fail(ctx, NYXHIP_ERR_UNSUPPORTED, "volumes: the 3-D GLCM matrix lives in LDS up to " + std::to_string(kVolLevelCap) + " levels; |glcm_grey_depth| = " +
-                                                         std::to_string(abs(s->glcm_grey_depth)) + " exceeds that cap");
-    }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (b->n_roi == 0) return NYXHIP_OK;
     hipStream_t st = ctx->stream();
@@ -186,9 +155,9 @@ int nyxhip_featurize_volumes(nyxhip_ctx* ctx, const nyxhip_batch3d* b, uint32_t 
         }
         nyxhip_batch3d d = *b;
         if (!glcm) { d.x = d.y = d.z = nullptr; d.bbox_w = d.bbox_h = d.bbox_d = nullptr; }
-        if (int rc = vol_device(ctx, &d, vmask, s, out, ld, max_px, max_cells)) return rc;
+        if (int rc = body(d, out, ld, max_px, max_cells)) return rc;
         HIP_TRY(ctx, hipStreamSynchronize(st));
-        return vol_check_status(ctx);
+        return check(ctx);
     }
 
     // host batch: check the arrays, stage them into one device slab, run, copy the table back
@@ -237,10 +206,62 @@ int nyxhip_featurize_volumes(nyxhip_ctx* ctx, const nyxhip_batch3d* b, uint32_t 
     d.min_inten = (const uint32_t*)(base + o_mn); d.max_inten = (const uint32_t*)(base + o_mx);
     if (slide) { d.slide_min = (const double*)(base + o_s0); d.slide_max = (const double*)(base + o_s1); }
     double* const d_out = (double*)(base + o_out);
-    if (int rc = vol_device(ctx, &d, vmask, s, d_out, ncol, max_px, max_cells)) { (void)hipStreamSynchronize(st); return rc; }
+    if (int rc = body(d, d_out, ncol, max_px, max_cells)) { (void)hipStreamSynchronize(st); return rc; }
     HIP_TRY(ctx, hipMemcpy2DAsync(out, ld * sizeof(double), d_out, ncol * sizeof(double), ncol * sizeof(double), nr, hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, hipStreamSynchronize(st));
-    return vol_check_status(ctx);
+    return check(ctx);
+}
+
+} // namespace nyxhip
+
+extern "C" {
+
+int nyxhip_vol_n_columns(uint32_t vmask, const nyxhip_settings* s)
+{
+    (void)s;
+    return vol_mask_ok(vmask) ? vol_cols(vmask) : -1;
+}
+
+int nyxhip_vol_column_name(uint32_t vmask, const nyxhip_settings* s, int col, char* buf, size_t buf_len)
+{
+    (void)s;
+    if (!buf || buf_len == 0 || !vol_mask_ok(vmask) || col < 0 || col >= vol_cols(vmask)) return NYXHIP_ERR_INVALID_ARG;
+    if (vmask & NYXHIP_VFAM_INTENSITY) {
+        if (col < kVolIntensityCols) { snprintf(buf, buf_len, "3%s", kVolIntensityNames[col]); return NYXHIP_OK; }
+        col -= kVolIntensityCols;
+    }
+    if (col < kVolGlcmAngled * kVolDirs) snprintf(buf, buf_len, "3GLCM_%s_%d", kVolGlcmNames[col / kVolDirs], col % kVolDirs);
+    else snprintf(buf, buf_len, "3GLCM_%s_AVE", kVolGlcmAveNames[col - kVolGlcmAngled * kVolDirs]);
+    return NYXHIP_OK;
+}
+
+int nyxhip_featurize_volumes(nyxhip_ctx* ctx, const nyxhip_batch3d* b, uint32_t vmask, const nyxhip_settings* s, double* out, size_t ld)
+{
+    if (!ctx) return NYXHIP_ERR_INVALID_ARG;
+    if (!b || !s || !out) return fail(ctx, NYXHIP_ERR_INVALID_ARG, "null batch / settings / out_table");
+    if (!vol_mask_ok(vmask)) return fail(ctx, NYXHIP_ERR_INVALID_ARG, "bad volume mask: NYXHIP_VFAM_INTENSITY | NYXHIP_VFAM_GLCM are the bits it has");
+    const bool glcm = (vmask & NYXHIP_VFAM_GLCM) != 0, inten = (vmask & NYXHIP_VFAM_INTENSITY) != 0;
+    if (b->n_roi && (!b->px_offset || !b->inten || !b->min_inten || !b->max_inten || (glcm && (!b->x || !b->y || !b->z || !b->bbox_w || !b->bbox_h || !b->bbox_d))))
+        return fail(ctx, NYXHIP_ERR_INVALID_ARG, "batch has null array pointers (px_offset, inten, min_inten, max_inten; for the GLCM block also x, y, z, bbox_w, bbox_h, bbox_d)");
+    if ((b->slide_min == nullptr) != (b->slide_max == nullptr)) return fail(ctx, NYXHIP_ERR_INVALID_ARG, "slide_min and slide_max must both be given or both NULL");
+    const size_t ncol = (size_t)vol_cols(vmask);
+    if (ld < ncol) return fail(ctx, NYXHIP_ERR_INVALID_ARG, "out_ld smaller than the column count");
+    if (b->n_roi > 0x7FFFFFFFull) return fail(ctx, NYXHIP_ERR_INVALID_ARG, "too many ROIs in one batch");
+    if (b->memory != NYXHIP_MEM_DEVICE && b->memory != NYXHIP_MEM_HOST) return fail(ctx, NYXHIP_ERR_INVALID_ARG, "bad batch->memory");
+    if (inten) {
+        if (s->grey_depth == 0) return fail(ctx, NYXHIP_ERR_INVALID_ARG, "grey_depth must be non-zero (histogram bin count)");
+        if ((uint32_t)abs(s->grey_depth) > kVolMaxHistBins)
+            return fail(ctx, NYXHIP_ERR_UNSUPPORTED, "volumes: the intensity histogram takes at most " + std::to_string(kVolMaxHistBins) + " bins");
+    }
+    if (glcm) {
+        if (s->glcm_offset < 1) return fail(ctx, NYXHIP_ERR_INVALID_ARG, "glcm_offset must be >= 1");
+        if (!s->ibsi && (uint32_t)abs(s->glcm_grey_depth) > kVolLevelCap)
+            return fail(ctx, NYXHIP_ERR_UNSUPPORTED, "volumes: the 3-D GLCM matrix lives in LDS up to " + std::to_string(kVolLevelCap) + " levels; |glcm_grey_depth| = " +
+                                                         std::to_string(abs(s->glcm_grey_depth)) + " exceeds that cap");
+    }
+    return vol_run(ctx, b, glcm, ncol, out, ld,
+                   [&](const nyxhip_batch3d& d, double* d_out, size_t d_ld, uint32_t max_px, uint32_t max_cells) { return vol_device(ctx, &d, vmask, s, d_out, d_ld, max_px, max_cells); },
+                   vol_check_status);
 }
 
 } // extern "C"

@@ -1,7 +1,8 @@
 """The `Feature3D` codes the volume entries serve (include/nyxhip.h, "volumes"): names, groups, expansion.
 
 The reference keeps its 3-D codes in an enum of their own (featureset.h:643-) with user-facing names that start with "3"
-(featureset.cpp:671-) and groups `*3D_...*` (:940-).  Two classes are served: the voxel-intensity class and the 3-D GLCM class.
+(featureset.cpp:671-) and groups `*3D_...*` (:940-).  Five classes are served: the voxel-intensity class and the 3-D GLCM class by the
+volume mask of nyxhip_featurize_volumes, the 3-D GLDM, NGLDM and NGTDM classes by the texture mask of nyxhip_featurize_volumes_tex.
 `featureset.expand`, its groups and the `Nyxus` class know nothing of them.
 """
 from __future__ import annotations
@@ -26,21 +27,29 @@ GLCM_3D_AVE = ["3GLCM_" + n + "_AVE" for n in (
     "ASM", "ACOR", "CLUPROM", "CLUSHADE", "CLUTEND", "CONTRAST", "CORRELATION", "DIFAVE", "DIFENTRO", "DIFVAR", "DIS", "ENERGY", "ENTROPY", "HOM1",
     "ID", "IDN", "IDM", "IDMN", "IV", "JAVE", "JE", "INFOMEAS1", "INFOMEAS2", "VARIANCE", "JMAX", "JVAR", "SUMAVERAGE", "SUMENTROPY", "SUMVARIANCE")]
 GLCM_3D = GLCM_3D_ANGLED + GLCM_3D_AVE
+# Feature3D order (featureset.cpp:827-840, :911-929, :931-935); the enum has the GLDM block before the NGLDM and NGTDM blocks
+GLDM_3D = ["3GLDM_" + n for n in ("SDE", "LDE", "GLN", "DN", "DNN", "GLV", "DV", "DE", "LGLE", "HGLE", "SDLGLE", "SDHGLE", "LDLGLE", "LDHGLE")]
+NGLDM_3D = ["3NGLDM_" + n for n in ("LDE", "HDE", "LGLCE", "HGLCE", "LDLGLE", "LDHGLE", "HDLGLE", "HDHGLE", "GLNU", "GLNUN", "DCNU", "DCNUN", "DCP", "GLM",
+                                    "GLV", "DCM", "DCV", "DCENT", "DCENE")]
+NGTDM_3D = ["3NGTDM_" + n for n in ("COARSENESS", "CONTRAST", "BUSYNESS", "COMPLEXITY", "STRENGTH")]
 
 # the reference's spelling (featureset.cpp:941, :944); group names match in any letter case, like the 2-D groups
-GROUPS_3D = {"*3D_ALL_INTENSITY*": INTENSITY_3D, "*3D_GLCM*": GLCM_3D}
-ORDER_3D = INTENSITY_3D + GLCM_3D
-VFAM_OF = {**{c: _abi.VFAM_INTENSITY for c in INTENSITY_3D}, **{c: _abi.VFAM_GLCM for c in GLCM_3D}}
+GROUPS_3D = {"*3D_ALL_INTENSITY*": INTENSITY_3D, "*3D_GLCM*": GLCM_3D, "*3D_GLDM*": GLDM_3D, "*3D_NGLDM*": NGLDM_3D, "*3D_NGTDM*": NGTDM_3D}
+ORDER_3D = INTENSITY_3D + GLCM_3D + GLDM_3D + NGLDM_3D + NGTDM_3D
+# a code belongs to one of the two mask spaces: the volume mask (VFAM_OF, 0 for a texture code) or the texture mask (VTEX_OF)
+VTEX_OF = {**{c: _abi.VTEX_GLDM for c in GLDM_3D}, **{c: _abi.VTEX_NGLDM for c in NGLDM_3D}, **{c: _abi.VTEX_NGTDM for c in NGTDM_3D}}
+VFAM_OF = {**{c: _abi.VFAM_INTENSITY for c in INTENSITY_3D}, **{c: _abi.VFAM_GLCM for c in GLCM_3D}, **{c: 0 for c in VTEX_OF}}
 
 
 def _refusal(names) -> str:
     return (f"feature(s) {names} are not served by the MI355X volume path. Served: the groups {sorted(GROUPS_3D)} and the individual codes of the "
-            f"two classes (3COV .. 3UNIFORMITY_PIU, 3GLCM_ACOR .. 3GLCM_SUMVARIANCE_AVE); *3D_ALL*, the 3-D shape class and the other 3-D "
-            "texture classes are not served")
+            f"five classes (3COV .. 3UNIFORMITY_PIU, 3GLCM_ACOR .. 3GLCM_SUMVARIANCE_AVE, 3GLDM_SDE .. 3GLDM_LDHGLE, 3NGLDM_LDE .. 3NGLDM_DCENE, "
+            "3NGTDM_COARSENESS .. 3NGTDM_STRENGTH); *3D_ALL*, the 3-D shape class and the 3-D GLRLM, GLSZM and GLDZM classes are not served")
 
 
 def expand3d(features: List[str]) -> Tuple[int, List[str]]:
-    """(volume mask, the requested codes in Feature3D order).  Raises ValueError for anything but the served groups and codes."""
+    """(volume mask, the requested codes in Feature3D order).  Raises ValueError for anything but the served groups and codes.  The
+    volume mask is 0 when only texture codes are asked for; their mask is tex_mask(codes)."""
     want, unknown = set(), []
     for f in features:
         if not isinstance(f, str):
@@ -61,6 +70,14 @@ def expand3d(features: List[str]) -> Tuple[int, List[str]]:
     for c in req:
         mask |= VFAM_OF[c]
     return mask, req
+
+
+def tex_mask(codes: List[str]) -> int:
+    """The texture mask (nyxhip_featurize_volumes_tex) that serves the GLDM / NGLDM / NGTDM codes among `codes`; 0: none."""
+    m = 0
+    for c in codes:
+        m |= VTEX_OF.get(c, 0)
+    return m
 
 
 def table_column(code: str) -> str:

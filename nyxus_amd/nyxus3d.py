@@ -1,8 +1,9 @@
 """`Nyxus3D` -- the reference's volumetric Python class (src/nyx/python/nyxus/nyxus.py:923 of the reference), served by
-nyxhip_featurize_volumes (include/nyxhip.h, "volumes").
+nyxhip_featurize_volumes and nyxhip_featurize_volumes_tex (include/nyxhip.h, "volumes").
 
-Two classes of the `Feature3D` enum are served: the voxel-intensity class (`*3D_ALL_INTENSITY*`, 36 codes) and the 3-D GLCM class
-(`*3D_GLCM*`, 30 angled codes and 29 `_AVE` codes).  The constructor takes the reference's keys and raises the reference's messages
+Five classes of the `Feature3D` enum are served: the voxel-intensity class (`*3D_ALL_INTENSITY*`, 36 codes), the 3-D GLCM class
+(`*3D_GLCM*`, 30 angled codes and 29 `_AVE` codes), and the 3-D GLDM, NGLDM and NGTDM classes (`*3D_GLDM*` 14, `*3D_NGLDM*` 19,
+`*3D_NGTDM*` 5 codes), whose grey depths and radius are metaparameters (`set_metaparam`) that start at 0 as in the reference.  The constructor takes the reference's keys and raises the reference's messages
 (nyxus.py:1014-1110).  `featurize` is the in-memory face: it mirrors `Nyxus.featurize` for volumes (the reference's class has none).
 The file workflows are not served: NIfTI / DICOM / z-stack ingest is outside this package.
 """
@@ -61,6 +62,8 @@ class Nyxus3D:
             raise ValueError("anisotropy is outside the MI355X hot path (SURVEY.md section 8)")
         self._features = list(features)
         self._mask, self._requested = featureset3d.expand3d(self._features)
+        self._tex_mask = featureset3d.tex_mask(self._requested)
+        self._tex_settings = _abi.VolTexSettings(0, 0, 0)   # compile_feature_settings zeroes the slots (env_features.cpp:712-736)
         # glcm_offset stays 1 and glcm_symmetric 0: the statics of the reference's 3-D GLCM class, which nothing in its Python face sets
         self._settings = _abi.default_settings(int(coarse_gray_depth), bool(kwargs.get("ibsi", False)))
         self._env = {"ram_limit": kwargs.get("ram_limit", -1)}
@@ -74,9 +77,60 @@ class Nyxus3D:
         return self._ctx
 
     def _columns(self):
-        names = _lib.vol_column_names(self._mask, self._settings)
+        names = (_lib.vol_column_names(self._mask, self._settings) if self._mask else []) + (_lib.voltex_column_names(self._tex_mask) if self._tex_mask else [])
         sel = [names.index(featureset3d.table_column(c)) for c in self._requested]
         return list(self._requested), sel
+
+    # env_metaparams.cpp:157-203 (set), :313-347 (get): the keys of the served classes
+    _METAPARAMS = {"3gldm/greydepth": "gldm_grey_depth", "3ngtdm/greydepth": "ngtdm_grey_depth", "3ngtdm/radius": "ngtdm_radius"}
+
+    def _metaparam_field(self, name: str) -> str:
+        if name not in self._METAPARAMS:
+            raise ValueError(f"Invalid metaparameter name {name}: the MI355X volume path serves {sorted(self._METAPARAMS)}")
+        return self._METAPARAMS[name]
+
+    def set_metaparam(self, paramval: str):
+        """Sets a feature-specific parameter, for example ``set_metaparam("3gldm/greydepth=-20")`` (nyxus.py:1111-1128)."""
+        sides = str(paramval).split("=")
+        if len(sides) != 2:
+            raise ValueError(f"Invalid metaparameter value {paramval}: error: expecting <feature>/<parameter>=<value>")
+        name, raw = sides[0].strip(), sides[1].strip()
+        field = self._metaparam_field(name)
+        try:
+            val = int(raw)
+        except ValueError:
+            val = None
+        if name == "3ngtdm/radius":
+            if val is None or val <= 0:
+                raise ValueError(f'Invalid metaparameter value {paramval}: error: cannot parse value "{raw}" of 3ngtdm/radius: expecting a positive integer')
+        elif val is None:
+            raise ValueError(f'Invalid metaparameter value {paramval}: error: cannot parse value "{raw}" of {name}: expecting an integer')
+        if not -2**31 <= val < 2**31:
+            raise ValueError(f'Invalid metaparameter value {paramval}: error: cannot parse value "{raw}" of {name}: expecting an integer')
+        setattr(self._tex_settings, field, val)
+
+    def get_metaparam(self, paramname: str) -> float:
+        """The value of a feature-specific parameter, as a float like the reference's (nyxus.py:1130-1147)."""
+        return float(getattr(self._tex_settings, self._metaparam_field(str(paramname).strip())))
+
+    def _tables(self, b: _abi.HostBatch3D, max_device_bytes: int) -> np.ndarray:
+        """The volume table and the texture table of a batch side by side, whichever the request needs (Feature3D order)."""
+        ctx, parts = self._context(), []
+        if self._mask:
+            parts.append(ctx.volumes_host(b, self._mask, self._settings, max_device_bytes=max_device_bytes))
+        if self._tex_mask:
+            try:
+                parts.append(ctx.volumes_tex_host(b, self._tex_mask, self._settings, self._tex_settings, max_device_bytes=max_device_bytes))
+            except _lib.NyxHipError as e:
+                t = self._tex_settings
+                zero = [k for k, f, bit in (("3gldm/greydepth", t.gldm_grey_depth, _abi.VTEX_GLDM), ("3ngtdm/greydepth", t.ngtdm_grey_depth, _abi.VTEX_NGTDM))
+                        if f == 0 and self._tex_mask & bit and not (bit == _abi.VTEX_NGTDM and t.ngtdm_radius == 0)]
+                if e.code == _abi.ERR_UNSUPPORTED and zero and not self._settings.ibsi:
+                    raise _lib.NyxHipError(e.code, f"{e.args[0]} -- a grey depth of 0 leaves the intensities unbinned: set " +
+                                           " and ".join(f'set_metaparam("{k}=<levels>")' for k in zero) +
+                                           f" with at most {_abi.VOLTEX_MAX_LEVELS} levels (negative: radiomics binning)") from e
+                raise
+        return parts[0] if len(parts) == 1 else np.hstack(parts)
 
     def featurize(self, intensity_volumes: np.ndarray, label_volumes: np.ndarray, intensity_names: Optional[list] = None,
                   label_names: Optional[list] = None):
@@ -129,7 +183,7 @@ class Nyxus3D:
         if rois:
             b = _abi.batch3d_from_rois(rois)
             rl = self._env.get("ram_limit", -1)
-            table = self._context().volumes_host(b, self._mask, self._settings, max_device_bytes=int(rl) << 20 if rl and rl > 0 else 0)
+            table = np.ascontiguousarray(self._tables(b, int(rl) << 20 if rl and rl > 0 else 0))
             _lib.load().nyxhip_finalize_table(table.ctypes.data, table.shape[0], table.shape[1], table.shape[1], C.c_double(self._settings.soft_nan))
             labels = b.roi_label
         else:
