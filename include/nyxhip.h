@@ -39,7 +39,8 @@ enum {
     NYXHIP_ERR_NO_DEVICE = 2,     /* HIP runtime / GPU not available           */
     NYXHIP_ERR_HIP = 3,           /* a HIP call failed (message has detail)    */
     NYXHIP_ERR_UNSUPPORTED = 4,   /* setting outside what the kernels cover    */
-    NYXHIP_ERR_ROI_TOO_LARGE = 5  /* ROI exceeds the LDS-resident capacity     */
+    NYXHIP_ERR_ROI_TOO_LARGE = 5, /* ROI exceeds the LDS-resident capacity     */
+    NYXHIP_ERR_INTERNAL = 6       /* a device loop reached its bound (a defect) */
 };
 
 /* ---- feature families (bitmask) -----------------------------------------
@@ -580,6 +581,52 @@ int nyxhip_voltex_column_name(uint32_t tex_mask, int col, char* buf, size_t buf_
 /* One row of nyxhip_voltex_n_columns(tex_mask) values per ROI.  Host batch: host table.  Device batch: device table.  Synchronous. */
 int nyxhip_featurize_volumes_tex(nyxhip_ctx* ctx, const nyxhip_batch3d* batch, uint32_t tex_mask, const nyxhip_settings* s,
                                  const nyxhip_voltex_settings* t, double* out_table, size_t out_ld);
+
+/* ---- volumes (3-D): GLRLM and GLSZM -------------------------------------------
+ * Two more classes of the reference's Feature3D enum on the batch type of the volume entries, behind entries and a mask space of their
+ * own (the volume mask and the texture mask keep their bits):
+ *   NYXHIP_VZONE_GLRLM   D3_GLRLM_feature (features/3d_glrlm.cpp): 16 angled codes 3GLRLM_SRE .. 3GLRLM_LRHGLE, 13 columns <name>_<k> each,
+ *                        k the index into shifts13[] (3d_glrlm.cpp:17-32, fields dz, dy, dx: direction 0 is (1, 1, 1), 4 is +z, 10 is +y,
+ *                        12 is +x), then the 16 codes 3GLRLM_SRE_AVE .. 3GLRLM_LRHGLE_AVE: calc_ave over the 13 values, soft_nan values
+ *                        included.  224 columns.  A run is a maximal line of cells of one non-zero level along the direction; under
+ *                        matlab binning the background of the box has level 1 and forms runs.
+ *   NYXHIP_VZONE_GLSZM   D3_GLSZM_feature (features/3d_glszm.cpp): 16 codes 3GLSZM_SAE .. 3GLSZM_LAHGLE.  A zone is a 26-connected component
+ *                        of cells of one level; cells of the background level (1 under matlab binning, else 0) form none.
+ * The GLRLM block of a row stands first.  SETTINGS READ.  nyxhip_settings: ibsi, soft_nan.  nyxhip_volzone_settings: the two slots below;
+ * a class bins with greyInfo = ibsi ? 0 : <class>_grey_depth (> 0 matlab levels, < 0 radiomics bins, 0 none).  The reference starts both
+ * at 0.  soft_nan is written in every column of a flat ROI (min_inten == max_inten: both classes answer before they bin; an _AVE column is
+ * then the average of thirteen soft_nan), of an ROI without voxels, and in the GLSZM block of an ROI without a zone.  An empty run matrix
+ * gives 0 in every GLRLM column.  Other NaN / inf stay (nyxhip_finalize_table).
+ * LIMITS.  Those of the volume entries (side, NYXHIP_VOL_MAX_CELLS, stated extrema, max_device_bytes, voxels outside their box), and:
+ * more than NYXHIP_VOLZONE_MAX_LEVELS levels is NYXHIP_ERR_UNSUPPORTED, never a wrong row -- |glrlm_grey_depth| and |glszm_grey_depth|
+ * are checked on the host, the largest intensity of an ROI (IBSI mode, or a grey depth of 0) on the device.  The workspace holds, per ROI
+ * of a chunk, 8 bytes per cell of the largest box for the GLSZM labels and, for GLRLM, a table of levels x run lengths per direction
+ * sized by the largest box sides of the batch (read from the boxes: a device batch costs one device->host copy of them).
+ * WHERE THE REFERENCE IS UNDEFINED.  Its formulas square a run length or a zone size j as `int`: double(j * j) overflows above 46340
+ * cells (3GLRLM_SRE, _LRE, _SRHGLE, _LRLGLE; 3GLSZM_SAE, _LAE: 3d_glszm.cpp:685, :709), and inten * inten * j * j of 3GLRLM_SRLGLE and
+ * _LRHGLE is a 32-bit unsigned product that wraps once level x j reaches 2^16.  A box of 36 x 36 x 37 cells already holds a zone above
+ * 46340 cells, so real volumes meet this.  This library computes double(j) * double(j), which is exact, everywhere.
+ * Every sum that more than one thread adds to is an integer and the list of large zones is sorted before it is read: a row has the same
+ * bits whatever shares its call, chunk, memory kind or batch order.  No kernel waits for another workgroup; every device loop has a
+ * bound derived from the box, and one that reaches it makes the call return NYXHIP_ERR_INTERNAL. */
+enum {
+    NYXHIP_VZONE_GLRLM = 1u << 0,
+    NYXHIP_VZONE_GLSZM = 1u << 1,
+    NYXHIP_VZONE_ALL = 0x3
+};
+#define NYXHIP_VOLZONE_MAX_LEVELS 128
+typedef struct nyxhip_volzone_settings {
+    int32_t glrlm_grey_depth;    /* NyxSetting::GLRLM_GREYDEPTH of fsett_D3_GLRLM */
+    int32_t glszm_grey_depth;    /* NyxSetting::GLSZM_GREYDEPTH of fsett_D3_GLSZM */
+} nyxhip_volzone_settings;
+
+/* Column catalogue of a zone mask: the count (< 0: invalid mask, 0 or any foreign bit) and the name of column `col`. */
+int nyxhip_volzone_n_columns(uint32_t zone_mask);
+int nyxhip_volzone_column_name(uint32_t zone_mask, int col, char* buf, size_t buf_len);
+
+/* One row of nyxhip_volzone_n_columns(zone_mask) values per ROI.  Host batch: host table.  Device batch: device table.  Synchronous. */
+int nyxhip_featurize_volumes_zones(nyxhip_ctx* ctx, const nyxhip_batch3d* batch, uint32_t zone_mask, const nyxhip_settings* s,
+                                   const nyxhip_volzone_settings* t, double* out_table, size_t out_ld);
 
 /* ---- measurement hooks -------------------------------------------------------
  * Average device time (ms) per featurize call since the last nyxhip_timing_reset(),

@@ -15,7 +15,7 @@ import numpy as np
 
 NYXHIP_OK = 0
 ERR_UNSUPPORTED = 4
-ERR_NAMES = {0: "OK", 1: "INVALID_ARG", 2: "NO_DEVICE", 3: "HIP", 4: "UNSUPPORTED", 5: "ROI_TOO_LARGE"}
+ERR_NAMES = {0: "OK", 1: "INVALID_ARG", 2: "NO_DEVICE", 3: "HIP", 4: "UNSUPPORTED", 5: "ROI_TOO_LARGE", 6: "INTERNAL"}
 
 FAM_INTENSITY = 1 << 0
 FAM_GLCM = 1 << 1
@@ -298,6 +298,19 @@ VOLTEX_MAX_RADIUS = 3        # NYXHIP_VOLTEX_MAX_RADIUS
 class VolTexSettings(C.Structure):
     """``nyxhip_voltex_settings`` (include/nyxhip.h); all three start at 0, as in the reference (env_features.cpp:712-736)."""
     _fields_ = [("gldm_grey_depth", C.c_int32), ("ngtdm_grey_depth", C.c_int32), ("ngtdm_radius", C.c_int32)]
+
+
+# the zone mask of nyxhip_featurize_volumes_zones (a mask space of its own)
+VZONE_GLRLM = 1 << 0         # D3_GLRLM_feature: 16 angled codes x 13 directions, 16 _AVE codes
+VZONE_GLSZM = 1 << 1         # D3_GLSZM_feature: 3GLSZM_SAE .. 3GLSZM_LAHGLE
+VZONE_ALL = 0x3
+VOLZONE_MAX_LEVELS = 128     # NYXHIP_VOLZONE_MAX_LEVELS
+VOLZONE_DIRECTIONS = 13
+
+
+class VolZoneSettings(C.Structure):
+    """``nyxhip_volzone_settings`` (include/nyxhip.h); both start at 0, as in the reference."""
+    _fields_ = [("glrlm_grey_depth", C.c_int32), ("glszm_grey_depth", C.c_int32)]
 
 
 class Batch3D(C.Structure):

@@ -34,6 +34,7 @@ ABI_SYMBOLS = [
     "nyxhip_imq_column_name", "nyxhip_imq_batch", "nyxhip_imq_tiles", "nyxhip_imq_slides",
     "nyxhip_vol_n_columns", "nyxhip_vol_column_name", "nyxhip_featurize_volumes",
     "nyxhip_voltex_n_columns", "nyxhip_voltex_column_name", "nyxhip_featurize_volumes_tex",
+    "nyxhip_volzone_n_columns", "nyxhip_volzone_column_name", "nyxhip_featurize_volumes_zones",
 ]
 
 
@@ -156,6 +157,11 @@ def load() -> C.CDLL:
         lib.nyxhip_voltex_column_name.argtypes = [C.c_uint32, C.c_int, C.c_char_p, C.c_size_t]
         lib.nyxhip_voltex_column_name.restype = C.c_int
         lib.nyxhip_featurize_volumes_tex.argtypes = [C.c_void_p, P(_abi.Batch3D), C.c_uint32, P(_abi.Settings), P(_abi.VolTexSettings), C.c_void_p, C.c_size_t]
+        lib.nyxhip_volzone_n_columns.argtypes = [C.c_uint32]
+        lib.nyxhip_volzone_n_columns.restype = C.c_int
+        lib.nyxhip_volzone_column_name.argtypes = [C.c_uint32, C.c_int, C.c_char_p, C.c_size_t]
+        lib.nyxhip_volzone_column_name.restype = C.c_int
+        lib.nyxhip_featurize_volumes_zones.argtypes = [C.c_void_p, P(_abi.Batch3D), C.c_uint32, P(_abi.Settings), P(_abi.VolZoneSettings), C.c_void_p, C.c_size_t]
         lib.nyxhip_featurize_volumes_tex.restype = C.c_int
     if hasattr(lib, "nyxhip_featurize_slides"):  # (absent from older builds of the ABI selected through NYXHIP_LIB for A/B runs)
         lib.nyxhip_featurize_slides.argtypes = [C.c_void_p, P(_abi.Tiles), C.c_uint32, P(_abi.Settings), C.c_void_p, C.c_size_t]
@@ -247,6 +253,22 @@ def voltex_column_names(tmask: int) -> List[str]:
         rc = lib.nyxhip_voltex_column_name(tmask, i, buf, 128)
         if rc != 0:
             raise NyxHipError(rc, f"volume texture column {i}")
+        out.append(buf.value.decode())
+    return out
+
+
+def volzone_column_names(zmask: int) -> List[str]:
+    """The columns of nyxhip_featurize_volumes_zones for a zone mask (_abi.VZONE_*)."""
+    lib = load()
+    n = lib.nyxhip_volzone_n_columns(zmask)
+    if n < 0:
+        raise NyxHipError(1, f"bad volume zone mask {zmask:#x}")
+    buf = C.create_string_buffer(128)
+    out = []
+    for i in range(n):
+        rc = lib.nyxhip_volzone_column_name(zmask, i, buf, 128)
+        if rc != 0:
+            raise NyxHipError(rc, f"volume zone column {i}")
         out.append(buf.value.decode())
     return out
 
@@ -419,6 +441,21 @@ class Context:
     def volumes_tex_device(self, cb: _abi.Batch3D, tmask: int, s: _abi.Settings, t: _abi.VolTexSettings, out_ptr: int, ld: int):
         """Device pointers in ``cb`` and a device table; synchronous (nyxhip_featurize_volumes_tex)."""
         self._check(self._lib.nyxhip_featurize_volumes_tex(self._h, C.byref(cb), tmask, C.byref(s), C.byref(t), C.c_void_p(out_ptr), ld))
+
+    def volumes_zones_host(self, batch: _abi.HostBatch3D, zmask: int, s: _abi.Settings, t: _abi.VolZoneSettings, stated: bool = False,
+                           max_device_bytes: int = 0) -> np.ndarray:
+        """The zone table [n_roi x nyxhip_volzone_n_columns] of a host batch (nyxhip_featurize_volumes_zones); NaN / inf are left in place."""
+        ncol = self._lib.nyxhip_volzone_n_columns(zmask)
+        if ncol < 0:
+            raise NyxHipError(1, f"bad volume zone mask {zmask:#x}")
+        out = np.empty((batch.n_roi, ncol), np.float64)
+        cb = batch.c_struct(stated=stated, max_device_bytes=max_device_bytes)
+        self._check(self._lib.nyxhip_featurize_volumes_zones(self._h, C.byref(cb), zmask, C.byref(s), C.byref(t), out.ctypes.data, ncol))
+        return out
+
+    def volumes_zones_device(self, cb: _abi.Batch3D, zmask: int, s: _abi.Settings, t: _abi.VolZoneSettings, out_ptr: int, ld: int):
+        """Device pointers in ``cb`` and a device table; synchronous (nyxhip_featurize_volumes_zones)."""
+        self._check(self._lib.nyxhip_featurize_volumes_zones(self._h, C.byref(cb), zmask, C.byref(s), C.byref(t), C.c_void_p(out_ptr), ld))
 
     def imq_host(self, batch: _abi.HostBatch, s: _abi.Settings) -> np.ndarray:
         """The image-quality columns [n_roi x 4] of a host batch (nyxhip_imq_batch); NaN / inf are left in place."""

@@ -3,7 +3,8 @@
 The reference keeps its 3-D codes in an enum of their own (featureset.h:643-) with user-facing names that start with "3"
 (featureset.cpp:671-) and groups `*3D_...*` (:940-).  Five classes are served: the voxel-intensity class and the 3-D GLCM class by the
 volume mask of nyxhip_featurize_volumes, the 3-D GLDM, NGLDM and NGTDM classes by the texture mask of nyxhip_featurize_volumes_tex.
-`featureset.expand`, its groups and the `Nyxus` class know nothing of them.
+`featureset.expand`, its groups and the `Nyxus` class know nothing of them.  Two more classes, the 3-D GLRLM and GLSZM, are served by the
+zone mask of nyxhip_featurize_volumes_zones through `expand3d_zones` and `Nyxus3DZones`; `expand3d` and `Nyxus3D` refuse them.
 """
 from __future__ import annotations
 
@@ -33,18 +34,31 @@ NGLDM_3D = ["3NGLDM_" + n for n in ("LDE", "HDE", "LGLCE", "HGLCE", "LDLGLE", "L
                                     "GLV", "DCM", "DCV", "DCENT", "DCENE")]
 NGTDM_3D = ["3NGTDM_" + n for n in ("COARSENESS", "CONTRAST", "BUSYNESS", "COMPLEXITY", "STRENGTH")]
 
+# Feature3D order (featureset.h:863-914, names featureset.cpp:861-909): in the enum the GLSZM block and then the GLRLM block (angled codes,
+# then the _AVE codes) stand behind the NGTDM block.  Served by Nyxus3DZones / expand3d_zones only (the zone mask of
+# nyxhip_featurize_volumes_zones); expand3d refuses them.
+GLSZM_3D = ["3GLSZM_" + n for n in ("SAE", "LAE", "GLN", "GLNN", "SZN", "SZNN", "ZP", "GLV", "ZV", "ZE", "LGLZE", "HGLZE", "SALGLE", "SAHGLE", "LALGLE", "LAHGLE")]
+GLRLM_3D_ANGLED = ["3GLRLM_" + n for n in ("SRE", "LRE", "GLN", "GLNN", "RLN", "RLNN", "RP", "GLV", "RV", "RE", "LGLRE", "HGLRE", "SRLGLE", "SRHGLE", "LRLGLE",
+                                           "LRHGLE")]
+GLRLM_3D_AVE = [c + "_AVE" for c in GLRLM_3D_ANGLED]
+GLRLM_3D = GLRLM_3D_ANGLED + GLRLM_3D_AVE
+
 # the reference's spelling (featureset.cpp:941, :944); group names match in any letter case, like the 2-D groups
 GROUPS_3D = {"*3D_ALL_INTENSITY*": INTENSITY_3D, "*3D_GLCM*": GLCM_3D, "*3D_GLDM*": GLDM_3D, "*3D_NGLDM*": NGLDM_3D, "*3D_NGTDM*": NGTDM_3D}
 ORDER_3D = INTENSITY_3D + GLCM_3D + GLDM_3D + NGLDM_3D + NGTDM_3D
 # a code belongs to one of the two mask spaces: the volume mask (VFAM_OF, 0 for a texture code) or the texture mask (VTEX_OF)
 VTEX_OF = {**{c: _abi.VTEX_GLDM for c in GLDM_3D}, **{c: _abi.VTEX_NGLDM for c in NGLDM_3D}, **{c: _abi.VTEX_NGTDM for c in NGTDM_3D}}
+GROUPS_3D_ZONES = {"*3D_GLRLM*": GLRLM_3D, "*3D_GLSZM*": GLSZM_3D}
+ORDER_3D_ZONES = ORDER_3D + GLSZM_3D + GLRLM_3D
+VZONE_OF = {**{c: _abi.VZONE_GLRLM for c in GLRLM_3D}, **{c: _abi.VZONE_GLSZM for c in GLSZM_3D}}
 VFAM_OF = {**{c: _abi.VFAM_INTENSITY for c in INTENSITY_3D}, **{c: _abi.VFAM_GLCM for c in GLCM_3D}, **{c: 0 for c in VTEX_OF}}
 
 
 def _refusal(names) -> str:
     return (f"feature(s) {names} are not served by the MI355X volume path. Served: the groups {sorted(GROUPS_3D)} and the individual codes of the "
             f"five classes (3COV .. 3UNIFORMITY_PIU, 3GLCM_ACOR .. 3GLCM_SUMVARIANCE_AVE, 3GLDM_SDE .. 3GLDM_LDHGLE, 3NGLDM_LDE .. 3NGLDM_DCENE, "
-            "3NGTDM_COARSENESS .. 3NGTDM_STRENGTH); *3D_ALL*, the 3-D shape class and the 3-D GLRLM, GLSZM and GLDZM classes are not served")
+            "3NGTDM_COARSENESS .. 3NGTDM_STRENGTH); *3D_ALL*, the 3-D shape class and the 3-D GLRLM, GLSZM and GLDZM classes are not served. "
+            "The 3-D GLRLM and GLSZM classes are served by Nyxus3DZones (featureset3d.expand3d_zones)")
 
 
 def expand3d(features: List[str]) -> Tuple[int, List[str]]:
@@ -72,6 +86,31 @@ def expand3d(features: List[str]) -> Tuple[int, List[str]]:
     return mask, req
 
 
+def expand3d_zones(features: List[str]) -> Tuple[int, List[str]]:
+    """expand3d with the groups *3D_GLRLM*, *3D_GLSZM* and their codes served too: (volume mask, the requested codes in Feature3D
+    order).  The texture mask is tex_mask(codes), the zone mask zone_mask(codes)."""
+    rest, zones = [], set()
+    for f in features:
+        u = f.strip().upper() if isinstance(f, str) else None
+        if u in GROUPS_3D_ZONES:
+            zones.update(GROUPS_3D_ZONES[u])
+        elif u in VZONE_OF:
+            zones.add(u)
+        else:
+            rest.append(f)
+    mask, req = expand3d(rest) if rest or not zones else (0, [])
+    want = set(req) | zones
+    return mask, [c for c in ORDER_3D_ZONES if c in want]
+
+
+def zone_mask(codes: List[str]) -> int:
+    """The zone mask (nyxhip_featurize_volumes_zones) that serves the GLRLM / GLSZM codes among `codes`; 0: none."""
+    m = 0
+    for c in codes:
+        m |= VZONE_OF.get(c, 0)
+    return m
+
+
 def tex_mask(codes: List[str]) -> int:
     """The texture mask (nyxhip_featurize_volumes_tex) that serves the GLDM / NGLDM / NGTDM codes among `codes`; 0: none."""
     m = 0
@@ -83,5 +122,5 @@ def tex_mask(codes: List[str]) -> int:
 def table_column(code: str) -> str:
     """The column of the C table that a DataFrame column shows.  The reference's buffer writer gives a Feature3D code exactly one value,
     fvals[code][0] (output_2_buffer.cpp:576-577; its GLCM expansion tests the 2-D class's codes only): an angled 3GLCM_* code is the
-    value of direction shifts[0] = (1, 1, 1)."""
-    return code + "_0" if code in GLCM_3D_ANGLED else code
+    value of direction shifts[0] = (1, 1, 1), and so is an angled 3GLRLM_* code (shifts13[0])."""
+    return code + "_0" if code in GLCM_3D_ANGLED or code in GLRLM_3D_ANGLED else code

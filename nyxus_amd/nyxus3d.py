@@ -6,6 +6,8 @@ Five classes of the `Feature3D` enum are served: the voxel-intensity class (`*3D
 `*3D_NGTDM*` 5 codes), whose grey depths and radius are metaparameters (`set_metaparam`) that start at 0 as in the reference.  The constructor takes the reference's keys and raises the reference's messages
 (nyxus.py:1014-1110).  `featurize` is the in-memory face: it mirrors `Nyxus.featurize` for volumes (the reference's class has none).
 The file workflows are not served: NIfTI / DICOM / z-stack ingest is outside this package.
+
+`Nyxus3DZones` (below) is `Nyxus3D` with the 3-D GLRLM and GLSZM classes served too (nyxhip_featurize_volumes_zones).
 """
 from __future__ import annotations
 
@@ -204,3 +206,82 @@ class Nyxus3D:
     def featurize_files(self, *args, **kwargs):
         raise NotImplementedError("Nyxus3D.featurize_files: NIfTI / DICOM / z-stack ingest is not served (the TIFF reader of this package "
                                   "decodes first pages only); assemble the volumes and call featurize()")
+
+
+class Nyxus3DZones(Nyxus3D):
+    """`Nyxus3D` with the 3-D GLRLM and GLSZM classes served too (nyxhip_featurize_volumes_zones): the groups `*3D_GLRLM*` (16 angled
+    codes, 16 `_AVE` codes) and `*3D_GLSZM*` (16 codes) and their codes, beside everything `Nyxus3D` takes.  Same constructor, same
+    `featurize`; the DataFrame columns stand in Feature3D order (featureset.h: the GLSZM block, then the GLRLM block, behind the NGTDM
+    block), and the column of an angled `3GLRLM_*` code is direction shifts13[0] = (1, 1, 1), as the reference's table writer gives a 3-D
+    code one value.  The grey depths of the two classes are the metaparameters `3glrlm/greydepth` and `3glszm/greydepth`; both start at 0
+    (no binning) as in the reference, where real intensities exceed the level cap: the error names the metaparameter to set.
+    `Nyxus3D` itself keeps refusing these classes."""
+
+    def __init__(self, features: List[str], **kwargs):
+        plain, _ = featureset3d.expand3d_zones(list(features))         # raises the refusal of expand3d for anything else
+        del plain
+        zone_only = [f for f in features if isinstance(f, str) and (f.strip().upper() in featureset3d.GROUPS_3D_ZONES or f.strip().upper() in featureset3d.VZONE_OF)]
+        rest = [f for f in features if f not in zone_only]
+        super().__init__(rest if rest else ["3MEAN"], **kwargs)        # (the checks of the keyword arguments; the request is set below)
+        self._features = list(features)
+        self._mask, self._requested = featureset3d.expand3d_zones(self._features)
+        self._tex_mask = featureset3d.tex_mask(self._requested)
+        self._zone_mask = featureset3d.zone_mask(self._requested)
+        self._zone_settings = _abi.VolZoneSettings(0, 0)
+
+    def _columns(self):
+        names = ((_lib.vol_column_names(self._mask, self._settings) if self._mask else []) +
+                 (_lib.voltex_column_names(self._tex_mask) if self._tex_mask else []) +
+                 (_lib.volzone_column_names(self._zone_mask) if self._zone_mask else []))
+        sel = [names.index(featureset3d.table_column(c)) for c in self._requested]
+        return list(self._requested), sel
+
+    # env_metaparams.cpp:204-239 (set), :348-375 (get: the reference spells the GLSZM key "3glsz" there)
+    _ZONE_METAPARAMS = {"3glrlm/greydepth": "glrlm_grey_depth", "3glszm/greydepth": "glszm_grey_depth"}
+    _ZONE_GET_ONLY = {"3glsz/greydepth": "glszm_grey_depth"}
+
+    def _served(self):
+        return sorted({**self._METAPARAMS, **self._ZONE_METAPARAMS})
+
+    def set_metaparam(self, paramval: str):
+        """`Nyxus3D.set_metaparam` and the keys ``3glrlm/greydepth`` and ``3glszm/greydepth`` (any integer; negative: radiomics bins)."""
+        sides = str(paramval).split("=")
+        name = sides[0].strip()
+        if len(sides) != 2 or name in self._METAPARAMS:
+            return super().set_metaparam(paramval)
+        if name not in self._ZONE_METAPARAMS:
+            raise ValueError(f"Invalid metaparameter name {name}: the MI355X volume path serves {self._served()}")
+        raw = sides[1].strip()
+        try:
+            val = int(raw)
+        except ValueError:
+            val = None
+        if val is None or not -2**31 <= val < 2**31:
+            raise ValueError(f'Invalid metaparameter value {paramval}: error: cannot parse value "{raw}" of {name}: expecting an integer')
+        setattr(self._zone_settings, self._ZONE_METAPARAMS[name], val)
+
+    def get_metaparam(self, paramname: str) -> float:
+        name = str(paramname).strip()
+        field = self._ZONE_METAPARAMS.get(name) or self._ZONE_GET_ONLY.get(name)
+        if field:
+            return float(getattr(self._zone_settings, field))
+        if name not in self._METAPARAMS:
+            raise ValueError(f"Invalid metaparameter name {name}: the MI355X volume path serves {self._served() + sorted(self._ZONE_GET_ONLY)}")
+        return super().get_metaparam(name)
+
+    def _tables(self, b: _abi.HostBatch3D, max_device_bytes: int) -> np.ndarray:
+        """The volume table, the texture table and the zone table of a batch side by side, whichever the request needs."""
+        parts = [super()._tables(b, max_device_bytes)] if (self._mask or self._tex_mask) else []
+        if self._zone_mask:
+            try:
+                parts.append(self._context().volumes_zones_host(b, self._zone_mask, self._settings, self._zone_settings, max_device_bytes=max_device_bytes))
+            except _lib.NyxHipError as e:
+                z = self._zone_settings
+                zero = [k for k, f, bit in (("3glrlm/greydepth", z.glrlm_grey_depth, _abi.VZONE_GLRLM), ("3glszm/greydepth", z.glszm_grey_depth, _abi.VZONE_GLSZM))
+                        if f == 0 and self._zone_mask & bit]
+                if e.code == _abi.ERR_UNSUPPORTED and zero and not self._settings.ibsi:
+                    raise _lib.NyxHipError(e.code, f"{e.args[0]} -- a grey depth of 0 leaves the intensities unbinned: set " +
+                                           " and ".join(f'set_metaparam("{k}=<levels>")' for k in zero) +
+                                           f" with at most {_abi.VOLZONE_MAX_LEVELS} levels (negative: radiomics binning)") from e
+                raise
+        return parts[0] if len(parts) == 1 else np.hstack(parts)
