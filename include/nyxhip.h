@@ -628,6 +628,47 @@ int nyxhip_volzone_column_name(uint32_t zone_mask, int col, char* buf, size_t bu
 int nyxhip_featurize_volumes_zones(nyxhip_ctx* ctx, const nyxhip_batch3d* batch, uint32_t zone_mask, const nyxhip_settings* s,
                                    const nyxhip_volzone_settings* t, double* out_table, size_t out_ld);
 
+/* ---- volumes (3-D): GLDZM ----------------------------------------------------
+ * The last texture class of the reference's Feature3D enum, behind an entry and a mask space of its own (the volume, texture and zone
+ * masks keep their bits):
+ *   NYXHIP_VDZ_GLDZM   D3_GLDZM_feature (features/3d_gldzm.cpp): 18 codes 3GLDZM_SDE .. 3GLDZM_ZDE in save_value order (GLE is computed
+ *                      and not saved).
+ * THE RULING.  Semantics are those of the text of 3d_gldzm.cpp, quirks included, with one exception: a cell of level 0 is treated in
+ * every binning mode as the reference treats it in IBSI mode -- it forms no zone and it is always a border.  Every sum of the
+ * reference's calc_features skips level 0 already and a level-0 zone adds only empty columns, so the value equals the reference's
+ * wherever the reference is defined; it is not defined under radiomics binning (grey_depth < 0) for a box that holds a level-0 cell (a
+ * cell outside the cloud, or a voxel of intensity 0): there it writes outside its matrix and its distances depend on traversal order.
+ *   binning    greyInfo = ibsi ? 0 : grey_depth of nyxhip_settings (the class has no grey depth of its own): > 0 matlab levels -- the
+ *              background of the box is then level 1, forms zones and merges with level-1 voxels, and only the box faces are borders;
+ *              < 0 radiomics bins; 0 none.
+ *   zones      6-connected components of equal level (E, S, W, N, +z, -z): diagonal contact does not join.
+ *   distance   of a cell: in its own z-plane, along +-x and +-y, the distance to the nearest cell that is level 0 or lies on the box face
+ *              (a cell on that face: 0), plus 1, the minimum of the four.  A face cell has 1, a cell beside a level-0 cell 2, and so has
+ *              a cell at x == 1.  The metric of a zone is the minimum over its cells; the matrix is [level][metric - 1].
+ *   ZP         Ns / voxels of the cloud; background zones under matlab binning count in Ns.  ZDE uses log2(p / Ns + 2.2e-16).
+ * SETTINGS READ.  nyxhip_settings: ibsi, grey_depth, soft_nan.  soft_nan is written in all 18 columns of a flat ROI (min_inten ==
+ * max_inten, before any binning) and of an ROI without voxels.  Other NaN / inf stay (nyxhip_finalize_table).
+ * LIMITS.  Those of the volume entries (side, NYXHIP_VOL_MAX_CELLS, stated extrema, max_device_bytes, voxels outside their box), and:
+ * more than NYXHIP_VOLDZONE_MAX_LEVELS levels is NYXHIP_ERR_UNSUPPORTED, never a wrong row -- |grey_depth| is checked on the host, the
+ * largest intensity of an ROI (IBSI mode, or a grey depth of 0) on the device.  The workspace holds, per ROI of a chunk, 11 bytes per
+ * cell of the largest box (level, 16-bit distance, label, zone minimum) and a table of levels x (min(w, h) / 2 + 2) sized by the
+ * largest boxes of the batch (read from the boxes: a device batch costs one device->host copy of them).
+ * Every sum that more than one thread adds to is an integer: a row has the same bits whatever shares its call, chunk, memory kind or
+ * batch order.  No kernel waits for another workgroup; every device loop has a bound derived from the box, and one that reaches it
+ * makes the call return NYXHIP_ERR_INTERNAL. */
+enum {
+    NYXHIP_VDZ_GLDZM = 1u << 0
+};
+#define NYXHIP_VOLDZONE_MAX_LEVELS 128
+
+/* Column catalogue of a distance-zone mask: the count (< 0: invalid mask, 0 or any foreign bit) and the name of column `col`. */
+int nyxhip_voldzone_n_columns(uint32_t dzone_mask);
+int nyxhip_voldzone_column_name(uint32_t dzone_mask, int col, char* buf, size_t buf_len);
+
+/* One row of 18 values per ROI.  Host batch: host table.  Device batch: device table.  Synchronous. */
+int nyxhip_featurize_volumes_dzones(nyxhip_ctx* ctx, const nyxhip_batch3d* batch, uint32_t dzone_mask, const nyxhip_settings* s,
+                                    double* out_table, size_t out_ld);
+
 /* ---- measurement hooks -------------------------------------------------------
  * Average device time (ms) per featurize call since the last nyxhip_timing_reset(),
  * measured with hipEvents recorded on the launch stream around EVERYTHING the call

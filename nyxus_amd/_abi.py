@@ -313,6 +313,12 @@ class VolZoneSettings(C.Structure):
     _fields_ = [("glrlm_grey_depth", C.c_int32), ("glszm_grey_depth", C.c_int32)]
 
 
+# the distance-zone mask of nyxhip_featurize_volumes_dzones (a mask space of its own); the entry reads nyxhip_settings only
+VDZ_GLDZM = 1 << 0           # D3_GLDZM_feature: 3GLDZM_SDE .. 3GLDZM_ZDE
+VOLDZONE_COLS = 18
+VOLDZONE_MAX_LEVELS = 128    # NYXHIP_VOLDZONE_MAX_LEVELS
+
+
 class Batch3D(C.Structure):
     """``nyxhip_batch3d`` (include/nyxhip.h)."""
 

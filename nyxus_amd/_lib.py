@@ -35,6 +35,7 @@ ABI_SYMBOLS = [
     "nyxhip_vol_n_columns", "nyxhip_vol_column_name", "nyxhip_featurize_volumes",
     "nyxhip_voltex_n_columns", "nyxhip_voltex_column_name", "nyxhip_featurize_volumes_tex",
     "nyxhip_volzone_n_columns", "nyxhip_volzone_column_name", "nyxhip_featurize_volumes_zones",
+    "nyxhip_voldzone_n_columns", "nyxhip_voldzone_column_name", "nyxhip_featurize_volumes_dzones",
 ]
 
 
@@ -163,6 +164,13 @@ def load() -> C.CDLL:
         lib.nyxhip_volzone_column_name.restype = C.c_int
         lib.nyxhip_featurize_volumes_zones.argtypes = [C.c_void_p, P(_abi.Batch3D), C.c_uint32, P(_abi.Settings), P(_abi.VolZoneSettings), C.c_void_p, C.c_size_t]
         lib.nyxhip_featurize_volumes_tex.restype = C.c_int
+    if hasattr(lib, "nyxhip_featurize_volumes_dzones"):
+        lib.nyxhip_voldzone_n_columns.argtypes = [C.c_uint32]
+        lib.nyxhip_voldzone_n_columns.restype = C.c_int
+        lib.nyxhip_voldzone_column_name.argtypes = [C.c_uint32, C.c_int, C.c_char_p, C.c_size_t]
+        lib.nyxhip_voldzone_column_name.restype = C.c_int
+        lib.nyxhip_featurize_volumes_dzones.argtypes = [C.c_void_p, P(_abi.Batch3D), C.c_uint32, P(_abi.Settings), C.c_void_p, C.c_size_t]
+        lib.nyxhip_featurize_volumes_dzones.restype = C.c_int
     if hasattr(lib, "nyxhip_featurize_slides"):  # (absent from older builds of the ABI selected through NYXHIP_LIB for A/B runs)
         lib.nyxhip_featurize_slides.argtypes = [C.c_void_p, P(_abi.Tiles), C.c_uint32, P(_abi.Settings), C.c_void_p, C.c_size_t]
         lib.nyxhip_featurize_slides.restype = C.c_int
@@ -269,6 +277,22 @@ def volzone_column_names(zmask: int) -> List[str]:
         rc = lib.nyxhip_volzone_column_name(zmask, i, buf, 128)
         if rc != 0:
             raise NyxHipError(rc, f"volume zone column {i}")
+        out.append(buf.value.decode())
+    return out
+
+
+def voldzone_column_names(dmask: int = _abi.VDZ_GLDZM) -> List[str]:
+    """The columns of nyxhip_featurize_volumes_dzones for a distance-zone mask (_abi.VDZ_*)."""
+    lib = load()
+    n = lib.nyxhip_voldzone_n_columns(dmask)
+    if n < 0:
+        raise NyxHipError(1, f"bad volume distance-zone mask {dmask:#x}")
+    buf = C.create_string_buffer(128)
+    out = []
+    for i in range(n):
+        rc = lib.nyxhip_voldzone_column_name(dmask, i, buf, 128)
+        if rc != 0:
+            raise NyxHipError(rc, f"volume distance-zone column {i}")
         out.append(buf.value.decode())
     return out
 
@@ -456,6 +480,20 @@ class Context:
     def volumes_zones_device(self, cb: _abi.Batch3D, zmask: int, s: _abi.Settings, t: _abi.VolZoneSettings, out_ptr: int, ld: int):
         """Device pointers in ``cb`` and a device table; synchronous (nyxhip_featurize_volumes_zones)."""
         self._check(self._lib.nyxhip_featurize_volumes_zones(self._h, C.byref(cb), zmask, C.byref(s), C.byref(t), C.c_void_p(out_ptr), ld))
+
+    def volumes_dzones_host(self, batch: _abi.HostBatch3D, dmask: int, s: _abi.Settings, stated: bool = False, max_device_bytes: int = 0) -> np.ndarray:
+        """The distance-zone table [n_roi x 18] of a host batch (nyxhip_featurize_volumes_dzones); NaN / inf are left in place."""
+        ncol = self._lib.nyxhip_voldzone_n_columns(dmask)
+        if ncol < 0:
+            raise NyxHipError(1, f"bad volume distance-zone mask {dmask:#x}")
+        out = np.empty((batch.n_roi, ncol), np.float64)
+        cb = batch.c_struct(stated=stated, max_device_bytes=max_device_bytes)
+        self._check(self._lib.nyxhip_featurize_volumes_dzones(self._h, C.byref(cb), dmask, C.byref(s), out.ctypes.data, ncol))
+        return out
+
+    def volumes_dzones_device(self, cb: _abi.Batch3D, dmask: int, s: _abi.Settings, out_ptr: int, ld: int):
+        """Device pointers in ``cb`` and a device table; synchronous (nyxhip_featurize_volumes_dzones)."""
+        self._check(self._lib.nyxhip_featurize_volumes_dzones(self._h, C.byref(cb), dmask, C.byref(s), C.c_void_p(out_ptr), ld))
 
     def imq_host(self, batch: _abi.HostBatch, s: _abi.Settings) -> np.ndarray:
         """The image-quality columns [n_roi x 4] of a host batch (nyxhip_imq_batch); NaN / inf are left in place."""

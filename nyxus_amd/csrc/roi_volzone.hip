@@ -35,6 +35,7 @@
 #include "launch_util.h"
 #include "roi_vol.h"
 #include "roi_volzone.h"
+#include "vol_zone_prims.h"
 #include "../../include/nyxhip.h"
 
 namespace nyxhip {
@@ -125,31 +126,6 @@ __global__ __launch_bounds__(256) void vz_runs_kernel(const VolzoneArgs A)
         atomicAdd(&G[(uint64_t)c * L + j], v);
     }
     if (tid == 0 && s_max) atomicMax(&H[k], s_max);
-}
-
-// Q sums at once: the 64 per-lane partials of sum q are added in lane order by lane q, and every lane gets the totals
-constexpr int kVzSums = 12;
-template <int Q> __device__ __forceinline__ void vz_lane_sums(double (&v)[Q], double (*s_p)[64], double* s_r, int lane)
-{
-    static_assert(Q <= kVzSums, "the LDS of the closing kernels holds kVzSums rows");
-    __syncthreads();
-#pragma unroll
-    for (int q = 0; q < Q; q++) s_p[q][lane] = v[q];
-    __syncthreads();
-    if (lane < Q) {
-        double t = 0.0;
-#pragma unroll 1
-        for (int l = 0; l < 64; l++) t += s_p[lane][l];
-        s_r[lane] = t;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int q = 0; q < Q; q++) v[q] = s_r[q];
-}
-__device__ __forceinline__ unsigned long long vz_wave_sum_u64(unsigned long long v)
-{
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
 }
 
 // 3d_glrlm.cpp:224-259 and the calc_* functions below it.  The matrix P is [Ng x Nr]; rows of absent levels and columns beyond the
@@ -280,41 +256,6 @@ __global__ __launch_bounds__(256) void vz_runs_ave_kernel(const VolzoneArgs A)
 }
 
 // ---- GLSZM ------------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t vz_ld(const uint32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-// The root of x.  Labels only decrease along a chase, so it takes fewer than `cells` steps; on the way every visited cell is pointed at
-// its grandparent (atomicMin: a label never rises, and stays inside its zone), which keeps the chains short.  `budget` counts the steps
-// of one caller: a chase that uses it up raises the error word and leaves.
-__device__ __forceinline__ uint32_t vz_find(const VolzoneArgs& A, uint32_t* Lb, uint32_t x, uint32_t cells, uint32_t& budget)
-{
-    uint32_t p = vz_ld(&Lb[x]);
-    while (p != x) {
-        if (budget == 0u || p >= cells) { vz_internal(A); budget = 0u; break; }
-        budget--;
-        const uint32_t gp = vz_ld(&Lb[p]);
-        if (gp >= cells) { vz_internal(A); budget = 0u; break; }
-        if (gp != p) atomicMin(&Lb[x], gp);
-        x = p;
-        p = gp;
-    }
-    return x;
-}
-__device__ __forceinline__ void vz_unite(const VolzoneArgs& A, uint32_t* Lb, uint32_t a, uint32_t b, uint32_t cells)
-{
-    // a round is repeated only when another thread lowered the root in between; rounds and chase steps share one budget
-    uint32_t budget = 4u * cells + 1024u;
-    for (;;) {
-        a = vz_find(A, Lb, a, cells, budget);
-        b = vz_find(A, Lb, b, cells, budget);
-        if (a == b || budget == 0u) return;
-        budget--;
-        if (a < b) { const uint32_t t = a; a = b; b = t; }
-        const uint32_t old = atomicMin(&Lb[a], b);         // a was a root when its label was still a
-        if (old == a) return;
-        a = old;
-    }
-}
-
 struct VzRange { uint32_t cells, c0, c1; bool any; };
 __device__ __forceinline__ VzRange vz_range(const VolzoneArgs& A, const VzRoi& R)
 {
@@ -369,7 +310,7 @@ __global__ __launch_bounds__(256) void vz_zone_merge_kernel(const VolzoneArgs A)
                     const int nx = x + dx;
                     if (nx < 0 || nx >= w) continue;
                     const uint32_t n = ((uint32_t)nz * R.h + (uint32_t)ny) * R.w + (uint32_t)nx;
-                    if (D[n] == c) vz_unite(A, Lb, i, n, g.cells);
+                    if (D[n] == c) vz_unite(A.status, Lb, i, n, g.cells);
                 }
             }
         }
@@ -389,7 +330,7 @@ __global__ __launch_bounds__(256) void vz_zone_count_kernel(const VolzoneArgs A)
         uint32_t r = kVzNoLabel;
         if (i < g.c1 && vz_ld(&Lb[i]) != kVzNoLabel) {
             uint32_t budget = g.cells;
-            r = vz_find(A, Lb, i, g.cells, budget);
+            r = vz_find(A.status, Lb, i, g.cells, budget);
             __hip_atomic_store(&Lb[i], r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // (a root keeps its own index)
         }
         const unsigned long long have = __ballot(r != kVzNoLabel);

@@ -4,7 +4,9 @@ The reference keeps its 3-D codes in an enum of their own (featureset.h:643-) wi
 (featureset.cpp:671-) and groups `*3D_...*` (:940-).  Five classes are served: the voxel-intensity class and the 3-D GLCM class by the
 volume mask of nyxhip_featurize_volumes, the 3-D GLDM, NGLDM and NGTDM classes by the texture mask of nyxhip_featurize_volumes_tex.
 `featureset.expand`, its groups and the `Nyxus` class know nothing of them.  Two more classes, the 3-D GLRLM and GLSZM, are served by the
-zone mask of nyxhip_featurize_volumes_zones through `expand3d_zones` and `Nyxus3DZones`; `expand3d` and `Nyxus3D` refuse them.
+zone mask of nyxhip_featurize_volumes_zones through `expand3d_zones` and `Nyxus3DZones`; `expand3d` and `Nyxus3D` refuse them.  The last
+texture class, the 3-D GLDZM, is served by the distance-zone mask of nyxhip_featurize_volumes_dzones through `expand3d_dzones` and
+`Nyxus3DDistanceZones`; the other expansions and classes refuse it.
 """
 from __future__ import annotations
 
@@ -51,6 +53,14 @@ VTEX_OF = {**{c: _abi.VTEX_GLDM for c in GLDM_3D}, **{c: _abi.VTEX_NGLDM for c i
 GROUPS_3D_ZONES = {"*3D_GLRLM*": GLRLM_3D, "*3D_GLSZM*": GLSZM_3D}
 ORDER_3D_ZONES = ORDER_3D + GLSZM_3D + GLRLM_3D
 VZONE_OF = {**{c: _abi.VZONE_GLRLM for c in GLRLM_3D}, **{c: _abi.VZONE_GLSZM for c in GLSZM_3D}}
+# Feature3D order (featureset.h:815-833, names featureset.cpp:842-859): in the enum the GLDZM block stands between the GLDM and the NGLDM
+# blocks.  Served by Nyxus3DDistanceZones / expand3d_dzones only (the distance-zone mask of nyxhip_featurize_volumes_dzones); expand3d
+# and expand3d_zones refuse it.
+GLDZM_3D = ["3GLDZM_" + n for n in ("SDE", "LDE", "LGLZE", "HGLZE", "SDLGLE", "SDHGLE", "LDLGLE", "LDHGLE", "GLNU", "GLNUN", "ZDNU", "ZDNUN", "ZP", "GLM", "GLV", "ZDM",
+                                    "ZDV", "ZDE")]
+GROUPS_3D_DZONES = {"*3D_GLDZM*": GLDZM_3D}
+ORDER_3D_DZONES = INTENSITY_3D + GLCM_3D + GLDM_3D + GLDZM_3D + NGLDM_3D + NGTDM_3D + GLSZM_3D + GLRLM_3D
+VDZ_OF = {c: _abi.VDZ_GLDZM for c in GLDZM_3D}
 VFAM_OF = {**{c: _abi.VFAM_INTENSITY for c in INTENSITY_3D}, **{c: _abi.VFAM_GLCM for c in GLCM_3D}, **{c: 0 for c in VTEX_OF}}
 
 
@@ -58,7 +68,8 @@ def _refusal(names) -> str:
     return (f"feature(s) {names} are not served by the MI355X volume path. Served: the groups {sorted(GROUPS_3D)} and the individual codes of the "
             f"five classes (3COV .. 3UNIFORMITY_PIU, 3GLCM_ACOR .. 3GLCM_SUMVARIANCE_AVE, 3GLDM_SDE .. 3GLDM_LDHGLE, 3NGLDM_LDE .. 3NGLDM_DCENE, "
             "3NGTDM_COARSENESS .. 3NGTDM_STRENGTH); *3D_ALL*, the 3-D shape class and the 3-D GLRLM, GLSZM and GLDZM classes are not served. "
-            "The 3-D GLRLM and GLSZM classes are served by Nyxus3DZones (featureset3d.expand3d_zones)")
+            "The 3-D GLRLM and GLSZM classes are served by Nyxus3DZones (featureset3d.expand3d_zones), the 3-D GLDZM class by "
+            "Nyxus3DDistanceZones (featureset3d.expand3d_dzones)")
 
 
 def expand3d(features: List[str]) -> Tuple[int, List[str]]:
@@ -101,6 +112,31 @@ def expand3d_zones(features: List[str]) -> Tuple[int, List[str]]:
     mask, req = expand3d(rest) if rest or not zones else (0, [])
     want = set(req) | zones
     return mask, [c for c in ORDER_3D_ZONES if c in want]
+
+
+def expand3d_dzones(features: List[str]) -> Tuple[int, List[str]]:
+    """expand3d_zones with the group *3D_GLDZM* and its codes served too: (volume mask, the requested codes in Feature3D order).  The
+    distance-zone mask is dzone_mask(codes)."""
+    rest, dz = [], set()
+    for f in features:
+        u = f.strip().upper() if isinstance(f, str) else None
+        if u in GROUPS_3D_DZONES:
+            dz.update(GROUPS_3D_DZONES[u])
+        elif u in VDZ_OF:
+            dz.add(u)
+        else:
+            rest.append(f)
+    mask, req = expand3d_zones(rest) if rest or not dz else (0, [])
+    want = set(req) | dz
+    return mask, [c for c in ORDER_3D_DZONES if c in want]
+
+
+def dzone_mask(codes: List[str]) -> int:
+    """The distance-zone mask (nyxhip_featurize_volumes_dzones) that serves the GLDZM codes among `codes`; 0: none."""
+    m = 0
+    for c in codes:
+        m |= VDZ_OF.get(c, 0)
+    return m
 
 
 def zone_mask(codes: List[str]) -> int:

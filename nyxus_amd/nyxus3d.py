@@ -7,7 +7,8 @@ Five classes of the `Feature3D` enum are served: the voxel-intensity class (`*3D
 (nyxus.py:1014-1110).  `featurize` is the in-memory face: it mirrors `Nyxus.featurize` for volumes (the reference's class has none).
 The file workflows are not served: NIfTI / DICOM / z-stack ingest is outside this package.
 
-`Nyxus3DZones` (below) is `Nyxus3D` with the 3-D GLRLM and GLSZM classes served too (nyxhip_featurize_volumes_zones).
+`Nyxus3DZones` (below) is `Nyxus3D` with the 3-D GLRLM and GLSZM classes served too (nyxhip_featurize_volumes_zones), and
+`Nyxus3DDistanceZones` is `Nyxus3DZones` with the 3-D GLDZM class served too (nyxhip_featurize_volumes_dzones).
 """
 from __future__ import annotations
 
@@ -285,3 +286,44 @@ class Nyxus3DZones(Nyxus3D):
                                            f" with at most {_abi.VOLZONE_MAX_LEVELS} levels (negative: radiomics binning)") from e
                 raise
         return parts[0] if len(parts) == 1 else np.hstack(parts)
+
+
+class Nyxus3DDistanceZones(Nyxus3DZones):
+    """`Nyxus3DZones` with the 3-D GLDZM class served too (nyxhip_featurize_volumes_dzones): the group `*3D_GLDZM*` (18 codes) and its
+    codes, beside everything `Nyxus3DZones` takes.  Same constructor, same `featurize`, same metaparameters; the DataFrame columns stand
+    in Feature3D order (featureset.h: the GLDZM block between the GLDM and the NGLDM blocks).  The class bins with `coarse_gray_depth`
+    (or not at all in IBSI mode): the reference has no `3gldzm/greydepth` metaparameter, and this class refuses that key as
+    `Nyxus3DZones` does.  A cell of level 0 forms no zone and is always a border, in every binning mode.
+    `Nyxus3D` and `Nyxus3DZones` keep refusing the class; `*3D_ALL*` stays refused because the 3-D shape class is not served."""
+
+    def __init__(self, features: List[str], **kwargs):
+        featureset3d.expand3d_dzones(list(features))                   # raises the refusal of expand3d for anything else
+        dz_only = [f for f in features if isinstance(f, str) and (f.strip().upper() in featureset3d.GROUPS_3D_DZONES or f.strip().upper() in featureset3d.VDZ_OF)]
+        rest = [f for f in features if f not in dz_only]
+        super().__init__(rest if rest else ["3MEAN"], **kwargs)        # (the checks of the keyword arguments; the request is set below)
+        self._features = list(features)
+        self._mask, self._requested = featureset3d.expand3d_dzones(self._features)
+        self._tex_mask = featureset3d.tex_mask(self._requested)
+        self._zone_mask = featureset3d.zone_mask(self._requested)
+        self._dzone_mask = featureset3d.dzone_mask(self._requested)
+
+    def _columns(self):
+        names = ((_lib.vol_column_names(self._mask, self._settings) if self._mask else []) +
+                 (_lib.voltex_column_names(self._tex_mask) if self._tex_mask else []) +
+                 (_lib.volzone_column_names(self._zone_mask) if self._zone_mask else []) +
+                 (_lib.voldzone_column_names(self._dzone_mask) if self._dzone_mask else []))
+        sel = [names.index(featureset3d.table_column(c)) for c in self._requested]
+        return list(self._requested), sel
+
+    def _tables(self, b: _abi.HostBatch3D, max_device_bytes: int) -> np.ndarray:
+        """The tables `Nyxus3DZones` assembles and the distance-zone table side by side, whichever the request needs."""
+        parts = [super()._tables(b, max_device_bytes)] if (self._mask or self._tex_mask or self._zone_mask) else []
+        if self._dzone_mask:
+            parts.append(self._context().volumes_dzones_host(b, self._dzone_mask, self._settings, max_device_bytes=max_device_bytes))
+        return parts[0] if len(parts) == 1 else np.hstack(parts)
+
+    def featurize_directory(self, *args, **kwargs):
+        raise NotImplementedError("Nyxus3DDistanceZones.featurize_directory: NIfTI / DICOM / z-stack ingest is not served; assemble the volumes and call featurize()")
+
+    def featurize_files(self, *args, **kwargs):
+        raise NotImplementedError("Nyxus3DDistanceZones.featurize_files: NIfTI / DICOM / z-stack ingest is not served; assemble the volumes and call featurize()")
