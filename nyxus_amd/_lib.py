@@ -181,120 +181,59 @@ def load() -> C.CDLL:
     return lib
 
 
-def column_names(mask: int, s: _abi.Settings) -> List[str]:
-    lib = load()
-    n = lib.nyxhip_n_columns(mask, C.byref(s))
+def _catalogue(n_columns, column_name, lead: tuple, column_noun: str, mask_noun: Optional[str] = None) -> List[str]:
+    """The names of an n_columns / column_name pair of the library.  `lead`: the arguments ahead of the column index (mask, settings, or
+    nothing); `n_columns`: the C function, or the count itself; the nouns are those of the error texts (`mask_noun`: of a refused mask)."""
+    n = n_columns(*lead) if callable(n_columns) else n_columns
+    if n < 0 and mask_noun:
+        raise NyxHipError(1, f"bad {mask_noun} {lead[0]:#x}")
     buf = C.create_string_buffer(128)
     out = []
     for i in range(n):
-        rc = lib.nyxhip_column_name(mask, C.byref(s), i, buf, 128)
+        rc = column_name(*lead, i, buf, 128)
         if rc != 0:
-            raise NyxHipError(rc, f"column {i}")
+            raise NyxHipError(rc, f"{column_noun} {i}")
         out.append(buf.value.decode())
     return out
+
+
+def column_names(mask: int, s: _abi.Settings) -> List[str]:
+    return _catalogue(load().nyxhip_n_columns, load().nyxhip_column_name, (mask, C.byref(s)), "column")
 
 
 def neighbor_column_names() -> List[str]:
     """The nine columns of nyxhip_neighbors_batch / _tiles, enum order."""
-    lib = load()
-    buf = C.create_string_buffer(128)
-    out = []
-    for i in range(_abi.NEIGHBOR_COLS):
-        rc = lib.nyxhip_neighbor_column_name(i, buf, 128)
-        if rc != 0:
-            raise NyxHipError(rc, f"neighbor column {i}")
-        out.append(buf.value.decode())
-    return out
+    return _catalogue(_abi.NEIGHBOR_COLS, load().nyxhip_neighbor_column_name, (), "neighbor column")
 
 
 def ih_column_names() -> List[str]:
     """The 46 columns of nyxhip_ih_batch / _tiles, enum order."""
-    lib = load()
-    buf = C.create_string_buffer(128)
-    out = []
-    for i in range(_abi.IH_COLS):
-        rc = lib.nyxhip_ih_column_name(i, buf, 128)
-        if rc != 0:
-            raise NyxHipError(rc, f"intensity-histogram column {i}")
-        out.append(buf.value.decode())
-    return out
+    return _catalogue(_abi.IH_COLS, load().nyxhip_ih_column_name, (), "intensity-histogram column")
 
 
 def imq_column_names() -> List[str]:
     """The 4 columns of nyxhip_imq_batch / _tiles / _slides, enum order."""
-    lib = load()
-    buf = C.create_string_buffer(128)
-    out = []
-    for i in range(_abi.IMQ_COLS):
-        rc = lib.nyxhip_imq_column_name(i, buf, 128)
-        if rc != 0:
-            raise NyxHipError(rc, f"image-quality column {i}")
-        out.append(buf.value.decode())
-    return out
+    return _catalogue(_abi.IMQ_COLS, load().nyxhip_imq_column_name, (), "image-quality column")
 
 
 def vol_column_names(vmask: int, s: _abi.Settings) -> List[str]:
     """The columns of nyxhip_featurize_volumes for a volume mask (_abi.VFAM_*)."""
-    lib = load()
-    n = lib.nyxhip_vol_n_columns(vmask, C.byref(s))
-    if n < 0:
-        raise NyxHipError(1, f"bad volume mask {vmask:#x}")
-    buf = C.create_string_buffer(128)
-    out = []
-    for i in range(n):
-        rc = lib.nyxhip_vol_column_name(vmask, C.byref(s), i, buf, 128)
-        if rc != 0:
-            raise NyxHipError(rc, f"volume column {i}")
-        out.append(buf.value.decode())
-    return out
+    return _catalogue(load().nyxhip_vol_n_columns, load().nyxhip_vol_column_name, (vmask, C.byref(s)), "volume column", "volume mask")
 
 
 def voltex_column_names(tmask: int) -> List[str]:
     """The columns of nyxhip_featurize_volumes_tex for a texture mask (_abi.VTEX_*)."""
-    lib = load()
-    n = lib.nyxhip_voltex_n_columns(tmask)
-    if n < 0:
-        raise NyxHipError(1, f"bad volume texture mask {tmask:#x}")
-    buf = C.create_string_buffer(128)
-    out = []
-    for i in range(n):
-        rc = lib.nyxhip_voltex_column_name(tmask, i, buf, 128)
-        if rc != 0:
-            raise NyxHipError(rc, f"volume texture column {i}")
-        out.append(buf.value.decode())
-    return out
+    return _catalogue(load().nyxhip_voltex_n_columns, load().nyxhip_voltex_column_name, (tmask,), "volume texture column", "volume texture mask")
 
 
 def volzone_column_names(zmask: int) -> List[str]:
     """The columns of nyxhip_featurize_volumes_zones for a zone mask (_abi.VZONE_*)."""
-    lib = load()
-    n = lib.nyxhip_volzone_n_columns(zmask)
-    if n < 0:
-        raise NyxHipError(1, f"bad volume zone mask {zmask:#x}")
-    buf = C.create_string_buffer(128)
-    out = []
-    for i in range(n):
-        rc = lib.nyxhip_volzone_column_name(zmask, i, buf, 128)
-        if rc != 0:
-            raise NyxHipError(rc, f"volume zone column {i}")
-        out.append(buf.value.decode())
-    return out
+    return _catalogue(load().nyxhip_volzone_n_columns, load().nyxhip_volzone_column_name, (zmask,), "volume zone column", "volume zone mask")
 
 
 def voldzone_column_names(dmask: int = _abi.VDZ_GLDZM) -> List[str]:
     """The columns of nyxhip_featurize_volumes_dzones for a distance-zone mask (_abi.VDZ_*)."""
-    lib = load()
-    n = lib.nyxhip_voldzone_n_columns(dmask)
-    if n < 0:
-        raise NyxHipError(1, f"bad volume distance-zone mask {dmask:#x}")
-    buf = C.create_string_buffer(128)
-    out = []
-    for i in range(n):
-        rc = lib.nyxhip_voldzone_column_name(dmask, i, buf, 128)
-        if rc != 0:
-            raise NyxHipError(rc, f"volume distance-zone column {i}")
-        out.append(buf.value.decode())
-    return out
+    return _catalogue(load().nyxhip_voldzone_n_columns, load().nyxhip_voldzone_column_name, (dmask,), "volume distance-zone column", "volume distance-zone mask")
 
 
 # Contexts still open at interpreter exit are destroyed here, while the HIP runtime is certainly alive (Python's atexit handlers
@@ -437,15 +376,21 @@ class Context:
         self._check(self._lib.nyxhip_fetch_result(self._h, labels.ctypes.data, tiles.ctypes.data, table.ctypes.data, ncol))
         return tiles, labels, table
 
-    def volumes_host(self, batch: _abi.HostBatch3D, vmask: int, s: _abi.Settings, stated: bool = False, max_device_bytes: int = 0) -> np.ndarray:
-        """The volume table [n_roi x nyxhip_vol_n_columns] of a host batch (nyxhip_featurize_volumes); NaN / inf are left in place."""
-        ncol = self._lib.nyxhip_vol_n_columns(vmask, C.byref(s))
+    def _volume_table(self, entry, n_columns, mask_noun: str, batch: _abi.HostBatch3D, mask: int, n_lead: tuple, lead: tuple, stated: bool,
+                      max_device_bytes: int) -> np.ndarray:
+        """The table [n_roi x n_columns(mask, *n_lead)] of a host batch through a volume entry: entry(ctx, batch, mask, *lead, table, ld)."""
+        ncol = n_columns(mask, *n_lead)
         if ncol < 0:
-            raise NyxHipError(1, f"bad volume mask {vmask:#x}")
+            raise NyxHipError(1, f"bad {mask_noun} {mask:#x}")
         out = np.empty((batch.n_roi, ncol), np.float64)
         cb = batch.c_struct(stated=stated, max_device_bytes=max_device_bytes)
-        self._check(self._lib.nyxhip_featurize_volumes(self._h, C.byref(cb), vmask, C.byref(s), out.ctypes.data, ncol))
+        self._check(entry(self._h, C.byref(cb), mask, *lead, out.ctypes.data, ncol))
         return out
+
+    def volumes_host(self, batch: _abi.HostBatch3D, vmask: int, s: _abi.Settings, stated: bool = False, max_device_bytes: int = 0) -> np.ndarray:
+        """The volume table [n_roi x nyxhip_vol_n_columns] of a host batch (nyxhip_featurize_volumes); NaN / inf are left in place."""
+        return self._volume_table(self._lib.nyxhip_featurize_volumes, self._lib.nyxhip_vol_n_columns, "volume mask", batch, vmask, (C.byref(s),), (C.byref(s),), stated,
+                                  max_device_bytes)
 
     def volumes_device(self, cb: _abi.Batch3D, vmask: int, s: _abi.Settings, out_ptr: int, ld: int):
         """Device pointers in ``cb`` and a device table; synchronous (nyxhip_featurize_volumes)."""
@@ -454,13 +399,8 @@ class Context:
     def volumes_tex_host(self, batch: _abi.HostBatch3D, tmask: int, s: _abi.Settings, t: _abi.VolTexSettings, stated: bool = False,
                          max_device_bytes: int = 0) -> np.ndarray:
         """The texture table [n_roi x nyxhip_voltex_n_columns] of a host batch (nyxhip_featurize_volumes_tex); NaN / inf are left in place."""
-        ncol = self._lib.nyxhip_voltex_n_columns(tmask)
-        if ncol < 0:
-            raise NyxHipError(1, f"bad volume texture mask {tmask:#x}")
-        out = np.empty((batch.n_roi, ncol), np.float64)
-        cb = batch.c_struct(stated=stated, max_device_bytes=max_device_bytes)
-        self._check(self._lib.nyxhip_featurize_volumes_tex(self._h, C.byref(cb), tmask, C.byref(s), C.byref(t), out.ctypes.data, ncol))
-        return out
+        return self._volume_table(self._lib.nyxhip_featurize_volumes_tex, self._lib.nyxhip_voltex_n_columns, "volume texture mask", batch, tmask, (),
+                                  (C.byref(s), C.byref(t)), stated, max_device_bytes)
 
     def volumes_tex_device(self, cb: _abi.Batch3D, tmask: int, s: _abi.Settings, t: _abi.VolTexSettings, out_ptr: int, ld: int):
         """Device pointers in ``cb`` and a device table; synchronous (nyxhip_featurize_volumes_tex)."""
@@ -469,13 +409,8 @@ class Context:
     def volumes_zones_host(self, batch: _abi.HostBatch3D, zmask: int, s: _abi.Settings, t: _abi.VolZoneSettings, stated: bool = False,
                            max_device_bytes: int = 0) -> np.ndarray:
         """The zone table [n_roi x nyxhip_volzone_n_columns] of a host batch (nyxhip_featurize_volumes_zones); NaN / inf are left in place."""
-        ncol = self._lib.nyxhip_volzone_n_columns(zmask)
-        if ncol < 0:
-            raise NyxHipError(1, f"bad volume zone mask {zmask:#x}")
-        out = np.empty((batch.n_roi, ncol), np.float64)
-        cb = batch.c_struct(stated=stated, max_device_bytes=max_device_bytes)
-        self._check(self._lib.nyxhip_featurize_volumes_zones(self._h, C.byref(cb), zmask, C.byref(s), C.byref(t), out.ctypes.data, ncol))
-        return out
+        return self._volume_table(self._lib.nyxhip_featurize_volumes_zones, self._lib.nyxhip_volzone_n_columns, "volume zone mask", batch, zmask, (),
+                                  (C.byref(s), C.byref(t)), stated, max_device_bytes)
 
     def volumes_zones_device(self, cb: _abi.Batch3D, zmask: int, s: _abi.Settings, t: _abi.VolZoneSettings, out_ptr: int, ld: int):
         """Device pointers in ``cb`` and a device table; synchronous (nyxhip_featurize_volumes_zones)."""
@@ -483,13 +418,8 @@ class Context:
 
     def volumes_dzones_host(self, batch: _abi.HostBatch3D, dmask: int, s: _abi.Settings, stated: bool = False, max_device_bytes: int = 0) -> np.ndarray:
         """The distance-zone table [n_roi x 18] of a host batch (nyxhip_featurize_volumes_dzones); NaN / inf are left in place."""
-        ncol = self._lib.nyxhip_voldzone_n_columns(dmask)
-        if ncol < 0:
-            raise NyxHipError(1, f"bad volume distance-zone mask {dmask:#x}")
-        out = np.empty((batch.n_roi, ncol), np.float64)
-        cb = batch.c_struct(stated=stated, max_device_bytes=max_device_bytes)
-        self._check(self._lib.nyxhip_featurize_volumes_dzones(self._h, C.byref(cb), dmask, C.byref(s), out.ctypes.data, ncol))
-        return out
+        return self._volume_table(self._lib.nyxhip_featurize_volumes_dzones, self._lib.nyxhip_voldzone_n_columns, "volume distance-zone mask", batch, dmask, (),
+                                  (C.byref(s),), stated, max_device_bytes)
 
     def volumes_dzones_device(self, cb: _abi.Batch3D, dmask: int, s: _abi.Settings, out_ptr: int, ld: int):
         """Device pointers in ``cb`` and a device table; synchronous (nyxhip_featurize_volumes_dzones)."""

@@ -1,6 +1,6 @@
 // nyxhip_vol.hip -- the volume entries of include/nyxhip.h: the column catalogue of the volume mask (nyxhip_vol_n_columns,
-// nyxhip_vol_column_name) and nyxhip_featurize_volumes: checks, staging of a host batch, chunks of ROIs under the device budget, the
-// launches of roi_vol.hip.
+// nyxhip_vol_column_name) and nyxhip_featurize_volumes: its checks and the launches of roi_vol.hip per chunk.  Defines the host path
+// of vol_host.h that the four volume entry files share.
 #include "nyxhip_ctx.h"
 #include "vol_host.h"
 
@@ -29,21 +29,10 @@ constexpr uint32_t kVolMaxHistBins = 16384;            // the bounds of the inte
 bool vol_mask_ok(uint32_t m) { return m != 0 && (m & ~(uint32_t)NYXHIP_VFAM_ALL) == 0; }
 int vol_cols(uint32_t m) { return ((m & NYXHIP_VFAM_INTENSITY) ? kVolIntensityCols : 0) + ((m & NYXHIP_VFAM_GLCM) ? kVolGlcmCols : 0); }
 
-size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
-
-int vol_check_status(nyxhip_ctx* ctx)
-{
-    const int rc = check_status(ctx);
-    if (rc == NYXHIP_ERR_UNSUPPORTED)
-        return fail(ctx, rc, "volumes: the 3-D GLCM matrix lives in LDS up to " + std::to_string(kVolLevelCap) +
-                                 " levels, and an ROI has a larger intensity (IBSI mode: the levels are the intensities)");
-    if (rc == NYXHIP_ERR_ROI_TOO_LARGE)
-        return fail(ctx, rc, "volumes: an ROI exceeds the stated extrema, a box side of " + std::to_string(kVolMaxSide) + " or " +
-                                 std::to_string(kVolMaxCells) + " cells");
-    if (rc == NYXHIP_ERR_INVALID_ARG)
-        return fail(ctx, rc, "volumes: a voxel lies outside its box, or an intensity outside [min_inten, max_inten]");
-    return rc;
-}
+const VolTexts kTexts = {
+    "volumes", "settings", "(px_offset, inten, min_inten, max_inten; for the GLCM block also x, y, z, bbox_w, bbox_h, bbox_d)",
+    "volumes: the 3-D GLCM matrix lives in LDS up to " + std::to_string(kVolLevelCap) + " levels", "IBSI mode",
+    ", or an intensity outside [min_inten, max_inten]", nullptr, false};
 
 // the ROIs of a device-resident batch -> d_out [n_roi x ld] (device), in chunks whose workspace fits the budget; enqueued on the stream
 int vol_device(nyxhip_ctx* ctx, const nyxhip_batch3d* b, uint32_t vmask, const nyxhip_settings* s, double* d_out, size_t ld, uint32_t max_px,
@@ -56,47 +45,34 @@ int vol_device(nyxhip_ctx* ctx, const nyxhip_batch3d* b, uint32_t vmask, const n
     a.px_offset = b->px_offset; a.x = b->x; a.y = b->y; a.z = b->z; a.inten = b->inten;
     a.bbox_w = b->bbox_w; a.bbox_h = b->bbox_h; a.bbox_d = b->bbox_d; a.vmin = b->min_inten; a.vmax = b->max_inten;
     a.slide_min = b->slide_min; a.slide_max = b->slide_max;
-    a.grey_info = s->ibsi ? 0 : s->glcm_grey_depth;       // 3d_glcm.cpp:51-53
     a.offset = s->glcm_offset; a.symmetric = s->glcm_symmetric;
     a.n_hist = (uint32_t)abs(s->grey_depth);
     a.soft_nan = s->soft_nan; a.out = d_out; a.ld = ld;
     a.col_intensity = inten ? 0 : -1; a.col_glcm = glcm ? (inten ? kVolIntensityCols : 0) : -1;
     a.status = ctx->d_status.as<int>();
-    a.max_cells = max_cells ? max_cells : 1u; a.max_px = max_px ? max_px : 1u;
+    const size_t per_roi = vol_layout(a, vmask, s, max_px, max_cells);
     a.stage_cells = (std::min(a.max_cells, kVolLdsCells) + 15u) & ~15u;
     a.ng_bound = a.grey_info ? (uint32_t)abs(a.grey_info) : kVolLevelCap;
-    a.box_stride = glcm ? al256(a.max_cells) : 0;
-    a.key_stride = inten ? (al256(4 * (size_t)a.max_px) >> 2) : 0;
-    const size_t per_roi = a.box_stride + 8 * (size_t)a.key_stride;
-    size_t budget = 0;
-    if (int rc = vol_budget(ctx, b, ctx->d_vol.bytes, budget)) return rc;
-    if (per_roi > budget)
-        return fail(ctx, NYXHIP_ERR_ROI_TOO_LARGE, "volumes: the workspace of one ROI (" + std::to_string(per_roi) + " bytes) does not fit max_device_bytes");
-    const uint64_t chunk = std::min<uint64_t>(std::min<uint64_t>(budget / per_roi, 65535), b->n_roi);   // (a grid dimension counts the ROIs of a chunk)
-    HIP_TRY(ctx, ctx->d_vol.reserve((size_t)chunk * per_roi, st));
+    uint64_t chunk = 0;
+    if (int rc = vol_plan_chunks(ctx, kTexts, *b, per_roi, chunk)) return rc;
     a.boxes = ctx->d_vol.as<unsigned char>();
     a.keys = (uint32_t*)(ctx->d_vol.as<char>() + (size_t)chunk * a.box_stride);
     for (uint64_t r0 = 0; r0 < b->n_roi; r0 += chunk) {
         a.roi0 = r0; a.n_roi = std::min<uint64_t>(chunk, b->n_roi - r0);
         if (glcm) {
-            // cells outside the cloud hold the background level
-            HIP_TRY(ctx, hipMemsetAsync(a.boxes, vol_background_level(a.grey_info), (size_t)a.n_roi * a.box_stride, st));
-            if (int rc = launch_vol_bin(a, st)) return fail(ctx, NYXHIP_ERR_HIP, std::string("volume binning kernel: launch failed: ") + hipGetErrorString((hipError_t)rc));
-            if (int rc = launch_vol_glcm(a, st)) return fail(ctx, NYXHIP_ERR_HIP, std::string("3-D GLCM kernel: launch failed: ") + hipGetErrorString((hipError_t)rc));
+            if (int rc = vol_bin_launch(ctx, a)) return rc;
+            if (int rc = launched(ctx, launch_vol_glcm(a, st), "3-D GLCM kernel")) return rc;
         }
         if (inten)
-            if (int rc = launch_vol_intensity(a, st)) return fail(ctx, NYXHIP_ERR_HIP, std::string("voxel-intensity kernel: launch failed: ") + hipGetErrorString((hipError_t)rc));
+            if (int rc = launched(ctx, launch_vol_intensity(a, st), "voxel-intensity kernel")) return rc;
     }
     return NYXHIP_OK;
 }
 
-} // namespace
-
-namespace nyxhip {
-
-int vol_budget(nyxhip_ctx* ctx, const nyxhip_batch3d* b, size_t held, size_t& budget)
+// the budget of a call's workspace: max_device_bytes, or half of the free device memory (`held`: what the workspace buffer already holds)
+int vol_budget(nyxhip_ctx* ctx, const nyxhip_batch3d& b, size_t held, size_t& budget)
 {
-    budget = (size_t)b->max_device_bytes;
+    budget = (size_t)b.max_device_bytes;
     if (budget == 0) {
         size_t fr = 0, tot = 0;
         HIP_TRY(ctx, hipMemGetInfo(&fr, &tot));
@@ -104,6 +80,74 @@ int vol_budget(nyxhip_ctx* ctx, const nyxhip_batch3d* b, size_t held, size_t& bu
         budget = (fr + held) / 2 / (size_t)sharers;
     }
     return NYXHIP_OK;
+}
+
+// the device status of a call, in the entry's words
+int vol_check_status(nyxhip_ctx* ctx, const VolTexts& tx)
+{
+    const int rc = check_status(ctx);
+    const std::string label = std::string(tx.label) + ": ";
+    if (rc == NYXHIP_ERR_UNSUPPORTED) return fail(ctx, rc, tx.cap + ", and an ROI has a larger intensity (" + tx.unbinned + ": the levels are the intensities)");
+    if (rc == NYXHIP_ERR_ROI_TOO_LARGE)
+        return fail(ctx, rc, label + "an ROI exceeds the stated extrema, a box side of " + std::to_string(kVolMaxSide) + " or " + std::to_string(kVolMaxCells) + " cells");
+    if (rc == NYXHIP_ERR_INVALID_ARG) return fail(ctx, rc, label + "a voxel lies outside its box" + tx.outside);
+    if (rc == NYXHIP_ERR_INTERNAL && tx.internal) return fail(ctx, rc, label + tx.internal);
+    return rc;
+}
+
+} // namespace
+
+namespace nyxhip {
+
+int vol_entry_checks(nyxhip_ctx* ctx, const VolTexts& tx, const nyxhip_batch3d* b, bool have_settings, const double* out, const char* bad_mask, bool boxes,
+                     bool slide_pair, size_t ncol, size_t ld)
+{
+    if (!b || !have_settings || !out) return fail(ctx, NYXHIP_ERR_INVALID_ARG, std::string("null batch / ") + tx.settings + " / out_table");
+    if (bad_mask) return fail(ctx, NYXHIP_ERR_INVALID_ARG, bad_mask);
+    if (b->n_roi && (!b->px_offset || !b->inten || !b->min_inten || !b->max_inten || (boxes && (!b->x || !b->y || !b->z || !b->bbox_w || !b->bbox_h || !b->bbox_d))))
+        return fail(ctx, NYXHIP_ERR_INVALID_ARG, std::string("batch has null array pointers ") + tx.arrays);
+    if (slide_pair && (b->slide_min == nullptr) != (b->slide_max == nullptr))
+        return fail(ctx, NYXHIP_ERR_INVALID_ARG, "slide_min and slide_max must both be given or both NULL");
+    if (ld < ncol) return fail(ctx, NYXHIP_ERR_INVALID_ARG, "out_ld smaller than the column count");
+    if (b->n_roi > 0x7FFFFFFFull) return fail(ctx, NYXHIP_ERR_INVALID_ARG, "too many ROIs in one batch");
+    if (b->memory != NYXHIP_MEM_DEVICE && b->memory != NYXHIP_MEM_HOST) return fail(ctx, NYXHIP_ERR_INVALID_ARG, "bad batch->memory");
+    return NYXHIP_OK;
+}
+
+int launched(nyxhip_ctx* ctx, int rc, const char* what)
+{
+    return rc ? fail(ctx, NYXHIP_ERR_HIP, std::string(what) + ": launch failed: " + hipGetErrorString((hipError_t)rc)) : NYXHIP_OK;
+}
+
+int vol_plan_chunks(nyxhip_ctx* ctx, const VolTexts& tx, const nyxhip_batch3d& b, size_t per_roi, uint64_t& chunk)
+{
+    size_t budget = 0;
+    if (per_roi)
+        if (int rc = vol_budget(ctx, b, ctx->d_vol.bytes, budget)) return rc;
+    chunk = vol_chunk(per_roi, budget, b.n_roi);
+    if (chunk == 0)
+        return fail(ctx, NYXHIP_ERR_ROI_TOO_LARGE, std::string(tx.label) + ": the workspace of one ROI (" + std::to_string(per_roi) + " bytes) does not fit max_device_bytes");
+    if (per_roi) HIP_TRY(ctx, ctx->d_vol.reserve((size_t)chunk * per_roi, ctx->stream()));
+    return NYXHIP_OK;
+}
+
+int vol_bin_launch(nyxhip_ctx* ctx, const VolArgs& v)
+{
+    hipStream_t st = ctx->stream();
+    HIP_TRY(ctx, hipMemsetAsync(v.boxes, vol_background_level(v.grey_info), (size_t)v.n_roi * v.box_stride, st));
+    return launched(ctx, launch_vol_bin(v, st), "volume binning kernel");
+}
+
+int vol_bin(nyxhip_ctx* ctx, const nyxhip_batch3d& b, uint64_t roi0, uint64_t n_roi, unsigned char* boxes, uint64_t box_stride, int grey_info, uint32_t max_px,
+            uint32_t max_cells)
+{
+    VolArgs v;
+    memset(&v, 0, sizeof(v));
+    v.roi0 = roi0; v.n_roi = n_roi; v.px_offset = b.px_offset; v.x = b.x; v.y = b.y; v.z = b.z; v.inten = b.inten;
+    v.bbox_w = b.bbox_w; v.bbox_h = b.bbox_h; v.bbox_d = b.bbox_d; v.vmin = b.min_inten; v.vmax = b.max_inten;
+    v.grey_info = grey_info; v.status = ctx->d_status.as<int>(); v.boxes = boxes; v.box_stride = box_stride;
+    v.max_cells = max_cells ? max_cells : 1u; v.max_px = max_px ? max_px : 1u;
+    return vol_bin_launch(ctx, v);
 }
 
 // checks of the per-ROI arrays on the host (a host batch, or the copies of a device batch); the extrema they imply
@@ -125,9 +169,11 @@ int vol_scan(nyxhip_ctx* ctx, uint64_t nr, const uint64_t* off, const uint32_t* 
     return NYXHIP_OK;
 }
 
-// what both volume entries do behind their own checks: the extrema (stated or derived), the staging of a host batch into one device
-// slab, `body` on the device batch, the copy back, the device status through `check`.  `glcm`: the entry reads coordinates and boxes.
-int vol_run(nyxhip_ctx* ctx, const nyxhip_batch3d* b, bool glcm, size_t ncol, double* out, size_t ld, const VolBody& body, int (*check)(nyxhip_ctx*))
+// what every volume entry does behind its own checks: the extrema (stated or derived), the box sides of the batch where the entry sizes
+// its workspace by them (from the host arrays this function holds anyway; copied only for a device batch with stated extrema), the
+// staging of a host batch into one device slab, `body` on the device batch, the copy back, the device status in the entry's words.
+// `boxes`: the entry reads coordinates and boxes.
+int vol_run(nyxhip_ctx* ctx, const VolTexts& tx, const nyxhip_batch3d* b, bool boxes, size_t ncol, double* out, size_t ld, const VolBody& body)
 {
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (b->n_roi == 0) return NYXHIP_OK;
@@ -136,38 +182,43 @@ int vol_run(nyxhip_ctx* ctx, const nyxhip_batch3d* b, bool glcm, size_t ncol, do
     // a batch without boxes (the intensity block alone): every ROI's box counts as one cell
     std::vector<uint32_t> ones;
     uint32_t max_px = b->max_px, max_cells = b->max_bbox_cells;
+    VolSides sides = {{1u, 1u, 1u}, vdz_pitch(1u, 1u)};
 
     if (b->memory == NYXHIP_MEM_DEVICE) {
-        if (max_px == 0) {                                 // derive: one copy of the offsets and the boxes
-            std::vector<uint64_t> off(nr + 1);
+        const bool derive = max_px == 0;
+        if (!derive && boxes && (max_cells == 0 || max_cells > kVolMaxCells))
+            return max_cells ? fail(ctx, NYXHIP_ERR_ROI_TOO_LARGE, "volumes: a box exceeds " + std::to_string(kVolMaxCells) + " cells (256^3)")
+                             : fail(ctx, NYXHIP_ERR_INVALID_ARG, "max_px is stated and max_bbox_cells is not");
+        if (derive || tx.sides) {                          // one copy of the boxes, and to derive of the offsets
+            std::vector<uint64_t> off(derive ? nr + 1 : 0);
             std::vector<uint32_t> whd(3 * nr, 1u);
-            HIP_TRY(ctx, hipMemcpyAsync(off.data(), b->px_offset, 8 * (nr + 1), hipMemcpyDeviceToHost, st));
-            if (glcm) {
+            if (derive) HIP_TRY(ctx, hipMemcpyAsync(off.data(), b->px_offset, 8 * (nr + 1), hipMemcpyDeviceToHost, st));
+            if (boxes) {
                 HIP_TRY(ctx, hipMemcpyAsync(whd.data(), b->bbox_w, 4 * nr, hipMemcpyDeviceToHost, st));
                 HIP_TRY(ctx, hipMemcpyAsync(whd.data() + nr, b->bbox_h, 4 * nr, hipMemcpyDeviceToHost, st));
                 HIP_TRY(ctx, hipMemcpyAsync(whd.data() + 2 * nr, b->bbox_d, 4 * nr, hipMemcpyDeviceToHost, st));
             }
             HIP_TRY(ctx, hipStreamSynchronize(st));
-            if (int rc = vol_scan(ctx, nr, off.data(), whd.data(), whd.data() + nr, whd.data() + 2 * nr, max_px, max_cells)) return rc;
-        } else if (glcm && (max_cells == 0 || max_cells > kVolMaxCells)) {
-            return max_cells ? fail(ctx, NYXHIP_ERR_ROI_TOO_LARGE, "volumes: a box exceeds " + std::to_string(kVolMaxCells) + " cells (256^3)")
-                             : fail(ctx, NYXHIP_ERR_INVALID_ARG, "max_px is stated and max_bbox_cells is not");
+            if (derive)
+                if (int rc = vol_scan(ctx, nr, off.data(), whd.data(), whd.data() + nr, whd.data() + 2 * nr, max_px, max_cells)) return rc;
+            if (tx.sides) sides = vol_sides(nr, whd.data(), whd.data() + nr, whd.data() + 2 * nr, max_cells ? max_cells : 1u);
         }
         nyxhip_batch3d d = *b;
-        if (!glcm) { d.x = d.y = d.z = nullptr; d.bbox_w = d.bbox_h = d.bbox_d = nullptr; }
-        if (int rc = body(d, out, ld, max_px, max_cells)) return rc;
+        if (!boxes) { d.x = d.y = d.z = nullptr; d.bbox_w = d.bbox_h = d.bbox_d = nullptr; }
+        if (int rc = body(d, out, ld, max_px, max_cells, sides)) return rc;
         HIP_TRY(ctx, hipStreamSynchronize(st));
-        return check(ctx);
+        return vol_check_status(ctx, tx);
     }
 
     // host batch: check the arrays, stage them into one device slab, run, copy the table back
     {
         const uint32_t* w = b->bbox_w; const uint32_t* h = b->bbox_h; const uint32_t* dd = b->bbox_d;
-        if (!glcm) { ones.assign(nr, 1u); w = h = dd = ones.data(); }
+        if (!boxes) { ones.assign(nr, 1u); w = h = dd = ones.data(); }
         uint32_t dpx = 0, dcells = 0;
         if (int rc = vol_scan(ctx, nr, b->px_offset, w, h, dd, dpx, dcells)) return rc;
         if (max_px == 0) { max_px = dpx; max_cells = dcells; }
-        else if (glcm && (max_cells == 0 || max_cells > kVolMaxCells)) return fail(ctx, NYXHIP_ERR_INVALID_ARG, "max_px is stated and max_bbox_cells is not (or exceeds 256^3)");
+        else if (boxes && (max_cells == 0 || max_cells > kVolMaxCells)) return fail(ctx, NYXHIP_ERR_INVALID_ARG, "max_px is stated and max_bbox_cells is not (or exceeds 256^3)");
+        if (tx.sides) sides = vol_sides(nr, w, h, dd, max_cells ? max_cells : 1u);
     }
     const uint64_t npx = b->px_offset[nr];
     const bool slide = b->slide_min != nullptr;
@@ -178,14 +229,14 @@ int vol_run(nyxhip_ctx* ctx, const nyxhip_batch3d* b, bool glcm, size_t ncol, do
     char* const base = ctx->d_stage.as<char>();
     HIP_TRY(ctx, hipMemcpyAsync(base + o_off, b->px_offset, 8 * (nr + 1), hipMemcpyHostToDevice, st));
     if (npx) {
-        if (glcm) {
+        if (boxes) {
             HIP_TRY(ctx, hipMemcpyAsync(base + o_x, b->x, 2 * npx, hipMemcpyHostToDevice, st));
             HIP_TRY(ctx, hipMemcpyAsync(base + o_y, b->y, 2 * npx, hipMemcpyHostToDevice, st));
             HIP_TRY(ctx, hipMemcpyAsync(base + o_z, b->z, 2 * npx, hipMemcpyHostToDevice, st));
         }
         HIP_TRY(ctx, hipMemcpyAsync(base + o_i, b->inten, 4 * npx, hipMemcpyHostToDevice, st));
     }
-    if (glcm) {
+    if (boxes) {
         HIP_TRY(ctx, hipMemcpyAsync(base + o_w, b->bbox_w, 4 * nr, hipMemcpyHostToDevice, st));
         HIP_TRY(ctx, hipMemcpyAsync(base + o_h, b->bbox_h, 4 * nr, hipMemcpyHostToDevice, st));
         HIP_TRY(ctx, hipMemcpyAsync(base + o_d, b->bbox_d, 4 * nr, hipMemcpyHostToDevice, st));
@@ -200,16 +251,16 @@ int vol_run(nyxhip_ctx* ctx, const nyxhip_batch3d* b, bool glcm, size_t ncol, do
     memset(&d, 0, sizeof(d));
     d.n_roi = nr; d.memory = NYXHIP_MEM_DEVICE; d.max_device_bytes = b->max_device_bytes;
     d.px_offset = (const uint64_t*)(base + o_off);
-    if (glcm) { d.x = (const uint16_t*)(base + o_x); d.y = (const uint16_t*)(base + o_y); d.z = (const uint16_t*)(base + o_z); }
+    if (boxes) { d.x = (const uint16_t*)(base + o_x); d.y = (const uint16_t*)(base + o_y); d.z = (const uint16_t*)(base + o_z); }
     d.inten = (const uint32_t*)(base + o_i);
-    if (glcm) { d.bbox_w = (const uint32_t*)(base + o_w); d.bbox_h = (const uint32_t*)(base + o_h); d.bbox_d = (const uint32_t*)(base + o_d); }
+    if (boxes) { d.bbox_w = (const uint32_t*)(base + o_w); d.bbox_h = (const uint32_t*)(base + o_h); d.bbox_d = (const uint32_t*)(base + o_d); }
     d.min_inten = (const uint32_t*)(base + o_mn); d.max_inten = (const uint32_t*)(base + o_mx);
     if (slide) { d.slide_min = (const double*)(base + o_s0); d.slide_max = (const double*)(base + o_s1); }
     double* const d_out = (double*)(base + o_out);
-    if (int rc = body(d, d_out, ncol, max_px, max_cells)) { (void)hipStreamSynchronize(st); return rc; }
+    if (int rc = body(d, d_out, ncol, max_px, max_cells, sides)) { (void)hipStreamSynchronize(st); return rc; }
     HIP_TRY(ctx, hipMemcpy2DAsync(out, ld * sizeof(double), d_out, ncol * sizeof(double), ncol * sizeof(double), nr, hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, hipStreamSynchronize(st));
-    return check(ctx);
+    return vol_check_status(ctx, tx);
 }
 
 } // namespace nyxhip
@@ -238,16 +289,11 @@ int nyxhip_vol_column_name(uint32_t vmask, const nyxhip_settings* s, int col, ch
 int nyxhip_featurize_volumes(nyxhip_ctx* ctx, const nyxhip_batch3d* b, uint32_t vmask, const nyxhip_settings* s, double* out, size_t ld)
 {
     if (!ctx) return NYXHIP_ERR_INVALID_ARG;
-    if (!b || !s || !out) return fail(ctx, NYXHIP_ERR_INVALID_ARG, "null batch / settings / out_table");
-    if (!vol_mask_ok(vmask)) return fail(ctx, NYXHIP_ERR_INVALID_ARG, "bad volume mask: NYXHIP_VFAM_INTENSITY | NYXHIP_VFAM_GLCM are the bits it has");
     const bool glcm = (vmask & NYXHIP_VFAM_GLCM) != 0, inten = (vmask & NYXHIP_VFAM_INTENSITY) != 0;
-    if (b->n_roi && (!b->px_offset || !b->inten || !b->min_inten || !b->max_inten || (glcm && (!b->x || !b->y || !b->z || !b->bbox_w || !b->bbox_h || !b->bbox_d))))
-        return fail(ctx, NYXHIP_ERR_INVALID_ARG, "batch has null array pointers (px_offset, inten, min_inten, max_inten; for the GLCM block also x, y, z, bbox_w, bbox_h, bbox_d)");
-    if ((b->slide_min == nullptr) != (b->slide_max == nullptr)) return fail(ctx, NYXHIP_ERR_INVALID_ARG, "slide_min and slide_max must both be given or both NULL");
     const size_t ncol = (size_t)vol_cols(vmask);
-    if (ld < ncol) return fail(ctx, NYXHIP_ERR_INVALID_ARG, "out_ld smaller than the column count");
-    if (b->n_roi > 0x7FFFFFFFull) return fail(ctx, NYXHIP_ERR_INVALID_ARG, "too many ROIs in one batch");
-    if (b->memory != NYXHIP_MEM_DEVICE && b->memory != NYXHIP_MEM_HOST) return fail(ctx, NYXHIP_ERR_INVALID_ARG, "bad batch->memory");
+    if (int rc = vol_entry_checks(ctx, kTexts, b, s != nullptr, out, vol_mask_ok(vmask) ? nullptr : "bad volume mask: NYXHIP_VFAM_INTENSITY | NYXHIP_VFAM_GLCM are the bits it has",
+                                  glcm, true, ncol, ld))
+        return rc;
     if (inten) {
         if (s->grey_depth == 0) return fail(ctx, NYXHIP_ERR_INVALID_ARG, "grey_depth must be non-zero (histogram bin count)");
         if ((uint32_t)abs(s->grey_depth) > kVolMaxHistBins)
@@ -256,12 +302,12 @@ int nyxhip_featurize_volumes(nyxhip_ctx* ctx, const nyxhip_batch3d* b, uint32_t 
     if (glcm) {
         if (s->glcm_offset < 1) return fail(ctx, NYXHIP_ERR_INVALID_ARG, "glcm_offset must be >= 1");
         if (!s->ibsi && (uint32_t)abs(s->glcm_grey_depth) > kVolLevelCap)
-            return fail(ctx, NYXHIP_ERR_UNSUPPORTED, "volumes: the 3-D GLCM matrix lives in LDS up to " + std::to_string(kVolLevelCap) + " levels; |glcm_grey_depth| = " +
-                                                         std::to_string(abs(s->glcm_grey_depth)) + " exceeds that cap");
+            return fail(ctx, NYXHIP_ERR_UNSUPPORTED, kTexts.cap + "; |glcm_grey_depth| = " + std::to_string(abs(s->glcm_grey_depth)) + " exceeds that cap");
     }
-    return vol_run(ctx, b, glcm, ncol, out, ld,
-                   [&](const nyxhip_batch3d& d, double* d_out, size_t d_ld, uint32_t max_px, uint32_t max_cells) { return vol_device(ctx, &d, vmask, s, d_out, d_ld, max_px, max_cells); },
-                   vol_check_status);
+    return vol_run(ctx, kTexts, b, glcm, ncol, out, ld,
+                   [&](const nyxhip_batch3d& d, double* d_out, size_t d_ld, uint32_t max_px, uint32_t max_cells, const VolSides&) {
+                       return vol_device(ctx, &d, vmask, s, d_out, d_ld, max_px, max_cells);
+                   });
 }
 
 } // extern "C"

@@ -72,87 +72,74 @@ def _refusal(names) -> str:
             "Nyxus3DDistanceZones (featureset3d.expand3d_dzones)")
 
 
-def expand3d(features: List[str]) -> Tuple[int, List[str]]:
-    """(volume mask, the requested codes in Feature3D order).  Raises ValueError for anything but the served groups and codes.  The
-    volume mask is 0 when only texture codes are asked for; their mask is tex_mask(codes)."""
+# what an expansion serves: (groups, code -> mask bit) per tier, and the Feature3D order of all its codes
+_TIERS_3D = [(GROUPS_3D, VFAM_OF)]
+_TIERS_3D_ZONES = _TIERS_3D + [(GROUPS_3D_ZONES, VZONE_OF)]
+_TIERS_3D_DZONES = _TIERS_3D_ZONES + [(GROUPS_3D_DZONES, VDZ_OF)]
+
+
+def _expand(features: List[str], tiers, order: List[str]) -> Tuple[int, List[str]]:
     want, unknown = set(), []
     for f in features:
         if not isinstance(f, str):
             raise ValueError(f"feature names must be strings, got {f!r}")
         u = f.strip().upper()
-        if u in GROUPS_3D:
-            want.update(GROUPS_3D[u])
-        elif u in VFAM_OF:
-            want.add(u)
+        for groups, table in tiers:
+            if u in groups:
+                want.update(groups[u])
+                break
+            if u in table:
+                want.add(u)
+                break
         else:
             unknown.append(f)
     if unknown:
         raise ValueError(_refusal(unknown))
     if not want:
         raise ValueError("no features requested")
-    req = [c for c in ORDER_3D if c in want]
-    mask = 0
-    for c in req:
-        mask |= VFAM_OF[c]
-    return mask, req
+    req = [c for c in order if c in want]
+    return mask_of(req, VFAM_OF), req
+
+
+def mask_of(codes: List[str], table) -> int:
+    """The bits of `table` (code -> mask bit) that serve the codes among `codes`; 0: none."""
+    m = 0
+    for c in codes:
+        m |= table.get(c, 0)
+    return m
+
+
+def expand3d(features: List[str]) -> Tuple[int, List[str]]:
+    """(volume mask, the requested codes in Feature3D order).  Raises ValueError for anything but the served groups and codes.  The
+    volume mask is 0 when only texture codes are asked for; their mask is tex_mask(codes)."""
+    return _expand(features, _TIERS_3D, ORDER_3D)
 
 
 def expand3d_zones(features: List[str]) -> Tuple[int, List[str]]:
     """expand3d with the groups *3D_GLRLM*, *3D_GLSZM* and their codes served too: (volume mask, the requested codes in Feature3D
     order).  The texture mask is tex_mask(codes), the zone mask zone_mask(codes)."""
-    rest, zones = [], set()
-    for f in features:
-        u = f.strip().upper() if isinstance(f, str) else None
-        if u in GROUPS_3D_ZONES:
-            zones.update(GROUPS_3D_ZONES[u])
-        elif u in VZONE_OF:
-            zones.add(u)
-        else:
-            rest.append(f)
-    mask, req = expand3d(rest) if rest or not zones else (0, [])
-    want = set(req) | zones
-    return mask, [c for c in ORDER_3D_ZONES if c in want]
+    return _expand(features, _TIERS_3D_ZONES, ORDER_3D_ZONES)
 
 
 def expand3d_dzones(features: List[str]) -> Tuple[int, List[str]]:
     """expand3d_zones with the group *3D_GLDZM* and its codes served too: (volume mask, the requested codes in Feature3D order).  The
     distance-zone mask is dzone_mask(codes)."""
-    rest, dz = [], set()
-    for f in features:
-        u = f.strip().upper() if isinstance(f, str) else None
-        if u in GROUPS_3D_DZONES:
-            dz.update(GROUPS_3D_DZONES[u])
-        elif u in VDZ_OF:
-            dz.add(u)
-        else:
-            rest.append(f)
-    mask, req = expand3d_zones(rest) if rest or not dz else (0, [])
-    want = set(req) | dz
-    return mask, [c for c in ORDER_3D_DZONES if c in want]
+    return _expand(features, _TIERS_3D_DZONES, ORDER_3D_DZONES)
 
 
 def dzone_mask(codes: List[str]) -> int:
     """The distance-zone mask (nyxhip_featurize_volumes_dzones) that serves the GLDZM codes among `codes`; 0: none."""
-    m = 0
-    for c in codes:
-        m |= VDZ_OF.get(c, 0)
-    return m
+    return mask_of(codes, VDZ_OF)
 
 
 def zone_mask(codes: List[str]) -> int:
     """The zone mask (nyxhip_featurize_volumes_zones) that serves the GLRLM / GLSZM codes among `codes`; 0: none."""
-    m = 0
-    for c in codes:
-        m |= VZONE_OF.get(c, 0)
-    return m
+    return mask_of(codes, VZONE_OF)
 
 
 def tex_mask(codes: List[str]) -> int:
     """The texture mask (nyxhip_featurize_volumes_tex) that serves the GLDM / NGLDM / NGTDM codes among `codes`; 0: none."""
-    m = 0
-    for c in codes:
-        m |= VTEX_OF.get(c, 0)
-    return m
+    return mask_of(codes, VTEX_OF)
 
 
 def table_column(code: str) -> str:

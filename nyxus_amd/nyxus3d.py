@@ -13,7 +13,7 @@ The file workflows are not served: NIfTI / DICOM / z-stack ingest is outside thi
 from __future__ import annotations
 
 import ctypes as C
-from typing import List, Optional
+from typing import Callable, List, NamedTuple, Optional
 
 import numpy as np
 
@@ -38,7 +38,44 @@ def clouds_from_volume(inten: np.ndarray, label: np.ndarray):
     return [{"label": int(lab[a]), "x": xx[a:b], "y": yy[a:b], "z": zz[a:b], "inten": val[a:b]} for a, b in zip(starts, ends)]
 
 
+class _Block(NamedTuple):
+    """One table of the volume path, as the classes below serve it."""
+    mask_attr: str                     # the attribute that holds the block's mask
+    table: dict                        # code -> mask bit (featureset3d)
+    names: Callable                    # (mask, settings) -> the column names of the C table
+    entry: str                         # the `Context` method: entry(batch, mask, settings[, block settings], max_device_bytes=)
+    settings_attr: Optional[str] = None
+    new_settings: Optional[Callable] = None
+    params: dict = {}                  # metaparameter key -> field of the block's settings (env_metaparams.cpp:157-239 set, :313-375 get)
+    get_only: dict = {}                # keys get_metaparam alone takes
+    positive: frozenset = frozenset()  # keys whose value must be a positive integer
+    # (key, field, mask bit, radius field or None): the grey depths that start at 0 = unbinned, for the hint of a refused call; a class
+    # whose radius is 0 reads no levels.  cap: the level cap the hint names
+    depths: tuple = ()
+    cap: int = 0
+
+
+_VOL = _Block("_mask", featureset3d.VFAM_OF, lambda m, s: _lib.vol_column_names(m, s), "volumes_host")
+# compile_feature_settings zeroes the slots (env_features.cpp:712-736)
+_TEX = _Block("_tex_mask", featureset3d.VTEX_OF, lambda m, s: _lib.voltex_column_names(m), "volumes_tex_host", "_tex_settings", lambda: _abi.VolTexSettings(0, 0, 0),
+              params={"3gldm/greydepth": "gldm_grey_depth", "3ngtdm/greydepth": "ngtdm_grey_depth", "3ngtdm/radius": "ngtdm_radius"},
+              positive=frozenset({"3ngtdm/radius"}),
+              depths=(("3gldm/greydepth", "gldm_grey_depth", _abi.VTEX_GLDM, None), ("3ngtdm/greydepth", "ngtdm_grey_depth", _abi.VTEX_NGTDM, "ngtdm_radius")),
+              cap=_abi.VOLTEX_MAX_LEVELS)
+# (the reference spells the GLSZM key "3glsz" where it reads it back)
+_ZONE = _Block("_zone_mask", featureset3d.VZONE_OF, lambda m, s: _lib.volzone_column_names(m), "volumes_zones_host", "_zone_settings", lambda: _abi.VolZoneSettings(0, 0),
+               params={"3glrlm/greydepth": "glrlm_grey_depth", "3glszm/greydepth": "glszm_grey_depth"}, get_only={"3glsz/greydepth": "glszm_grey_depth"},
+               depths=(("3glrlm/greydepth", "glrlm_grey_depth", _abi.VZONE_GLRLM, None), ("3glszm/greydepth", "glszm_grey_depth", _abi.VZONE_GLSZM, None)),
+               cap=_abi.VOLZONE_MAX_LEVELS)
+_DZONE = _Block("_dzone_mask", featureset3d.VDZ_OF, lambda m, s: _lib.voldzone_column_names(m), "volumes_dzones_host")
+
+
 class Nyxus3D:
+    _BLOCKS = (_VOL, _TEX)                       # the tables the class serves, in the order they are computed and stand side by side
+    _expand = staticmethod(featureset3d.expand3d)
+    _INGEST = ("Nyxus3D.{}: NIfTI / DICOM / z-stack ingest is not served (the TIFF reader of this package decodes first pages only); "
+               "assemble the volumes and call featurize()")
+
     def __init__(self, features: List[str], **kwargs):
         invalid = set(kwargs) - _VALID_KEYS
         if invalid:
@@ -64,9 +101,11 @@ class Nyxus3D:
         if any(kwargs.get(k, 1.0) != 1.0 for k in ("anisotropy_x", "anisotropy_y", "anisotropy_z")):
             raise ValueError("anisotropy is outside the MI355X hot path (SURVEY.md section 8)")
         self._features = list(features)
-        self._mask, self._requested = featureset3d.expand3d(self._features)
-        self._tex_mask = featureset3d.tex_mask(self._requested)
-        self._tex_settings = _abi.VolTexSettings(0, 0, 0)   # compile_feature_settings zeroes the slots (env_features.cpp:712-736)
+        _, self._requested = self._expand(self._features)
+        for blk in self._BLOCKS:
+            setattr(self, blk.mask_attr, featureset3d.mask_of(self._requested, blk.table))
+            if blk.settings_attr:
+                setattr(self, blk.settings_attr, blk.new_settings())
         # glcm_offset stays 1 and glcm_symmetric 0: the statics of the reference's 3-D GLCM class, which nothing in its Python face sets
         self._settings = _abi.default_settings(int(coarse_gray_depth), bool(kwargs.get("ibsi", False)))
         self._env = {"ram_limit": kwargs.get("ram_limit", -1)}
@@ -80,58 +119,62 @@ class Nyxus3D:
         return self._ctx
 
     def _columns(self):
-        names = (_lib.vol_column_names(self._mask, self._settings) if self._mask else []) + (_lib.voltex_column_names(self._tex_mask) if self._tex_mask else [])
+        names = []
+        for blk in self._BLOCKS:
+            mask = getattr(self, blk.mask_attr)
+            if mask:
+                names += blk.names(mask, self._settings)
         sel = [names.index(featureset3d.table_column(c)) for c in self._requested]
         return list(self._requested), sel
 
-    # env_metaparams.cpp:157-203 (set), :313-347 (get): the keys of the served classes
-    _METAPARAMS = {"3gldm/greydepth": "gldm_grey_depth", "3ngtdm/greydepth": "ngtdm_grey_depth", "3ngtdm/radius": "ngtdm_radius"}
-
-    def _metaparam_field(self, name: str) -> str:
-        if name not in self._METAPARAMS:
-            raise ValueError(f"Invalid metaparameter name {name}: the MI355X volume path serves {sorted(self._METAPARAMS)}")
-        return self._METAPARAMS[name]
+    def _metaparam(self, name: str, get: bool):
+        """(settings object, field) of a metaparameter key of the served blocks."""
+        for blk in self._BLOCKS:
+            field = blk.params.get(name) or (get and blk.get_only.get(name))
+            if field:
+                return getattr(self, blk.settings_attr), field
+        served = sorted(k for blk in self._BLOCKS for k in blk.params) + (sorted(k for blk in self._BLOCKS for k in blk.get_only) if get else [])
+        raise ValueError(f"Invalid metaparameter name {name}: the MI355X volume path serves {served}")
 
     def set_metaparam(self, paramval: str):
-        """Sets a feature-specific parameter, for example ``set_metaparam("3gldm/greydepth=-20")`` (nyxus.py:1111-1128)."""
+        """Sets a feature-specific parameter, for example ``set_metaparam("3gldm/greydepth=-20")`` (nyxus.py:1111-1128).  The grey depths
+        take any integer (negative: radiomics bins), ``3ngtdm/radius`` a positive one."""
         sides = str(paramval).split("=")
         if len(sides) != 2:
             raise ValueError(f"Invalid metaparameter value {paramval}: error: expecting <feature>/<parameter>=<value>")
         name, raw = sides[0].strip(), sides[1].strip()
-        field = self._metaparam_field(name)
+        settings, field = self._metaparam(name, get=False)
         try:
             val = int(raw)
         except ValueError:
             val = None
-        if name == "3ngtdm/radius":
-            if val is None or val <= 0:
-                raise ValueError(f'Invalid metaparameter value {paramval}: error: cannot parse value "{raw}" of 3ngtdm/radius: expecting a positive integer')
-        elif val is None:
+        if any(name in blk.positive for blk in self._BLOCKS) and (val is None or val <= 0):
+            raise ValueError(f'Invalid metaparameter value {paramval}: error: cannot parse value "{raw}" of {name}: expecting a positive integer')
+        if val is None or not -2**31 <= val < 2**31:
             raise ValueError(f'Invalid metaparameter value {paramval}: error: cannot parse value "{raw}" of {name}: expecting an integer')
-        if not -2**31 <= val < 2**31:
-            raise ValueError(f'Invalid metaparameter value {paramval}: error: cannot parse value "{raw}" of {name}: expecting an integer')
-        setattr(self._tex_settings, field, val)
+        setattr(settings, field, val)
 
     def get_metaparam(self, paramname: str) -> float:
         """The value of a feature-specific parameter, as a float like the reference's (nyxus.py:1130-1147)."""
-        return float(getattr(self._tex_settings, self._metaparam_field(str(paramname).strip())))
+        settings, field = self._metaparam(str(paramname).strip(), get=True)
+        return float(getattr(settings, field))
 
     def _tables(self, b: _abi.HostBatch3D, max_device_bytes: int) -> np.ndarray:
-        """The volume table and the texture table of a batch side by side, whichever the request needs (Feature3D order)."""
+        """The tables of the served blocks of a batch side by side, whichever the request needs (one entry each, in block order)."""
         ctx, parts = self._context(), []
-        if self._mask:
-            parts.append(ctx.volumes_host(b, self._mask, self._settings, max_device_bytes=max_device_bytes))
-        if self._tex_mask:
+        for blk in self._BLOCKS:
+            mask = getattr(self, blk.mask_attr)
+            if not mask:
+                continue
+            t = getattr(self, blk.settings_attr) if blk.settings_attr else None
             try:
-                parts.append(ctx.volumes_tex_host(b, self._tex_mask, self._settings, self._tex_settings, max_device_bytes=max_device_bytes))
+                parts.append(getattr(ctx, blk.entry)(b, mask, self._settings, *([t] if t is not None else []), max_device_bytes=max_device_bytes))
             except _lib.NyxHipError as e:
-                t = self._tex_settings
-                zero = [k for k, f, bit in (("3gldm/greydepth", t.gldm_grey_depth, _abi.VTEX_GLDM), ("3ngtdm/greydepth", t.ngtdm_grey_depth, _abi.VTEX_NGTDM))
-                        if f == 0 and self._tex_mask & bit and not (bit == _abi.VTEX_NGTDM and t.ngtdm_radius == 0)]
+                zero = [k for k, f, bit, radius in blk.depths if getattr(t, f) == 0 and mask & bit and not (radius and getattr(t, radius) == 0)]
                 if e.code == _abi.ERR_UNSUPPORTED and zero and not self._settings.ibsi:
                     raise _lib.NyxHipError(e.code, f"{e.args[0]} -- a grey depth of 0 leaves the intensities unbinned: set " +
                                            " and ".join(f'set_metaparam("{k}=<levels>")' for k in zero) +
-                                           f" with at most {_abi.VOLTEX_MAX_LEVELS} levels (negative: radiomics binning)") from e
+                                           f" with at most {blk.cap} levels (negative: radiomics binning)") from e
                 raise
         return parts[0] if len(parts) == 1 else np.hstack(parts)
 
@@ -201,12 +244,10 @@ class Nyxus3D:
         return df
 
     def featurize_directory(self, *args, **kwargs):
-        raise NotImplementedError("Nyxus3D.featurize_directory: NIfTI / DICOM / z-stack ingest is not served (the TIFF reader of this package "
-                                  "decodes first pages only); assemble the volumes and call featurize()")
+        raise NotImplementedError(self._INGEST.format("featurize_directory"))
 
     def featurize_files(self, *args, **kwargs):
-        raise NotImplementedError("Nyxus3D.featurize_files: NIfTI / DICOM / z-stack ingest is not served (the TIFF reader of this package "
-                                  "decodes first pages only); assemble the volumes and call featurize()")
+        raise NotImplementedError(self._INGEST.format("featurize_files"))
 
 
 class Nyxus3DZones(Nyxus3D):
@@ -218,74 +259,8 @@ class Nyxus3DZones(Nyxus3D):
     (no binning) as in the reference, where real intensities exceed the level cap: the error names the metaparameter to set.
     `Nyxus3D` itself keeps refusing these classes."""
 
-    def __init__(self, features: List[str], **kwargs):
-        plain, _ = featureset3d.expand3d_zones(list(features))         # raises the refusal of expand3d for anything else
-        del plain
-        zone_only = [f for f in features if isinstance(f, str) and (f.strip().upper() in featureset3d.GROUPS_3D_ZONES or f.strip().upper() in featureset3d.VZONE_OF)]
-        rest = [f for f in features if f not in zone_only]
-        super().__init__(rest if rest else ["3MEAN"], **kwargs)        # (the checks of the keyword arguments; the request is set below)
-        self._features = list(features)
-        self._mask, self._requested = featureset3d.expand3d_zones(self._features)
-        self._tex_mask = featureset3d.tex_mask(self._requested)
-        self._zone_mask = featureset3d.zone_mask(self._requested)
-        self._zone_settings = _abi.VolZoneSettings(0, 0)
-
-    def _columns(self):
-        names = ((_lib.vol_column_names(self._mask, self._settings) if self._mask else []) +
-                 (_lib.voltex_column_names(self._tex_mask) if self._tex_mask else []) +
-                 (_lib.volzone_column_names(self._zone_mask) if self._zone_mask else []))
-        sel = [names.index(featureset3d.table_column(c)) for c in self._requested]
-        return list(self._requested), sel
-
-    # env_metaparams.cpp:204-239 (set), :348-375 (get: the reference spells the GLSZM key "3glsz" there)
-    _ZONE_METAPARAMS = {"3glrlm/greydepth": "glrlm_grey_depth", "3glszm/greydepth": "glszm_grey_depth"}
-    _ZONE_GET_ONLY = {"3glsz/greydepth": "glszm_grey_depth"}
-
-    def _served(self):
-        return sorted({**self._METAPARAMS, **self._ZONE_METAPARAMS})
-
-    def set_metaparam(self, paramval: str):
-        """`Nyxus3D.set_metaparam` and the keys ``3glrlm/greydepth`` and ``3glszm/greydepth`` (any integer; negative: radiomics bins)."""
-        sides = str(paramval).split("=")
-        name = sides[0].strip()
-        if len(sides) != 2 or name in self._METAPARAMS:
-            return super().set_metaparam(paramval)
-        if name not in self._ZONE_METAPARAMS:
-            raise ValueError(f"Invalid metaparameter name {name}: the MI355X volume path serves {self._served()}")
-        raw = sides[1].strip()
-        try:
-            val = int(raw)
-        except ValueError:
-            val = None
-        if val is None or not -2**31 <= val < 2**31:
-            raise ValueError(f'Invalid metaparameter value {paramval}: error: cannot parse value "{raw}" of {name}: expecting an integer')
-        setattr(self._zone_settings, self._ZONE_METAPARAMS[name], val)
-
-    def get_metaparam(self, paramname: str) -> float:
-        name = str(paramname).strip()
-        field = self._ZONE_METAPARAMS.get(name) or self._ZONE_GET_ONLY.get(name)
-        if field:
-            return float(getattr(self._zone_settings, field))
-        if name not in self._METAPARAMS:
-            raise ValueError(f"Invalid metaparameter name {name}: the MI355X volume path serves {self._served() + sorted(self._ZONE_GET_ONLY)}")
-        return super().get_metaparam(name)
-
-    def _tables(self, b: _abi.HostBatch3D, max_device_bytes: int) -> np.ndarray:
-        """The volume table, the texture table and the zone table of a batch side by side, whichever the request needs."""
-        parts = [super()._tables(b, max_device_bytes)] if (self._mask or self._tex_mask) else []
-        if self._zone_mask:
-            try:
-                parts.append(self._context().volumes_zones_host(b, self._zone_mask, self._settings, self._zone_settings, max_device_bytes=max_device_bytes))
-            except _lib.NyxHipError as e:
-                z = self._zone_settings
-                zero = [k for k, f, bit in (("3glrlm/greydepth", z.glrlm_grey_depth, _abi.VZONE_GLRLM), ("3glszm/greydepth", z.glszm_grey_depth, _abi.VZONE_GLSZM))
-                        if f == 0 and self._zone_mask & bit]
-                if e.code == _abi.ERR_UNSUPPORTED and zero and not self._settings.ibsi:
-                    raise _lib.NyxHipError(e.code, f"{e.args[0]} -- a grey depth of 0 leaves the intensities unbinned: set " +
-                                           " and ".join(f'set_metaparam("{k}=<levels>")' for k in zero) +
-                                           f" with at most {_abi.VOLZONE_MAX_LEVELS} levels (negative: radiomics binning)") from e
-                raise
-        return parts[0] if len(parts) == 1 else np.hstack(parts)
+    _BLOCKS = (_VOL, _TEX, _ZONE)
+    _expand = staticmethod(featureset3d.expand3d_zones)
 
 
 class Nyxus3DDistanceZones(Nyxus3DZones):
@@ -296,34 +271,6 @@ class Nyxus3DDistanceZones(Nyxus3DZones):
     `Nyxus3DZones` does.  A cell of level 0 forms no zone and is always a border, in every binning mode.
     `Nyxus3D` and `Nyxus3DZones` keep refusing the class; `*3D_ALL*` stays refused because the 3-D shape class is not served."""
 
-    def __init__(self, features: List[str], **kwargs):
-        featureset3d.expand3d_dzones(list(features))                   # raises the refusal of expand3d for anything else
-        dz_only = [f for f in features if isinstance(f, str) and (f.strip().upper() in featureset3d.GROUPS_3D_DZONES or f.strip().upper() in featureset3d.VDZ_OF)]
-        rest = [f for f in features if f not in dz_only]
-        super().__init__(rest if rest else ["3MEAN"], **kwargs)        # (the checks of the keyword arguments; the request is set below)
-        self._features = list(features)
-        self._mask, self._requested = featureset3d.expand3d_dzones(self._features)
-        self._tex_mask = featureset3d.tex_mask(self._requested)
-        self._zone_mask = featureset3d.zone_mask(self._requested)
-        self._dzone_mask = featureset3d.dzone_mask(self._requested)
-
-    def _columns(self):
-        names = ((_lib.vol_column_names(self._mask, self._settings) if self._mask else []) +
-                 (_lib.voltex_column_names(self._tex_mask) if self._tex_mask else []) +
-                 (_lib.volzone_column_names(self._zone_mask) if self._zone_mask else []) +
-                 (_lib.voldzone_column_names(self._dzone_mask) if self._dzone_mask else []))
-        sel = [names.index(featureset3d.table_column(c)) for c in self._requested]
-        return list(self._requested), sel
-
-    def _tables(self, b: _abi.HostBatch3D, max_device_bytes: int) -> np.ndarray:
-        """The tables `Nyxus3DZones` assembles and the distance-zone table side by side, whichever the request needs."""
-        parts = [super()._tables(b, max_device_bytes)] if (self._mask or self._tex_mask or self._zone_mask) else []
-        if self._dzone_mask:
-            parts.append(self._context().volumes_dzones_host(b, self._dzone_mask, self._settings, max_device_bytes=max_device_bytes))
-        return parts[0] if len(parts) == 1 else np.hstack(parts)
-
-    def featurize_directory(self, *args, **kwargs):
-        raise NotImplementedError("Nyxus3DDistanceZones.featurize_directory: NIfTI / DICOM / z-stack ingest is not served; assemble the volumes and call featurize()")
-
-    def featurize_files(self, *args, **kwargs):
-        raise NotImplementedError("Nyxus3DDistanceZones.featurize_files: NIfTI / DICOM / z-stack ingest is not served; assemble the volumes and call featurize()")
+    _BLOCKS = (_VOL, _TEX, _ZONE, _DZONE)
+    _expand = staticmethod(featureset3d.expand3d_dzones)
+    _INGEST = "Nyxus3DDistanceZones.{}: NIfTI / DICOM / z-stack ingest is not served; assemble the volumes and call featurize()"

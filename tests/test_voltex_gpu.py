@@ -196,6 +196,21 @@ def test_a_row_has_the_same_bits_however_it_is_asked_for(ctx):
     assert same(device_rows(ctx, mixed_b, s, t, max_device_bytes=per_roi), mixed).all()
 
 
+def test_ngtdm_at_radius_0_alone_takes_no_workspace_and_keeps_its_bits(ctx):
+    """NGTDM alone at radius 0 has neither a box nor a table: no workspace, so no budget is read and a budget of one byte serves it.
+    Its five columns carry the bits they have in the table of the whole mask: NaN without a zone, soft_nan below two levels."""
+    s, t = voltex_cases.settings("r0")
+    for bname in ("wide", "boxes"):                                                      # the smallest batch of more than one ROI; rows of both kinds
+        b = voltex_cases.batch(bname)
+        want = ctx.volumes_tex_host(b, ALL, s, t)[:, G + N:]
+        for budget in (0, 1):
+            assert same(ctx.volumes_tex_host(b, _abi.VTEX_NGTDM, s, t, max_device_bytes=budget), want).all(), (bname, budget)
+            assert same(device_rows(ctx, b, s, t, tmask=_abi.VTEX_NGTDM, max_device_bytes=budget), want).all(), (bname, budget)
+        with pytest.raises(_lib.NyxHipError, match="max_device_bytes"):                  # (the whole mask does take a workspace)
+            ctx.volumes_tex_host(b, ALL, s, t, max_device_bytes=1)
+    assert np.isnan(want).any() and (want == s.soft_nan).any()
+
+
 def test_nyxus3d_featurize_against_the_recording():
     api = json.load(open(os.path.join(HERE, "golden", "voltex", "api_expected.json")))
     I, M = voltex_cases.api_volumes()
