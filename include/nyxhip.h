@@ -669,6 +669,41 @@ int nyxhip_voldzone_column_name(uint32_t dzone_mask, int col, char* buf, size_t 
 int nyxhip_featurize_volumes_dzones(nyxhip_ctx* ctx, const nyxhip_batch3d* batch, uint32_t dzone_mask, const nyxhip_settings* s,
                                     double* out_table, size_t out_ld);
 
+/* ---- volumes (3-D): shape ------------------------------------------------------
+ * The shape class of the reference's Feature3D enum, behind an entry and a mask space of its own (the other four masks keep their bits):
+ *   NYXHIP_VSHAPE_MORPHOLOGY   D3_SurfaceFeature (features/3d_surface.cpp:322-516): 14 codes 3AREA .. 3FLATNESS in enum order.
+ * The reference's single-ROI mode (:331-352) is not served.
+ *   3VOXEL_VOLUME     voxels x (4/3 pi / 8) / 0.5236; every voxel of the cloud counts, intensity 0 included.
+ *   3AREA             the exposed voxel faces: per voxel the 6-neighbours that are not in the cloud.  An integer, exact.
+ *   3AREA_2_VOLUME, 3COMPACTNESS1, 3COMPACTNESS2, 3SPHERICAL_DISPROPORTION, 3SPHERICITY   the reference's closed forms of those two.
+ *   3MAJOR_AXIS_LEN, 3MINOR_AXIS_LEN, 3LEAST_AXIS_LEN   4 sqrt(lambda_i) of the sample covariance (divisor N - 1) of the voxel
+ *                     coordinates, eigenvalues descending; 3ELONGATION, 3FLATNESS: sqrt(l1 / l0), sqrt(l2 / l0).  The covariance comes
+ *                     from exact integer sums, the eigenvalues from cyclic Jacobi in fp64.  A negative eigenvalue, or one below 2^-40 of
+ *                     the largest, is 0 (a rank-deficient cloud: a line, a plane); one voxel, or l0 == 0, gives 0 in all five columns.
+ *   3VOLUME_CONVEXHULL = 3MESH_VOLUME
+ * THE RULING.  The hull columns hold the EXACT volume of the convex hull of the centres of the voxels of non-zero intensity, and 0
+ * where those span fewer than three dimensions.  The reference hulls the per-plane contours of the same voxels with a float
+ * quickhull (eps 1e-10f) that is not exact: it equals this value wherever its hull is correct and is off by up to percents on round
+ * or sparse clouds.  6 V is accumulated as an integer with exact integer predicates: a row has the same bits
+ * whatever shares its call, chunk, memory kind or batch order.
+ * SETTINGS READ.  nyxhip_settings: soft_nan, written in all 14 columns of an ROI without voxels.  No grey depth, no level cap.
+ * LIMITS.  Those of the volume entries (side, NYXHIP_VOL_MAX_CELLS cells and voxels, stated extrema, max_device_bytes, voxels outside
+ * their box).  The workspace holds, per ROI of a chunk, a byte per cell of the largest box and 200 to 340 bytes per (z, y) row of the
+ * largest box sides of the batch (row extremes, chains, hull candidates, visited edges, edge stack).  No kernel waits for another
+ * workgroup; every loop of the hull has a bound derived from its candidate count, and one that reaches it makes the call return
+ * NYXHIP_ERR_INTERNAL. */
+enum {
+    NYXHIP_VSHAPE_MORPHOLOGY = 1u << 0
+};
+
+/* Column catalogue of a shape mask: the count (< 0: invalid mask, 0 or any foreign bit) and the name of column `col`. */
+int nyxhip_vshape_n_columns(uint32_t shape_mask);
+int nyxhip_vshape_column_name(uint32_t shape_mask, int col, char* buf, size_t buf_len);
+
+/* One row of 14 values per ROI.  Host batch: host table.  Device batch: device table.  Synchronous. */
+int nyxhip_featurize_volumes_shape(nyxhip_ctx* ctx, const nyxhip_batch3d* batch, uint32_t shape_mask, const nyxhip_settings* s,
+                                   double* out_table, size_t out_ld);
+
 /* ---- measurement hooks -------------------------------------------------------
  * Average device time (ms) per featurize call since the last nyxhip_timing_reset(),
  * measured with hipEvents recorded on the launch stream around EVERYTHING the call

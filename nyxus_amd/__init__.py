@@ -8,6 +8,6 @@ C ABI of ``include/nyxhip.h``.
 from . import _abi  # noqa: F401
 from .nyxus import Nyxus  # noqa: F401
 from .imq import ImageQuality  # noqa: F401
-from .nyxus3d import Nyxus3D, Nyxus3DZones, Nyxus3DDistanceZones  # noqa: F401
+from .nyxus3d import Nyxus3D, Nyxus3DZones, Nyxus3DDistanceZones, Nyxus3DShape  # noqa: F401
 
 __version__ = "0.1.0"

@@ -318,6 +318,10 @@ VDZ_GLDZM = 1 << 0           # D3_GLDZM_feature: 3GLDZM_SDE .. 3GLDZM_ZDE
 VOLDZONE_COLS = 18
 VOLDZONE_MAX_LEVELS = 128    # NYXHIP_VOLDZONE_MAX_LEVELS
 
+# the shape mask of nyxhip_featurize_volumes_shape (a mask space of its own); the entry reads soft_nan of nyxhip_settings only
+VSHAPE_MORPHOLOGY = 1 << 0   # D3_SurfaceFeature: 3AREA .. 3FLATNESS
+VOLSHAPE_COLS = 14
+
 
 class Batch3D(C.Structure):
     """``nyxhip_batch3d`` (include/nyxhip.h)."""

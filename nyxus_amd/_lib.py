@@ -36,6 +36,7 @@ ABI_SYMBOLS = [
     "nyxhip_voltex_n_columns", "nyxhip_voltex_column_name", "nyxhip_featurize_volumes_tex",
     "nyxhip_volzone_n_columns", "nyxhip_volzone_column_name", "nyxhip_featurize_volumes_zones",
     "nyxhip_voldzone_n_columns", "nyxhip_voldzone_column_name", "nyxhip_featurize_volumes_dzones",
+    "nyxhip_vshape_n_columns", "nyxhip_vshape_column_name", "nyxhip_featurize_volumes_shape",
 ]
 
 
@@ -171,6 +172,13 @@ def load() -> C.CDLL:
         lib.nyxhip_voldzone_column_name.restype = C.c_int
         lib.nyxhip_featurize_volumes_dzones.argtypes = [C.c_void_p, P(_abi.Batch3D), C.c_uint32, P(_abi.Settings), C.c_void_p, C.c_size_t]
         lib.nyxhip_featurize_volumes_dzones.restype = C.c_int
+    if hasattr(lib, "nyxhip_featurize_volumes_shape"):
+        lib.nyxhip_vshape_n_columns.argtypes = [C.c_uint32]
+        lib.nyxhip_vshape_n_columns.restype = C.c_int
+        lib.nyxhip_vshape_column_name.argtypes = [C.c_uint32, C.c_int, C.c_char_p, C.c_size_t]
+        lib.nyxhip_vshape_column_name.restype = C.c_int
+        lib.nyxhip_featurize_volumes_shape.argtypes = [C.c_void_p, P(_abi.Batch3D), C.c_uint32, P(_abi.Settings), C.c_void_p, C.c_size_t]
+        lib.nyxhip_featurize_volumes_shape.restype = C.c_int
     if hasattr(lib, "nyxhip_featurize_slides"):  # (absent from older builds of the ABI selected through NYXHIP_LIB for A/B runs)
         lib.nyxhip_featurize_slides.argtypes = [C.c_void_p, P(_abi.Tiles), C.c_uint32, P(_abi.Settings), C.c_void_p, C.c_size_t]
         lib.nyxhip_featurize_slides.restype = C.c_int
@@ -234,6 +242,11 @@ def volzone_column_names(zmask: int) -> List[str]:
 def voldzone_column_names(dmask: int = _abi.VDZ_GLDZM) -> List[str]:
     """The columns of nyxhip_featurize_volumes_dzones for a distance-zone mask (_abi.VDZ_*)."""
     return _catalogue(load().nyxhip_voldzone_n_columns, load().nyxhip_voldzone_column_name, (dmask,), "volume distance-zone column", "volume distance-zone mask")
+
+
+def volshape_column_names(smask: int = _abi.VSHAPE_MORPHOLOGY) -> List[str]:
+    """The columns of nyxhip_featurize_volumes_shape for a shape mask (_abi.VSHAPE_*)."""
+    return _catalogue(load().nyxhip_vshape_n_columns, load().nyxhip_vshape_column_name, (smask,), "volume shape column", "volume shape mask")
 
 
 # Contexts still open at interpreter exit are destroyed here, while the HIP runtime is certainly alive (Python's atexit handlers
@@ -424,6 +437,15 @@ class Context:
     def volumes_dzones_device(self, cb: _abi.Batch3D, dmask: int, s: _abi.Settings, out_ptr: int, ld: int):
         """Device pointers in ``cb`` and a device table; synchronous (nyxhip_featurize_volumes_dzones)."""
         self._check(self._lib.nyxhip_featurize_volumes_dzones(self._h, C.byref(cb), dmask, C.byref(s), C.c_void_p(out_ptr), ld))
+
+    def volumes_shape_host(self, batch: _abi.HostBatch3D, smask: int, s: _abi.Settings, stated: bool = False, max_device_bytes: int = 0) -> np.ndarray:
+        """The shape table [n_roi x 14] of a host batch (nyxhip_featurize_volumes_shape); NaN / inf are left in place."""
+        return self._volume_table(self._lib.nyxhip_featurize_volumes_shape, self._lib.nyxhip_vshape_n_columns, "volume shape mask", batch, smask, (),
+                                  (C.byref(s),), stated, max_device_bytes)
+
+    def volumes_shape_device(self, cb: _abi.Batch3D, smask: int, s: _abi.Settings, out_ptr: int, ld: int):
+        """Device pointers in ``cb`` and a device table; synchronous (nyxhip_featurize_volumes_shape)."""
+        self._check(self._lib.nyxhip_featurize_volumes_shape(self._h, C.byref(cb), smask, C.byref(s), C.c_void_p(out_ptr), ld))
 
     def imq_host(self, batch: _abi.HostBatch, s: _abi.Settings) -> np.ndarray:
         """The image-quality columns [n_roi x 4] of a host batch (nyxhip_imq_batch); NaN / inf are left in place."""

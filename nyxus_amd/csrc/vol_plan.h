@@ -10,6 +10,7 @@
 #include "roi_voltex.h"
 #include "roi_volzone.h"
 #include "roi_voldzone.h"
+#include "roi_volshape.h"
 
 namespace nyxhip {
 
@@ -125,6 +126,27 @@ inline size_t voldzone_layout(VoldzoneArgs& a, const nyxhip_settings* s, uint32_
     a.cell_stride = al256(4 * (size_t)a.max_cells) >> 2;
     a.dist_stride = al256(2 * (size_t)a.max_cells) >> 1;
     return a.box_stride + 4 * a.tab_stride + 2 * a.dist_stride + 8 * a.cell_stride;
+}
+
+// nyxhip_featurize_volumes_shape: the head, the row extremes and the occupancy box (zeroed per chunk), then the chains, the candidates,
+// the visited set and the edge stack of the hull, all sized by the (z, y) rows of the largest box sides of the batch
+struct VolshapeLayout { size_t per_roi, zeroed; };
+inline VolshapeLayout volshape_layout(VolshapeArgs& a, uint32_t max_px, uint32_t max_cells, const VolSides& sides)
+{
+    a.max_cells = max_cells ? max_cells : 1u; a.max_px = max_px ? max_px : 1u;
+    for (int ax = 0; ax < 3; ax++) a.side_max[ax] = sides.side_max[ax];
+    const uint64_t rows = (uint64_t)a.side_max[1] * a.side_max[2];
+    a.rows_max = (uint32_t)(rows < a.max_cells ? rows : a.max_cells);
+    a.row_stride = al256(4 * (size_t)a.rows_max) >> 2;
+    a.occ_stride = al256(a.max_cells);
+    a.cand_stride = 2 * a.row_stride;
+    a.lds_cand = (uint32_t)(a.cand_stride < kVshLdsCand ? a.cand_stride : kVshLdsCand);
+    a.visited_stride = vsh_table(a.cand_stride);
+    a.stack_stride = 3 * a.cand_stride;
+    VolshapeLayout L;
+    L.zeroed = 8 * (size_t)kVshHead + 8 * a.row_stride + a.occ_stride;
+    L.per_roi = L.zeroed + 8 * a.row_stride + 8 * (a.cand_stride + a.visited_stride + a.stack_stride);
+    return L;
 }
 
 } // namespace nyxhip

@@ -6,7 +6,8 @@ volume mask of nyxhip_featurize_volumes, the 3-D GLDM, NGLDM and NGTDM classes b
 `featureset.expand`, its groups and the `Nyxus` class know nothing of them.  Two more classes, the 3-D GLRLM and GLSZM, are served by the
 zone mask of nyxhip_featurize_volumes_zones through `expand3d_zones` and `Nyxus3DZones`; `expand3d` and `Nyxus3D` refuse them.  The last
 texture class, the 3-D GLDZM, is served by the distance-zone mask of nyxhip_featurize_volumes_dzones through `expand3d_dzones` and
-`Nyxus3DDistanceZones`; the other expansions and classes refuse it.
+`Nyxus3DDistanceZones`; the other expansions and classes refuse it.  The shape class (14 codes, `*3D_ALL_MORPHOLOGY*`) is served by the
+shape mask of nyxhip_featurize_volumes_shape through `expand3d_shape` and `Nyxus3DShape`, and with it `*3D_ALL*`.
 """
 from __future__ import annotations
 
@@ -61,6 +62,15 @@ GLDZM_3D = ["3GLDZM_" + n for n in ("SDE", "LDE", "LGLZE", "HGLZE", "SDLGLE", "S
 GROUPS_3D_DZONES = {"*3D_GLDZM*": GLDZM_3D}
 ORDER_3D_DZONES = INTENSITY_3D + GLCM_3D + GLDM_3D + GLDZM_3D + NGLDM_3D + NGTDM_3D + GLSZM_3D + GLRLM_3D
 VDZ_OF = {c: _abi.VDZ_GLDZM for c in GLDZM_3D}
+# Feature3D order (featureset.h:678-693, names featureset.cpp:712-725): in the enum the shape block stands directly behind the intensity
+# block.  Served by Nyxus3DShape / expand3d_shape only (the shape mask of nyxhip_featurize_volumes_shape); the other expansions refuse
+# it.  *3D_ALL* is the union of what the five entries serve, in enum order: the enum's neighbour and moments groups are compiled out of
+# the reference (#if 0) and single codes of theirs do not exist.
+SHAPE_3D = ["3" + n for n in ("AREA", "AREA_2_VOLUME", "COMPACTNESS1", "COMPACTNESS2", "MESH_VOLUME", "SPHERICAL_DISPROPORTION", "SPHERICITY", "VOLUME_CONVEXHULL",
+                              "VOXEL_VOLUME", "MAJOR_AXIS_LEN", "MINOR_AXIS_LEN", "LEAST_AXIS_LEN", "ELONGATION", "FLATNESS")]
+ORDER_3D_SHAPE = INTENSITY_3D + SHAPE_3D + GLCM_3D + GLDM_3D + GLDZM_3D + NGLDM_3D + NGTDM_3D + GLSZM_3D + GLRLM_3D
+GROUPS_3D_SHAPE = {"*3D_ALL_MORPHOLOGY*": SHAPE_3D, "*3D_ALL*": ORDER_3D_SHAPE}
+VSHAPE_OF = {c: _abi.VSHAPE_MORPHOLOGY for c in SHAPE_3D}
 VFAM_OF = {**{c: _abi.VFAM_INTENSITY for c in INTENSITY_3D}, **{c: _abi.VFAM_GLCM for c in GLCM_3D}, **{c: 0 for c in VTEX_OF}}
 
 
@@ -76,6 +86,7 @@ def _refusal(names) -> str:
 _TIERS_3D = [(GROUPS_3D, VFAM_OF)]
 _TIERS_3D_ZONES = _TIERS_3D + [(GROUPS_3D_ZONES, VZONE_OF)]
 _TIERS_3D_DZONES = _TIERS_3D_ZONES + [(GROUPS_3D_DZONES, VDZ_OF)]
+_TIERS_3D_SHAPE = _TIERS_3D_DZONES + [(GROUPS_3D_SHAPE, VSHAPE_OF)]
 
 
 def _expand(features: List[str], tiers, order: List[str]) -> Tuple[int, List[str]]:
@@ -125,6 +136,17 @@ def expand3d_dzones(features: List[str]) -> Tuple[int, List[str]]:
     """expand3d_zones with the group *3D_GLDZM* and its codes served too: (volume mask, the requested codes in Feature3D order).  The
     distance-zone mask is dzone_mask(codes)."""
     return _expand(features, _TIERS_3D_DZONES, ORDER_3D_DZONES)
+
+
+def expand3d_shape(features: List[str]) -> Tuple[int, List[str]]:
+    """expand3d_dzones with the groups *3D_ALL_MORPHOLOGY*, *3D_ALL* and the 14 shape codes served too: (volume mask, the requested codes in
+    Feature3D order).  The shape mask is shape_mask(codes)."""
+    return _expand(features, _TIERS_3D_SHAPE, ORDER_3D_SHAPE)
+
+
+def shape_mask(codes: List[str]) -> int:
+    """The shape mask (nyxhip_featurize_volumes_shape) that serves the shape codes among `codes`; 0: none."""
+    return mask_of(codes, VSHAPE_OF)
 
 
 def dzone_mask(codes: List[str]) -> int:

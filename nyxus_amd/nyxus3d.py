@@ -8,7 +8,8 @@ Five classes of the `Feature3D` enum are served: the voxel-intensity class (`*3D
 The file workflows are not served: NIfTI / DICOM / z-stack ingest is outside this package.
 
 `Nyxus3DZones` (below) is `Nyxus3D` with the 3-D GLRLM and GLSZM classes served too (nyxhip_featurize_volumes_zones), and
-`Nyxus3DDistanceZones` is `Nyxus3DZones` with the 3-D GLDZM class served too (nyxhip_featurize_volumes_dzones).
+`Nyxus3DDistanceZones` is `Nyxus3DZones` with the 3-D GLDZM class served too (nyxhip_featurize_volumes_dzones), and `Nyxus3DShape` is
+`Nyxus3DDistanceZones` with the 3-D shape class and `*3D_ALL*` served too (nyxhip_featurize_volumes_shape).
 """
 from __future__ import annotations
 
@@ -68,6 +69,7 @@ _ZONE = _Block("_zone_mask", featureset3d.VZONE_OF, lambda m, s: _lib.volzone_co
                depths=(("3glrlm/greydepth", "glrlm_grey_depth", _abi.VZONE_GLRLM, None), ("3glszm/greydepth", "glszm_grey_depth", _abi.VZONE_GLSZM, None)),
                cap=_abi.VOLZONE_MAX_LEVELS)
 _DZONE = _Block("_dzone_mask", featureset3d.VDZ_OF, lambda m, s: _lib.voldzone_column_names(m), "volumes_dzones_host")
+_SHAPE = _Block("_shape_mask", featureset3d.VSHAPE_OF, lambda m, s: _lib.volshape_column_names(m), "volumes_shape_host")
 
 
 class Nyxus3D:
@@ -274,3 +276,17 @@ class Nyxus3DDistanceZones(Nyxus3DZones):
     _BLOCKS = (_VOL, _TEX, _ZONE, _DZONE)
     _expand = staticmethod(featureset3d.expand3d_dzones)
     _INGEST = "Nyxus3DDistanceZones.{}: NIfTI / DICOM / z-stack ingest is not served; assemble the volumes and call featurize()"
+
+
+class Nyxus3DShape(Nyxus3DDistanceZones):
+    """`Nyxus3DDistanceZones` with the 3-D shape class served too (nyxhip_featurize_volumes_shape): the group `*3D_ALL_MORPHOLOGY*` (14
+    codes, `3AREA` .. `3FLATNESS`) and its codes, beside everything `Nyxus3DDistanceZones` takes, and with them `*3D_ALL*`: every code the
+    five entries serve, in Feature3D order (the enum's neighbour and moments groups are compiled out of the reference).  Same
+    constructor, same `featurize`, same metaparameters; the DataFrame columns of the class stand directly behind the intensity block and in
+    front of the GLCM's, as in the enum.  `3VOLUME_CONVEXHULL` and `3MESH_VOLUME` hold the exact volume of the convex hull of the centres of
+    the voxels of non-zero intensity; the reference's single-ROI mode of the class is not served.
+    `Nyxus3D`, `Nyxus3DZones` and `Nyxus3DDistanceZones` keep refusing the class and `*3D_ALL*`."""
+
+    _BLOCKS = (_VOL, _TEX, _ZONE, _DZONE, _SHAPE)
+    _expand = staticmethod(featureset3d.expand3d_shape)
+    _INGEST = "Nyxus3DShape.{}: NIfTI / DICOM / z-stack ingest is not served; assemble the volumes and call featurize()"
