@@ -733,6 +733,13 @@ int nyxhip_timing_get(nyxhip_ctx* ctx, double* avg_kernel_ms, uint64_t* n_launch
  * ROI, so a call is split by ROI size.  Returns the number of bytes the full text needs (excluding the NUL), or < 0. */
 int nyxhip_launch_report(nyxhip_ctx* ctx, char* buf, size_t buf_len);
 
+/* Diagnostic: the per-ROI words that every featurize call clears at its start, as the LAST call on this context left them -- waits for
+ * the context's stream, then counts the non-zero entries among the first n_roi of each table: *n_orders the matrix orders that the
+ * feature kernels stated for the GLCM feature launch (ROIs whose co-occurrence counts were exported), *n_flags the pending flags of the
+ * deferred intensity closing.  A flag is raised by the feature kernel and cleared by the closing launch that consumes it, so after a
+ * completed call *n_flags is 0; a table the last call's mask had no use for counts 0.  Either pointer may be NULL. */
+int nyxhip_debug_roi_words(nyxhip_ctx* ctx, uint64_t n_roi, uint64_t* n_orders, uint64_t* n_flags);
+
 #ifdef __cplusplus
 }
 #endif

@@ -27,7 +27,7 @@ ABI_SYMBOLS = [
     "nyxhip_featurize_batch_async", "nyxhip_sync", "nyxhip_finalize_table", "nyxhip_featurize_tile", "nyxhip_featurize_tiles",
     "nyxhip_timing_enable", "nyxhip_timing_reset", "nyxhip_timing_get",
     "nyxhip_featurize_tiles_v2", "nyxhip_fetch_result", "nyxhip_featurize_tiles_sharded", "nyxhip_fetch_result_sharded",
-    "nyxhip_launch_report", "nyxhip_featurize_batch_at", "nyxhip_featurize_batch_async_at",
+    "nyxhip_launch_report", "nyxhip_debug_roi_words", "nyxhip_featurize_batch_at", "nyxhip_featurize_batch_async_at",
     "nyxhip_neighbor_column_name", "nyxhip_neighbors_batch", "nyxhip_neighbors_tiles",
     "nyxhip_ih_column_name", "nyxhip_ih_batch", "nyxhip_ih_tiles",
     "nyxhip_featurize_slides",
@@ -185,6 +185,9 @@ def load() -> C.CDLL:
     if hasattr(lib, "nyxhip_launch_report"):     # (absent from older builds of the ABI selected through NYXHIP_LIB for A/B runs)
         lib.nyxhip_launch_report.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
         lib.nyxhip_launch_report.restype = C.c_int
+    if hasattr(lib, "nyxhip_debug_roi_words"):   # (absent from older builds of the ABI selected through NYXHIP_LIB for A/B runs)
+        lib.nyxhip_debug_roi_words.argtypes = [C.c_void_p, C.c_uint64, P(C.c_uint64), P(C.c_uint64)]
+        lib.nyxhip_debug_roi_words.restype = C.c_int
     _lib = lib
     return lib
 
@@ -618,6 +621,13 @@ class Context:
 
     def timing_reset(self):
         self._check(self._lib.nyxhip_timing_reset(self._h))
+
+    def roi_words(self, n_roi: int):
+        """(matrix orders stated, closing flags pending) among the first n_roi entries of the per-call tables as the last call left
+        them; waits for the stream (nyxhip_debug_roi_words)."""
+        a, b = C.c_uint64(0), C.c_uint64(0)
+        self._check(self._lib.nyxhip_debug_roi_words(self._h, n_roi, C.byref(a), C.byref(b)))
+        return int(a.value), int(b.value)
 
     def launch_report(self):
         """The size classes of the last featurize_batch call as launched (list of dicts; nyxhip_launch_report)."""

@@ -87,6 +87,14 @@ __device__ __forceinline__ uint32_t bin_pixel(uint32_t x, uint32_t mn, uint32_t 
     return x;
 }
 
+// ... the same with the matlab quotient (double)greybin_info / ((double)mx - 0.) already divided out by the caller (greybin_info > 0 only)
+__device__ __forceinline__ uint32_t bin_pixel(uint32_t x, uint32_t mn, uint32_t mx, int greybin_info, double matlab_slope)
+{
+    if (greybin_info > 0)
+        return bin_matlab(x, matlab_slope, greybin_info);
+    return bin_pixel(x, mn, mx, greybin_info);
+}
+
 // helpers/helpers.h:337-345 to_grayscale (NaN -> 0 as the x86-64 reference binary does)
 __device__ __forceinline__ uint32_t to_grayscale(uint32_t i, uint32_t min_i, uint32_t i_range, uint32_t n_levels)
 {

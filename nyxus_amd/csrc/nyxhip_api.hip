@@ -241,6 +241,27 @@ int nyxhip_timing_get(nyxhip_ctx* ctx, double* avg_kernel_ms, uint64_t* n_launch
     return NYXHIP_OK;
 }
 
+int nyxhip_debug_roi_words(nyxhip_ctx* ctx, uint64_t n_roi, uint64_t* n_orders, uint64_t* n_flags)
+{
+    if (!ctx) return NYXHIP_ERR_INVALID_ARG;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream()));
+    std::vector<uint32_t> h(n_roi);
+    auto count = [&](const uint32_t* d, uint64_t* out) -> int {
+        if (!out) return NYXHIP_OK;
+        *out = 0;
+        if (!d || n_roi == 0) return NYXHIP_OK;
+        // (the table of the last call holds at least its n_roi entries; a larger n_roi is the caller's error)
+        if ((size_t)((const char*)d - ctx->d_roi_words.as<char>()) + 4ull * n_roi > ctx->d_roi_words.bytes)
+            return fail(ctx, NYXHIP_ERR_INVALID_ARG, "n_roi exceeds the per-ROI tables of the last call");
+        HIP_TRY(ctx, hipMemcpy(h.data(), d, 4ull * n_roi, hipMemcpyDeviceToHost));
+        for (uint32_t v : h) *out += v != 0;
+        return NYXHIP_OK;
+    };
+    if (int rc = count(ctx->glcm_ng, n_orders)) return rc;
+    return count(ctx->close_flag, n_flags);
+}
+
 int nyxhip_launch_report(nyxhip_ctx* ctx, char* buf, size_t buf_len)
 {
     if (!ctx) return -NYXHIP_ERR_INVALID_ARG;

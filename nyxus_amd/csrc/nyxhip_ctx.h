@@ -151,10 +151,15 @@ struct nyxhip_ctx {
     DevBuf d_stage;
     // split GLCM: exported co-occurrence counts + matrix orders (grow-only)
     DevBuf d_glcm_ws;
-    DevBuf d_glcm_ng;                // [n_roi] matrix order of every ROI whose counts were exported in the CURRENT call (0: none) -- cleared per call
-    // deferred intensity closing (RoiArgs::close_rec / close_flag): per-ROI records and pending flags (grow-only; the flags cleared per call)
+    // Per-ROI words that every call clears, in ONE allocation and one hipMemsetAsync (launch_device_all): [n_roi] matrix order of every
+    // ROI whose counts were exported in the CURRENT call (0: none; RoiArgs::glcm_ng) | [n_roi] pending flags of the deferred intensity
+    // closing (RoiArgs::close_flag).  The second table starts at the first 256-byte boundary behind the first; the pointers of the
+    // current call are glcm_ng / close_flag below (NULL: the call's mask has no use for the table).
+    DevBuf d_roi_words;
+    uint32_t* glcm_ng = nullptr;
+    uint32_t* close_flag = nullptr;
+    // deferred intensity closing (RoiArgs::close_rec): per-ROI records (grow-only)
     DevBuf d_close_rec;
-    DevBuf d_close_flag;
     DevBuf d_logtab;                // moments: log(sqrt(d) + 0.001) per integer squared distance (roi_moments.hip)
     uint32_t logtab_n = 0;
     // contour + moments workspace (grow-only): contour points, contour lengths, per-pixel log distances

@@ -363,7 +363,7 @@ int build_args(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t mask, const nyxh
         a.n_hist = abs(s->grey_depth);
         if ((mask1 & NYXHIP_FAM_INTENSITY) && cap == 0) {      // (sized and cleared once per call by launch_device_all)
             a.close_rec = ctx->d_close_rec.as<double>();
-            a.close_flag = ctx->d_close_flag.as<uint32_t>();
+            a.close_flag = ctx->close_flag;
         }
         // small matrices (order <= 16, all angles in one pass, matlab or IBSI level values 1..Ng): the features run as their
         // own launch with one wave per ROI (glcm_features_kernel); the counts travel through a context-owned workspace
@@ -371,12 +371,12 @@ int build_args(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t mask, const nyxh
         if ((mask1 & NYXHIP_FAM_GLCM) && cap == 0 && gi >= 0 && a.L.ng_cap <= 16 && (int)a.L.app >= s->glcm_n_angles && s->glcm_n_angles > 0) {
             const size_t stride = (size_t)s->glcm_n_angles * a.L.ng_cap * a.L.ng_cap;
             const size_t need = 4 * stride * (size_t)b->n_roi + 256;
-            if (ctx->d_glcm_ws.reserve(need, nullptr) != hipSuccess || !ctx->d_glcm_ng) {   // (d_glcm_ng: sized and cleared once per call by launch_device_all)
+            if (ctx->d_glcm_ws.reserve(need, nullptr) != hipSuccess || !ctx->glcm_ng) {   // (glcm_ng: sized and cleared once per call by launch_device_all)
                 why = "out of device memory for the GLCM count workspace";
                 return NYXHIP_ERR_HIP;
             }
             {
-                a.glcm_ng = ctx->d_glcm_ng.as<uint32_t>();
+                a.glcm_ng = ctx->glcm_ng;
                 a.glcm_ws = ctx->d_glcm_ws.as<uint32_t>();
                 a.glcm_ws_stride = (uint32_t)stride;
             }
@@ -1100,22 +1100,29 @@ int launch_device_all(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t mask, con
         }
         ~LaneJoin() { join(); }
     } lane_join{ctx, st};
-    if (mask & NYXHIP_FAM_GLCM) {
-        // matrix orders of the split GLCM launches (RoiArgs::glcm_ng).  A table of its own: the count workspace may be re-allocated
-        // between the launch groups of a call.
-        const size_t need = 4ull * n_roi + 256;
-        HIP_TRY(ctx, ctx->d_glcm_ng.reserve(need, st, need + need / 4));
-        // 0 = "nothing to derive": an ROI whose feature kernel returns before it states its matrix order (error paths) must not leave
-        // glcm_features_kernel a stale order from an earlier call
-        HIP_TRY(ctx, hipMemsetAsync(ctx->d_glcm_ng.p, 0, 4ull * n_roi, st));
+    ctx->glcm_ng = ctx->close_flag = nullptr;
+    if (mask & (NYXHIP_FAM_GLCM | NYXHIP_FAM_INTENSITY)) {
+        // Matrix orders of the split GLCM launches (RoiArgs::glcm_ng; not part of the count workspace, which may be re-allocated between
+        // the launch groups of a call) and pending flags of the deferred intensity closing (RoiArgs::close_flag), side by side in one
+        // allocation: a call that asks for both clears both with one fill.
+        //   order 0 = "nothing to derive": an ROI whose feature kernel returns before it states its matrix order (error paths) must not
+        //   leave glcm_features_kernel a stale order from an earlier call;
+        //   intensity_close_kernel clears the flags it consumes; the clearing here covers a call that ended between a feature launch
+        //   and its closing launch.
+        const bool want_ng = (mask & NYXHIP_FAM_GLCM) != 0, want_flag = (mask & NYXHIP_FAM_INTENSITY) != 0;
+        const size_t table = (4ull * n_roi + 255) & ~(size_t)255;            // the second table's offset
+        const size_t need = 2 * table + 256;
+        HIP_TRY(ctx, ctx->d_roi_words.reserve(need, st, need + need / 4));
+        uint32_t* const base = ctx->d_roi_words.as<uint32_t>();
+        if (want_ng) ctx->glcm_ng = base;
+        if (want_flag) ctx->close_flag = base + table / 4;
+        if (want_ng && want_flag) HIP_TRY(ctx, hipMemsetAsync(base, 0, table + 4ull * n_roi, st));
+        else HIP_TRY(ctx, hipMemsetAsync(want_ng ? ctx->glcm_ng : ctx->close_flag, 0, 4ull * n_roi, st));
     }
     if (mask & NYXHIP_FAM_INTENSITY) {
-        // records and pending flags of the deferred intensity closing (RoiArgs::close_rec).  intensity_close_kernel clears the flags it
-        // consumes; the clearing here covers a call that ended between a feature launch and its closing launch
-        const size_t need_rec = 8ull * kCloseRec * n_roi + 256, need_flag = 4ull * n_roi + 256;
+        // records of the deferred intensity closing (RoiArgs::close_rec)
+        const size_t need_rec = 8ull * kCloseRec * n_roi + 256;
         HIP_TRY(ctx, ctx->d_close_rec.reserve(need_rec, st, need_rec + need_rec / 4));
-        HIP_TRY(ctx, ctx->d_close_flag.reserve(need_flag, st, need_flag + need_flag / 4));
-        HIP_TRY(ctx, hipMemsetAsync(ctx->d_close_flag.p, 0, 4ull * n_roi, st));
     }
     auto timed_class = [&](int cls, uint32_t count, const Extrema& E, const uint32_t* lp, uint32_t grid, uint32_t class_mask = 0, uint32_t group_sel = 0xF,
                            const ClassTotals* tot = nullptr) -> int {

@@ -41,7 +41,7 @@ namespace nyxhip {
 
 
 // slots of the block-wide scalar array s_stat
-enum { S_MEAN = 0, S_P10, S_P90, S_MEDIAN, S_MODE, S_NG };
+enum { S_MEAN = 0, S_P10, S_P90, S_MEDIAN, S_MODE, S_NG, S_SLOPE };   // (slots 8, 9 and 12 .. 14 are the engine's prefix offsets)
 
 // Lanes of one wave exchange data through LDS without a workgroup barrier: LDS
 // instructions of a wave execute in issue order, so only the compiler has to be
@@ -972,7 +972,16 @@ __device__ __forceinline__ void roi_features_body(const RoiArgs& A, const uint64
     const int greyInfo = A.ibsi ? 0 : A.grey_depth;
     if (FAST) __builtin_assume(greyInfo > 0 && greyInfo <= 16);
     if (G16) __builtin_assume(greyInfo > 16 && greyInfo <= 64);     // G16: matlab binning, 17..64 levels, 16-bit matrices (see the GLCM block)
-    const double mslope = greyInfo > 0 ? (double)greyInfo / ((double)vmax - 0.) : 0.0;
+    // The binning slope is a fact of the ROI.  SLOPE1 (the compact co-occurrence builds, FAM 1 and 3 on LDS): wave 0 divides it out
+    // once, in front of the phase-0 barrier, and publishes it in s_stat[S_SLOPE]; every wave reads it behind the barrier, and the
+    // degenerate guard takes its two levels from the same quotient.  Every other build forms it per wave, as before.
+#ifdef NYX_NO_SLOPE_ONCE
+    constexpr bool SLOPE1 = false;
+#else
+    constexpr bool SLOPE1 = FAST && !GS && !G16;
+#endif
+    double mslope = 0.0;
+    if constexpr (!SLOPE1) mslope = greyInfo > 0 ? (double)greyInfo / ((double)vmax - 0.) : 0.0;
 
     // ---- phase 0: clear LDS state; the output row is written in place (zeros first: features that are skipped stay 0; every
     //      later store to the row is separated from these by a workgroup barrier) ----------------------------------------
@@ -982,6 +991,14 @@ __device__ __forceinline__ void roi_features_body(const RoiArgs& A, const uint64
         uint32_t* d32 = (uint32_t*)s_dense;       // region is 16-byte aligned and padded
         // (8-bit planes: 64 more zero bytes behind the last row -- the "row below" of the last row and the cell every lane beyond the
         //  box reads in the co-occurrence sweep; the cell that takes out-of-box coordinates lies behind them)
+#ifndef NYX_NO_WIDE_CLEAR
+        // (the compact co-occurrence builds only, as SLOPE1: the generic tiers and the 17..64-level builds keep the 4-byte clear)
+        if constexpr (FAST && D8 && !GS && !G16) { // 16-byte stores: make_layout pads the plane's region to 16 bytes behind dense_cap + 64 + 8
+            uint4* const d128 = (uint4*)s_dense;  // bytes, and area <= dense_cap here, so the last store ends inside the region
+            for (uint32_t i = tid; i < (area + 64 + 15) / 16; i += BS)
+                d128[i] = make_uint4(0, 0, 0, 0);
+        } else
+#endif
         for (uint32_t i = tid; i < (D8 ? (area + 64 + 3) / 4 : (area + 1) / 2); i += BS)
             d32[i] = 0;
         if (greyInfo < 0)
@@ -999,9 +1016,17 @@ __device__ __forceinline__ void roi_features_body(const RoiArgs& A, const uint64
                 s_val[i] = 0xFFFFFFFFu;
         }
     }
+    if constexpr (SLOPE1) {
+        if (wave == 0) {                          // (the zeroing lane of the slot writes the slope itself: one store per slot, no order to keep)
+            const double slope0 = (double)greyInfo / ((double)vmax - 0.);
+            if (tid < 16)
+                s_stat[tid] = tid == S_SLOPE ? slope0 : 0.0;
+        }
+    } else
     if (tid < 16)
         s_stat[tid] = 0.0;
     grp_sync<GS, NW>();
+    if constexpr (SLOPE1) mslope = s_stat[S_SLOPE];
     if constexpr (HOIST) __builtin_amdgcn_sched_barrier(0);   // (the hoisted trip is widened BEHIND the barrier: see `first`)
 
     STAMP(0);
@@ -1376,6 +1401,11 @@ __device__ __forceinline__ void roi_features_body(const RoiArgs& A, const uint64
     //   phase 0 (1) | window loader only: its trips + 1, or 1 (the generic loader) | sums (2) | sweep (1, not for a blank ROI) |
     //   engine (2) | serial only: chain (1, not for a blank ROI) | unless the ROI is degenerate (a blank one is; its waves all
     //   leave in front of what follows): serial only: the zeroing pair (2); the co-occurrence sweep's end (1).
+    // Exchange through s_stat: slots 0 .. 5 (S_MEAN .. S_NG) between the sums' two barriers and later, 8 .. 9 and 12 .. 14 the engine's
+    // prefix offsets (12 .. 13 the generic window loader's s_hits, in front of the sums).  S_SLOPE (slot 6, SLOPE1 builds): the binning
+    // slope, written in front of the phase-0 barrier BY THE LANE THAT ZEROES THE SLOT (wave 0, tid 6 stores the quotient where the
+    // fifteen others store 0.0: one store per slot, so no order between a zero and the value has to be kept), read by every wave
+    // behind that barrier and again by the degenerate guard; nothing writes the slot afterwards.
     // Boundaries (STAMP / NYX_EXIT_AT) of these builds: 0 LDS cleared | 1 load pass | 2 mean published | 3 central-sum sweep, (overlapped:
     // matrices zeroed,) counting engine | 4 (a blank ROI's sums closed) | 5, 6 nothing | 7 chain (wave 0), n-bin bounds and entropy
     // (wave 1); serial: and their barrier | 8, 9 nothing | 10 serial: matrices zeroed between two barriers | 11 co-occurrence
@@ -1392,6 +1422,19 @@ __device__ __forceinline__ void roi_features_body(const RoiArgs& A, const uint64
     constexpr bool OVL_DEFER = OVL && DEFER_P;     // (the builds that leave the closing math to intensity_close_kernel: the record's flag)
 #endif
     const bool ovl = OVL && B->L.overlap != 0;
+    // GLCM degenerate guard of the FAST builds (glcm.cpp:27-95, on GLCM_GREYDEPTH): the ROI's extrema fall into one level.  Where the
+    // guard's depth is the sweep's (a fact of the launch, decided on the scalar unit) its two binnings take the published slope --
+    // the same quotient bin_pixel would divide out twice more; else bin_pixel as it stands.
+    [[maybe_unused]] auto guard_flat = [&]() -> bool {
+        const int gd = B->glcm_grey_depth;
+        if (SLOPE1 && gd == greyInfo) {
+            // (read from the slot again, not taken from `mslope`: that value is dead behind the load pass, and kept alive up to here it
+            //  costs the 61-VGPR builds a register pair.  FAM 1: one lane reads; FAM 3: every thread does, one uniform LDS read per ROI)
+            const double slope = s_stat[S_SLOPE];
+            return bin_pixel(vmin, vmin, vmax, gd, slope) == bin_pixel(vmax, vmin, vmax, gd, slope);
+        }
+        return bin_pixel(vmin, vmin, vmax, gd) == bin_pixel(vmax, vmin, vmax, gd);
+    };
 
     // ---- the pieces of the <= 16-level co-occurrence block (FAST, see the GLCM section) as callables: the overlapped launches zero the
     // matrices from inside the intensity block.  (The sweep keeps ONE call site, in the GLCM block: a second inlined copy behind the
@@ -1598,7 +1641,7 @@ __device__ __forceinline__ void roi_features_body(const RoiArgs& A, const uint64
             const double mean = tot / dn;              // the one IEEE division; every other thread reads the mean after the barrier
             s_stat[S_MEAN] = mean;
             if (FAST)                                  // GLCM degenerate guard (glcm.cpp:27-95, on GLCM_GREYDEPTH): two binnings, once per ROI
-                s_stat[S_NG] = bin_pixel(vmin, vmin, vmax, B->glcm_grey_depth) == bin_pixel(vmax, vmin, vmax, B->glcm_grey_depth) ? 1.0 : 0.0;
+                s_stat[S_NG] = guard_flat() ? 1.0 : 0.0;
             if (defer) {
                 rec[CR_TOT] = tot;
                 rec[CR_TOTSQ] = totsq;
@@ -2189,7 +2232,7 @@ __device__ __forceinline__ void roi_features_body(const RoiArgs& A, const uint64
         const int na = G.na, Ng = G.Ng, NG1 = G.NG1, NN = G.NN, cells = G.cells;
         const bool dpp = G.dpp;
         // (the guard of glcm.cpp:27-95 on GLCM_GREYDEPTH: taken beside the mean when the intensity block runs, here when it does not)
-        const bool degenerate = FAM == 3 ? bin_pixel(vmin, vmin, vmax, B->glcm_grey_depth) == bin_pixel(vmax, vmin, vmax, B->glcm_grey_depth) : s_stat[S_NG] != 0.0;
+        const bool degenerate = FAM == 3 ? guard_flat() : s_stat[S_NG] != 0.0;
         if (tid == 0)
             B->glcm_ng[roi] = degenerate ? 0u : (uint32_t)Ng;
         // (overlapped builds: wave 0 has filled the ROI's record -- sums beside the mean, central sums behind the sweep, robust scalars in
