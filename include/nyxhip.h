@@ -704,6 +704,68 @@ int nyxhip_vshape_column_name(uint32_t shape_mask, int col, char* buf, size_t bu
 int nyxhip_featurize_volumes_shape(nyxhip_ctx* ctx, const nyxhip_batch3d* batch, uint32_t shape_mask, const nyxhip_settings* s,
                                    double* out_table, size_t out_ld);
 
+/* ---- 2-D morphology: basic morphology, contour, convex hull, extrema -------------------
+ * Four classes of the reference's 2-D shape block (featureset.h:46-60, :71-82, :136-143), 41 columns:
+ *   NYXHIP_MORPH_BASIC    BasicMorphologyFeatures (features/basic_morphology.cpp:19-92): AREA_PIXELS_COUNT, AREA_UM2, CENTROID_X,
+ *                         CENTROID_Y, WEIGHTED_CENTROID_Y, WEIGHTED_CENTROID_X, MASS_DISPLACEMENT, COMPACTNESS, BBOX_YMIN, BBOX_XMIN,
+ *                         BBOX_HEIGHT, BBOX_WIDTH, DIAMETER_EQUAL_AREA, EXTENT, ASPECT_RATIO
+ *   NYXHIP_MORPH_CONTOUR  ContourFeature (features/contour.cpp:935-1021): PERIMETER, DIAMETER_EQUAL_PERIMETER, EDGE_MEAN_INTENSITY,
+ *                         EDGE_STDDEV_INTENSITY, EDGE_MAX_INTENSITY, EDGE_MIN_INTENSITY, EDGE_INTEGRATED_INTENSITY
+ *   NYXHIP_MORPH_HULL     ConvexHullFeature (features/convex_hull_nontriv.cpp:53-66): CIRCULARITY, CONVEX_HULL_AREA, SOLIDITY.  It reads
+ *                         the perimeter, so the contour chain runs whether or not NYXHIP_MORPH_CONTOUR is set.
+ *   NYXHIP_MORPH_EXTREMA  ExtremaFeature (features/extrema.cpp:15-74): EXTREMA_P1_X, EXTREMA_P1_Y .. EXTREMA_P8_X, EXTREMA_P8_Y
+ * The codes lie inside the shape block, where every bit of the family mask is spoken for, so the classes have a mask space, entries
+ * and an output table [n_roi x nyxhip_morph_n_columns(mask)] of their own, like the neighbor class; nyxhip_n_columns /
+ * nyxhip_column_name do not know them.  The columns of a mask stand in enum order, which is the order above.
+ *
+ * POSITION.  BBOX_XMIN / BBOX_YMIN, CENTROID_*, WEIGHTED_CENTROID_* and the sixteen extrema columns are image coordinates: the
+ * origin plus the coordinate inside the box.  MASS_DISPLACEMENT and COMPACTNESS are formed from those rounded centroids, as the
+ * reference forms them, so their last bits move with the origin (by a few ulp of the coordinate).  Every other column reads
+ * coordinate differences only and has the same bits wherever the ROI lies.  The boxes of a batch are tight (bbox_w - 1 and
+ * bbox_h - 1 occur as coordinates), as everywhere.  A pixel outside its box is never stored: NYXHIP_ERR_INVALID_ARG.
+ * AREA_UM2 is 0: the class writes it only when the XY resolution setting is positive, and the reference's feature settings
+ * (env_features.cpp:712-736) never carry one, so its API always reports the member's initial 0.
+ * No ROI is skipped for flat intensities (has_bad_data() is false in this version of the reference, roi_cache.cpp:43-47).
+ * SUMS.  sum x, sum y, sum x I, sum y I and sum I are exact integers on the device (sum x I as two 64-bit sums over the halves of
+ * the intensity); each is converted once and divided once.  That is the reference's sequential fp64 sum bit for bit while that sum
+ * stays below 2^53, and the correctly rounded exact value beyond.  The weighted centroids are 0 when sum I = 0.  MASS_DISPLACEMENT is
+ * sqrt(dx * dx + dy * dy), unfused.  COMPACTNESS is the standard deviation (n - 1; 0 for n <= 2, moments.h:38) of the pixel-to-centroid
+ * distances divided by n: a centred second pass where the reference updates on line, so it agrees to rounding.
+ * PERIMETER has the reference's bits (terms added one after the other in its order); 0 without a contour, like the five EDGE_*
+ * columns.  EDGE_* run over the merged contour, every point once per time it stands there, with the cloud's intensity at the point:
+ * MIN, MAX and INTEGRATED_INTENSITY are integers, MEAN is the integer sum divided by the count, STDDEV is sqrt(M2 / (count - 1)) from
+ * a centred second pass (0 for count <= 2); MEAN and STDDEV agree with the reference's on-line update to rounding.
+ * CONVEX_HULL_AREA = |shoelace| / 2 + (sum over hull edges of gcd(|dx|, |dy|)) / 2 + 1 over the reference's monotone-chain hull, formed
+ * as one integer and converted once: exact.  Fewer than two pixels: an empty hull, area 1.  SOLIDITY = n / area.  CIRCULARITY =
+ * sqrt(4 pi n / (p * p)) in IEEE operations: +inf where the perimeter is 0 -- left raw like every other table (nyxhip_finalize_table).
+ * EXTREMA.  P1 / P2: the top row's leftmost / rightmost pixel; P3 / P4: the right column's top / bottom pixel; P5 / P6: the bottom
+ * row's rightmost / leftmost pixel; P7 / P8: the left column's bottom / top pixel.
+ * An empty ROI has zeros.  settings->soft_nan is the only field of the settings that is read (by nyxhip_finalize_table, not here).
+ * LIMITS.  Those of the batch type.  A contour point outside its box makes the call return NYXHIP_ERR_INTERNAL. */
+enum {
+    NYXHIP_MORPH_BASIC = 1u << 0,     /* 15 columns */
+    NYXHIP_MORPH_CONTOUR = 1u << 1,   /*  7 */
+    NYXHIP_MORPH_HULL = 1u << 2,      /*  3: CIRCULARITY, CONVEX_HULL_AREA, SOLIDITY */
+    NYXHIP_MORPH_EXTREMA = 1u << 3,   /* 16 */
+    NYXHIP_MORPH_ALL = 0xFu           /* any other bit: NYXHIP_ERR_INVALID_ARG */
+};
+
+/* Column catalogue of a morphology mask: the count (< 0: invalid mask, 0 or any foreign bit) and the name of column `col`. */
+int nyxhip_morph_n_columns(uint32_t morph_mask);
+int nyxhip_morph_column_name(uint32_t morph_mask, int col, char* buf, size_t buf_len);
+
+/* A batch of ROIs, host or device memory like nyxhip_neighbors_batch (a host batch is staged into one slab; out_table lives where the
+ * batch lives).  origin_x / origin_y as in nyxhip_featurize_batch_at: both NULL (every origin (0, 0)) or both given, in batch->memory.
+ * The extrema hints of a device batch are taken when all are stated and derived otherwise.  Reads px_offset, x, y, inten, bbox_w, bbox_h.
+ * An empty batch is NYXHIP_OK.  Synchronous. */
+int nyxhip_morph_batch(nyxhip_ctx* ctx, const nyxhip_batch* batch, const uint32_t* origin_x, const uint32_t* origin_y,
+                       uint32_t morph_mask, const nyxhip_settings* s, double* out_table, size_t out_ld);
+/* The tile path (label scan, ROI assembly, chunks under max_device_bytes) with these classes as the reducer: the origins are the
+ * boxes' places inside their tile; rows in the (tile, label) order of nyxhip_featurize_tiles_v2, outputs as there. */
+int nyxhip_morph_tiles(nyxhip_ctx* ctx, const nyxhip_tiles* tiles, uint32_t morph_mask, const nyxhip_settings* s,
+                       uint32_t* out_labels, uint32_t* out_tile_index, uint64_t max_rows,
+                       double* out_table, size_t out_ld, uint64_t* n_roi_out);
+
 /* ---- measurement hooks -------------------------------------------------------
  * Average device time (ms) per featurize call since the last nyxhip_timing_reset(),
  * measured with hipEvents recorded on the launch stream around EVERYTHING the call

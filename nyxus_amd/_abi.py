@@ -64,6 +64,10 @@ NEIGHBOR_COLS = 9            # NYXHIP_NEIGHBOR_COLS: the table of nyxhip_neighbo
 IH_COLS = 46                 # NYXHIP_IH_COLS: the table of nyxhip_ih_batch / _tiles (no family bit: every bit of the mask is spoken for)
 IMQ_COLS = 4          # NYXHIP_IMQ_COLS: FOCUS_SCORE, LOCAL_FOCUS_SCORE, MAX_SATURATION, MIN_SATURATION
 MAX_GABOR_FILTERS = 16
+# NYXHIP_MORPH_*: the mask space of nyxhip_morph_batch / _tiles (no family bits: every bit of the family mask is spoken for)
+MORPH_BASIC, MORPH_CONTOUR, MORPH_HULL, MORPH_EXTREMA = 1 << 0, 1 << 1, 1 << 2, 1 << 3
+MORPH_ALL = 0xF
+MORPH_COLS = {MORPH_BASIC: 15, MORPH_CONTOUR: 7, MORPH_HULL: 3, MORPH_EXTREMA: 16}
 
 
 class Settings(C.Structure):

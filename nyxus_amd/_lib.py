@@ -37,6 +37,7 @@ ABI_SYMBOLS = [
     "nyxhip_volzone_n_columns", "nyxhip_volzone_column_name", "nyxhip_featurize_volumes_zones",
     "nyxhip_voldzone_n_columns", "nyxhip_voldzone_column_name", "nyxhip_featurize_volumes_dzones",
     "nyxhip_vshape_n_columns", "nyxhip_vshape_column_name", "nyxhip_featurize_volumes_shape",
+    "nyxhip_morph_n_columns", "nyxhip_morph_column_name", "nyxhip_morph_batch", "nyxhip_morph_tiles",
 ]
 
 
@@ -179,6 +180,16 @@ def load() -> C.CDLL:
         lib.nyxhip_vshape_column_name.restype = C.c_int
         lib.nyxhip_featurize_volumes_shape.argtypes = [C.c_void_p, P(_abi.Batch3D), C.c_uint32, P(_abi.Settings), C.c_void_p, C.c_size_t]
         lib.nyxhip_featurize_volumes_shape.restype = C.c_int
+    if hasattr(lib, "nyxhip_morph_batch"):       # (absent from older builds of the ABI selected through NYXHIP_LIB for A/B runs)
+        lib.nyxhip_morph_n_columns.argtypes = [C.c_uint32]
+        lib.nyxhip_morph_n_columns.restype = C.c_int
+        lib.nyxhip_morph_column_name.argtypes = [C.c_uint32, C.c_int, C.c_char_p, C.c_size_t]
+        lib.nyxhip_morph_column_name.restype = C.c_int
+        lib.nyxhip_morph_batch.argtypes = [C.c_void_p, P(_abi.Batch), C.c_void_p, C.c_void_p, C.c_uint32, P(_abi.Settings), C.c_void_p, C.c_size_t]
+        lib.nyxhip_morph_batch.restype = C.c_int
+        lib.nyxhip_morph_tiles.argtypes = [C.c_void_p, P(_abi.Tiles), C.c_uint32, P(_abi.Settings), C.c_void_p, C.c_void_p, C.c_uint64,
+                                           C.c_void_p, C.c_size_t, P(C.c_uint64)]
+        lib.nyxhip_morph_tiles.restype = C.c_int
     if hasattr(lib, "nyxhip_featurize_slides"):  # (absent from older builds of the ABI selected through NYXHIP_LIB for A/B runs)
         lib.nyxhip_featurize_slides.argtypes = [C.c_void_p, P(_abi.Tiles), C.c_uint32, P(_abi.Settings), C.c_void_p, C.c_size_t]
         lib.nyxhip_featurize_slides.restype = C.c_int
@@ -250,6 +261,11 @@ def voldzone_column_names(dmask: int = _abi.VDZ_GLDZM) -> List[str]:
 def volshape_column_names(smask: int = _abi.VSHAPE_MORPHOLOGY) -> List[str]:
     """The columns of nyxhip_featurize_volumes_shape for a shape mask (_abi.VSHAPE_*)."""
     return _catalogue(load().nyxhip_vshape_n_columns, load().nyxhip_vshape_column_name, (smask,), "volume shape column", "volume shape mask")
+
+
+def morph_column_names(mmask: int = _abi.MORPH_ALL) -> List[str]:
+    """The columns of nyxhip_morph_batch / _tiles for a morphology mask (_abi.MORPH_*), enum order."""
+    return _catalogue(load().nyxhip_morph_n_columns, load().nyxhip_morph_column_name, (mmask,), "morphology column", "morphology mask")
 
 
 # Contexts still open at interpreter exit are destroyed here, while the HIP runtime is certainly alive (Python's atexit handlers
@@ -354,6 +370,52 @@ class Context:
         t.max_device_bytes = int(max_device_bytes)
         n = C.c_uint64(0)
         self._check(self._lib.nyxhip_neighbors_tiles(self._h, C.byref(t), int(distance), C.byref(s), None, None, 0, None, 0, C.byref(n)))
+        labels = np.zeros(n.value, np.uint32); tiles = np.zeros(n.value, np.uint32); table = np.empty((n.value, ncol), np.float64)
+        self._check(self._lib.nyxhip_fetch_result(self._h, labels.ctypes.data, tiles.ctypes.data, table.ctypes.data, ncol))
+        return tiles, labels, table
+
+    def morph_host(self, batch: _abi.HostBatch, mmask: int, s: _abi.Settings) -> np.ndarray:
+        """The columns of morphology mask `mmask` (_abi.MORPH_*) of a host batch (nyxhip_morph_batch); NaN / inf are left in place.
+        batch.origin_x / origin_y: the boxes' places in their image (None: (0, 0))."""
+        ncol = self._lib.nyxhip_morph_n_columns(mmask)
+        if ncol < 0:
+            raise NyxHipError(1, f"bad morphology mask {mmask:#x}")
+        if batch.origin_unrepresentable:
+            raise ValueError("the morphology classes need the ROIs' origins, and this batch's lie below 0 or beyond 32 bits")
+        out = np.empty((batch.n_roi, ncol), np.float64)
+        cb = batch.c_struct()
+        self._check(self._lib.nyxhip_morph_batch(
+            self._h, C.byref(cb), batch.origin_x.ctypes.data if batch.origin_x is not None else None,
+            batch.origin_y.ctypes.data if batch.origin_y is not None else None, mmask, C.byref(s), out.ctypes.data, ncol))
+        return out
+
+    def morph_device(self, cb: _abi.Batch, origin_x_ptr: Optional[int], origin_y_ptr: Optional[int], mmask: int, s: _abi.Settings, out_ptr: int, ld: int):
+        """Device pointers in ``cb`` (px_offset, x, y, inten, bbox_w, bbox_h), device origins (or None) and a device table; synchronous
+        (nyxhip_morph_batch)."""
+        self._check(self._lib.nyxhip_morph_batch(self._h, C.byref(cb), C.c_void_p(origin_x_ptr), C.c_void_p(origin_y_ptr), mmask, C.byref(s),
+                                                 C.c_void_p(out_ptr), ld))
+
+    def morph_tiles_host(self, inten: np.ndarray, label: np.ndarray, mmask: int, s: _abi.Settings, max_device_bytes: int = 0):
+        """The columns of morphology mask `mmask` of a stack [n_tiles, H, W] of host tiles, one image per tile (nyxhip_morph_tiles).
+        Returns (tile_index, labels, table) in the (tile, label) row order of featurize_tiles_host."""
+        if inten.shape != label.shape or inten.ndim != 3:
+            raise ValueError("stacks must be 3-D arrays [n_tiles, H, W] of the same shape")
+        ncol = self._lib.nyxhip_morph_n_columns(mmask)
+        if ncol < 0:
+            raise NyxHipError(1, f"bad morphology mask {mmask:#x}")
+        dt = {np.dtype(np.uint8): _abi.U8, np.dtype(np.uint16): _abi.U16, np.dtype(np.uint32): _abi.U32}
+        inten = np.ascontiguousarray(inten if inten.dtype in dt else inten.astype(np.uint32))
+        label = np.ascontiguousarray(label if label.dtype in dt else label.astype(np.uint32))
+        nt, h, w = inten.shape
+        if nt == 0:
+            return np.zeros(0, np.uint32), np.zeros(0, np.uint32), np.zeros((0, ncol))
+        t = _abi.Tiles()
+        t.inten = inten.ctypes.data; t.label = label.ctypes.data
+        t.inten_dtype = dt[inten.dtype]; t.label_dtype = dt[label.dtype]
+        t.width = w; t.height = h; t.n_tiles = nt; t.memory = _abi.MEM_HOST; t.slide_mode = _abi.SLIDE_MONTAGE
+        t.max_device_bytes = int(max_device_bytes)
+        n = C.c_uint64(0)
+        self._check(self._lib.nyxhip_morph_tiles(self._h, C.byref(t), mmask, C.byref(s), None, None, 0, None, 0, C.byref(n)))
         labels = np.zeros(n.value, np.uint32); tiles = np.zeros(n.value, np.uint32); table = np.empty((n.value, ncol), np.float64)
         self._check(self._lib.nyxhip_fetch_result(self._h, labels.ctypes.data, tiles.ctypes.data, table.ctypes.data, ncol))
         return tiles, labels, table

@@ -9,6 +9,7 @@
 //   nyxhip_neighbors.hip the neighbor entries: column names, the launches over a device-resident batch, nyxhip_neighbors_batch
 //   nyxhip_ih.hip        the intensity-histogram entries: column names, the launches over a device-resident batch, nyxhip_ih_batch
 //   nyxhip_imq.hip       the image-quality entries: column names, the launches over a device-resident batch, nyxhip_imq_batch / _slides
+//   nyxhip_morph.hip     the 2-D morphology entries: column catalogue of a morphology mask, the launches over a device-resident batch, nyxhip_morph_batch
 //   nyxhip_vol.hip       the volume entries: column catalogue of the volume mask, chunks under the budget, nyxhip_featurize_volumes
 #pragma once
 #include <hip/hip_runtime.h>
@@ -33,6 +34,7 @@
 #include "roi_erosion.h"
 #include "roi_circle.h"
 #include "roi_neighbors.h"
+#include "roi_morph.h"
 #include "roi_ih.h"
 #include "roi_imq.h"
 #include "roi_vol.h"
@@ -177,6 +179,9 @@ struct nyxhip_ctx {
     // neighbor entries (roi_neighbors.hip): geometry table + candidate counts and offsets | candidate lists, minima, flags
     DevBuf d_nb_geo;
     DevBuf d_nb_cand;
+    // morphology entries (roi_morph.hip): derived batch extrema | the boxes beyond the LDS column table / intensity plane and their workspace
+    DevBuf d_morph_ext;
+    DeferredBufs d_morph;
     const uint32_t* origin_x_next = nullptr;   // set by nyxhip_featurize_batch[_async]_at and the tile path for their next launch_device call:
     const uint32_t* origin_y_next = nullptr;   // device arrays [n_roi] of the ROIs' box origins (NULL: (0, 0))
     // grow-only workspaces of the fused tile path: scan tables + rows | clouds | two staging slots for host tiles
@@ -312,9 +317,16 @@ int ih_device(nyxhip_ctx* ctx, const nyxhip_batch* b, const nyxhip_settings* s, 
 int imq_device(nyxhip_ctx* ctx, const nyxhip_batch* b, const nyxhip_settings* s, double* d_out, size_t ld, uint32_t max_area);
 int imq_check_status(nyxhip_ctx* ctx);                                 // check_status with this class's reading of NYXHIP_ERR_UNSUPPORTED
 extern const char* const kImqWidthMessage;
+// nyxhip_morph.hip: the columns of morphology mask `morph` of a device-resident batch -> d_out [n_roi x ld] (enqueued on the context's stream; the
+// contour chain and the boxes beyond the LDS carve cost a read-back each).  d_ox / d_oy: device arrays of the box origins (NULL: (0, 0)).
+// max_px / max_area / max_side: the batch extrema (any 0: derived on the device).
+int morph_device(nyxhip_ctx* ctx, const nyxhip_batch* b, const uint32_t* d_ox, const uint32_t* d_oy, uint32_t morph, const nyxhip_settings* s,
+                 double* d_out, size_t ld, uint32_t max_px, uint32_t max_area, uint32_t max_side);
 // the tile path's reducers besides the family kernels (the neighbor_distance slot of tiles_run / tiles_chunk): > 0 the neighbor class at that
-// distance, kTilesReducerIh the intensity-histogram class, kTilesReducerImq the image-quality classes
+// distance, kTilesReducerIh the intensity-histogram class, kTilesReducerImq the image-quality classes, kTilesReducerMorph the 2-D morphology
+// classes (their mask travels in the family_mask slot)
 constexpr int32_t kTilesReducerIh = -1;
 constexpr int32_t kTilesReducerImq = -2;
+constexpr int32_t kTilesReducerMorph = -3;
 
 } // namespace nyxhip
