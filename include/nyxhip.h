@@ -766,6 +766,43 @@ int nyxhip_morph_tiles(nyxhip_ctx* ctx, const nyxhip_tiles* tiles, uint32_t morp
                        uint32_t* out_labels, uint32_t* out_tile_index, uint64_t max_rows,
                        double* out_table, size_t out_ld, uint64_t* n_roi_out);
 
+/* ---- 2-D morphology: hexagonality and polygonality ---------------------------------------
+ * HexagonalityPolygonalityFeature (features/hexagonality_polygonality.cpp:14-217, featureset.h:146-148): POLYGONALITY_AVE,
+ * HEXAGONALITY_AVE, HEXAGONALITY_STDDEV -- the three codes that complete ConvexHullFeature::featureset (convex_hull.h:12-20) and with
+ * it the group *ALL_MORPHOLOGY*.  A closing formula over six numbers of the ROI: the pixel count (aux_area), NUM_NEIGHBORS at
+ * pixel_distance, PERIMETER, CONVEX_HULL_AREA, STAT_FERET_DIAM_MIN and STAT_FERET_DIAM_MAX.  Because it reads the neighbor count it
+ * relates the ROIs of ONE image, so it has entries and an output table [n_roi x NYXHIP_HEXPOLY_COLS] of its own with the arguments of
+ * the neighbor entries; nyxhip_n_columns / nyxhip_column_name do not know it.  One call runs the contour chain once and lets the
+ * neighbor kernels, the morphology kernel (CONTOUR | HULL) and the Feret kernel write into a scratch table of the context, then a
+ * lane per ROI closes the formula.
+ * GATES, in the reference's order (:202, then :43-49 and :159).  A row is three times -1.0 (the class's `novalue`; raw, not soft_nan)
+ * when the ROI has no contour, when CONVEX_HULL_AREA == 0, or when NUM_NEIGHBORS < 3.  No ROI is skipped for flat intensities
+ * (has_bad_data() is false in this version of the reference, roi_cache.cpp:43-47).
+ * FORMULA.  calculate() operation for operation (:34-152): the 11 areas and 14 perimeters in its order, the 55 + 91 ratios
+ * 1 - |1 - a / b| in its ib < ic order summed one after the other, area ratios that are not finite left out (:91), perimeter ratios
+ * not (:136: a NaN or an infinity -- STAT_FERET_DIAM_MIN == 0, a perimeter of 0 -- goes through the sums as it does there), population
+ * deviations from a second pass.  Left raw like every other table (nyxhip_finalize_table).
+ * BITS.  Every operation is an IEEE fp64 +, -, *, / or square root, unfused (the reference is built without FMA), and the six inputs
+ * have the reference's bits, so a row whose NUM_NEIGHBORS is at most 128 has the reference's bits: tan(M_PI / k), the only
+ * transcendental (:51-52), comes for k <= 128 from a table the context fills once with the host's libm.  Beyond 128 neighbors the
+ * device's tan serves POLYGONALITY_AVE (the project's standing tolerance); the two hexagonality columns do not read it.
+ * pixel_distance <= 0 is NYXHIP_ERR_INVALID_ARG; beyond 46340: NYXHIP_ERR_UNSUPPORTED (the neighbor class).  settings->soft_nan is
+ * the only field of the settings that is read (a ROI of fewer than two pixels has it as its Feret diameters; the first gate takes
+ * that row). */
+#define NYXHIP_HEXPOLY_COLS 3
+int nyxhip_hexpoly_column_name(int col, char* buf, size_t buf_len);
+
+/* Arguments, memory kinds, checks and error codes of nyxhip_neighbors_batch: image k owns rows [image_offset[k], image_offset[k + 1])
+ * (NULL: one image), strictly ascending in roi_label; origins both NULL or both given.  An empty batch is NYXHIP_OK.  Synchronous. */
+int nyxhip_hexpoly_batch(nyxhip_ctx* ctx, const nyxhip_batch* batch, const uint32_t* origin_x, const uint32_t* origin_y,
+                         const uint64_t* image_offset, uint64_t n_images, int32_t pixel_distance,
+                         const nyxhip_settings* s, double* out_table /* [n_roi x 3] */, size_t out_ld);
+/* The tile path (label scan, ROI assembly, chunks under max_device_bytes) with one image per tile, as nyxhip_neighbors_tiles; rows in
+ * the (tile, label) order of nyxhip_featurize_tiles_v2, outputs as there. */
+int nyxhip_hexpoly_tiles(nyxhip_ctx* ctx, const nyxhip_tiles* tiles, int32_t pixel_distance, const nyxhip_settings* s,
+                         uint32_t* out_labels, uint32_t* out_tile_index, uint64_t max_rows,
+                         double* out_table, size_t out_ld, uint64_t* n_roi_out);
+
 /* ---- measurement hooks -------------------------------------------------------
  * Average device time (ms) per featurize call since the last nyxhip_timing_reset(),
  * measured with hipEvents recorded on the launch stream around EVERYTHING the call

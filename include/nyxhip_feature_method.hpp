@@ -140,6 +140,15 @@ enum class FeatureIMQ : int {
     _FIRST_ = FOCUS_SCORE
 };
 
+// POLYGONALITY_AVE, HEXAGONALITY_AVE, HEXAGONALITY_STDDEV (featureset.h:146-148, in the reference between EXTREMA_P8_Y and
+// DIAMETER_MIN_ENCLOSING_CIRCLE): an enum of their own whose values continue behind FeatureIMQ, so that they index the same LR::fvals
+// and the codes numbered before them keep their values.
+enum class FeatureHexPoly : int {
+    POLYGONALITY_AVE = (int)FeatureIMQ::_COUNT_, HEXAGONALITY_AVE, HEXAGONALITY_STDDEV,
+    _COUNT_,
+    _FIRST_ = POLYGONALITY_AVE
+};
+
 // ---- settings (feature_settings.h:6-54) ----------------------------------------------------------
 union FeatureSetting { bool bval; int ival; double rval; };
 typedef std::vector<FeatureSetting> Fsettings;
@@ -177,7 +186,7 @@ public:
     PixIntens aux_min = (std::numeric_limits<PixIntens>::max)(), aux_max = 0;
     AABB aabb;
     std::vector<std::vector<double>> fvals;
-    void initialize_fvals() { fvals.assign((size_t)FeatureIMQ::_COUNT_, std::vector<double>(1, 0.0)); }   // roi_cache.cpp:105-110
+    void initialize_fvals() { fvals.assign((size_t)FeatureHexPoly::_COUNT_, std::vector<double>(1, 0.0)); }   // roi_cache.cpp:105-110
     // phase-1 bookkeeping of one pixel (feed_pixel_2_metrics, pixel_feed.cpp:19-43 + feed_pixel_2_cache :71-74)
     void feed_pixel(StatsInt x, StatsInt y, PixIntens i)
     {
@@ -195,7 +204,10 @@ struct Dataset { std::vector<SlideProps> dataset_props; };
 // ---- feature-set bits (featureset.h FeatureSet) ------------------------------------------------------
 class FeatureSet {
 public:
-    FeatureSet() : bits((size_t)FeatureIMQ::_COUNT_, false) {}
+    FeatureSet() : bits((size_t)FeatureHexPoly::_COUNT_, false) {}
+    void enableFeature(FeatureHexPoly f) { bits[(size_t)f] = true; }
+    bool isEnabled(FeatureHexPoly f) const { return bits[(size_t)f]; }
+    bool anyEnabled(const std::initializer_list<FeatureHexPoly>& F) const { for (auto f : F) if (bits[(size_t)f]) return true; return false; }
     void enableFeature(Feature2D f) { bits[(size_t)f] = true; }
     void enableFeature(FeatureIMQ f) { bits[(size_t)f] = true; }
     void enableFeatures(const std::initializer_list<FeatureIMQ>& F) { for (auto f : F) bits[(size_t)f] = true; }
@@ -426,11 +438,43 @@ public:
                                          const Fsettings& s, const Dataset& ds) { reduce_range(NYXHIP_FAM_RADIAL, start, end, labels, roiData, s, ds); }
 };
 
+using Roidata = std::unordered_map<int, LR>;
+// The ROIs of one image as the host batch of the entries that relate them to each other (nyxhip_neighbors_batch, nyxhip_hexpoly_batch):
+// the labels in ascending order (the order the reference sorts them into, neighbors.cpp:149-152), LR::aabb's origin, and every LR's
+// fvals sized for every code.
+struct ImageRois {
+    std::vector<int> L;
+    std::vector<uint32_t> lab, bw, bh, mn, mx, ox, oy, inten;
+    std::vector<uint64_t> off;
+    std::vector<uint16_t> x, y;
+    nyxhip_batch b{};
+    ImageRois(const char* who, Roidata& roiData, const std::unordered_set<int>& uniqueLabels) : L(uniqueLabels.begin(), uniqueLabels.end())
+    {
+        std::sort(L.begin(), L.end());
+        const size_t n = L.size();
+        lab.resize(n); bw.resize(n); bh.resize(n); mn.resize(n); mx.resize(n); ox.resize(n); oy.resize(n);
+        off.assign(n + 1, 0);
+        for (size_t i = 0; i < n; i++) {
+            LR& r = roiData.at(L[i]);
+            if (L[i] < 0 || r.aabb.get_xmin() < 0 || r.aabb.get_ymin() < 0) throw std::runtime_error(std::string(who) + ": negative label or origin");
+            lab[i] = (uint32_t)L[i]; bw[i] = (uint32_t)r.aabb.get_width(); bh[i] = (uint32_t)r.aabb.get_height();
+            mn[i] = r.aux_min; mx[i] = r.aux_max;
+            ox[i] = (uint32_t)r.aabb.get_xmin(); oy[i] = (uint32_t)r.aabb.get_ymin();
+            for (const Pixel2& p : r.raw_pixels) { x.push_back((uint16_t)(p.x - r.aabb.get_xmin())); y.push_back((uint16_t)(p.y - r.aabb.get_ymin())); inten.push_back(p.inten); }
+            off[i + 1] = inten.size();
+            if (r.fvals.size() < (size_t)FeatureHexPoly::_COUNT_) r.fvals.resize((size_t)FeatureHexPoly::_COUNT_, std::vector<double>(1, 0.0));
+        }
+        b.n_roi = n; b.roi_label = lab.data(); b.px_offset = off.data(); b.x = x.data(); b.y = y.data(); b.inten = inten.data();
+        b.bbox_w = bw.data(); b.bbox_h = bh.data(); b.min_inten = mn.data(); b.max_inten = mx.data();
+        b.memory = NYXHIP_MEM_HOST;
+    }
+    ImageRois(const ImageRois&) = delete;
+    ImageRois& operator=(const ImageRois&) = delete;
+};
 // NeighborsFeature (features/neighbors.h): no per-ROI class -- calculate() is empty in the reference too (neighbors.cpp:40-41) -- but a
 // reduction over the ROIs of one image: manual_reduce(roiData, settings, uniqueLabels) relates them to each other (boxes that overlap at
 // PIXELDISTANCE, then exact contour distances).  Served by nyxhip_neighbors_batch over the labels in ascending order (the order the
 // reference sorts them into, neighbors.cpp:149-152) with LR::aabb's origin; the contours are built inside the call.
-using Roidata = std::unordered_map<int, LR>;
 class NeighborsFeature : public FeatureMethod {
 public:
     NeighborsFeature() : FeatureMethod("NeighborsFeature") { provide_features(Feature2D::NUM_NEIGHBORS, Feature2D::ANG_BW_NEIGHBORS_MODE); }
@@ -442,34 +486,54 @@ public:
         if (uniqueLabels.empty()) return;
         nyxhip_settings s = make_settings(fst);
         const int radius = NYXHIP_STNGS_MISSING(fst) ? 5 : fst[(int)NyxSetting::PIXELDISTANCE].ival;   // (the reference's default neighbor distance)
-        std::vector<int> L(uniqueLabels.begin(), uniqueLabels.end());
-        std::sort(L.begin(), L.end());
+        ImageRois im("NeighborsFeature", roiData, uniqueLabels);
+        const std::vector<int>& L = im.L;
         const size_t n = L.size();
-        std::vector<uint32_t> lab(n), bw(n), bh(n), mn(n), mx(n), ox(n), oy(n), inten;
-        std::vector<uint64_t> off(n + 1, 0);
-        std::vector<uint16_t> x, y;
-        for (size_t i = 0; i < n; i++) {
-            LR& r = roiData.at(L[i]);
-            if (L[i] < 0 || r.aabb.get_xmin() < 0 || r.aabb.get_ymin() < 0) throw std::runtime_error("NeighborsFeature: negative label or origin");
-            lab[i] = (uint32_t)L[i]; bw[i] = (uint32_t)r.aabb.get_width(); bh[i] = (uint32_t)r.aabb.get_height();
-            mn[i] = r.aux_min; mx[i] = r.aux_max;
-            ox[i] = (uint32_t)r.aabb.get_xmin(); oy[i] = (uint32_t)r.aabb.get_ymin();
-            for (const Pixel2& p : r.raw_pixels) { x.push_back((uint16_t)(p.x - r.aabb.get_xmin())); y.push_back((uint16_t)(p.y - r.aabb.get_ymin())); inten.push_back(p.inten); }
-            off[i + 1] = inten.size();
-            if (r.fvals.empty()) r.initialize_fvals();
-        }
-        nyxhip_batch b{};
-        b.n_roi = n; b.roi_label = lab.data(); b.px_offset = off.data(); b.x = x.data(); b.y = y.data(); b.inten = inten.data();
-        b.bbox_w = bw.data(); b.bbox_h = bh.data(); b.min_inten = mn.data(); b.max_inten = mx.data();
-        b.memory = NYXHIP_MEM_HOST;
         std::vector<double> table(n * (size_t)NYXHIP_NEIGHBOR_COLS);
         nyxhip_ctx* ctx = context();
-        if (nyxhip_neighbors_batch(ctx, &b, ox.data(), oy.data(), nullptr, 0, radius, &s, table.data(), (size_t)NYXHIP_NEIGHBOR_COLS) != NYXHIP_OK)
+        if (nyxhip_neighbors_batch(ctx, &im.b, im.ox.data(), im.oy.data(), nullptr, 0, radius, &s, table.data(), (size_t)NYXHIP_NEIGHBOR_COLS) != NYXHIP_OK)
             throw std::runtime_error(std::string("nyxhip_neighbors_batch: ") + nyxhip_last_error(ctx));
         for (size_t i = 0; i < n; i++) {
             LR& r = roiData.at(L[i]);
             for (int c = 0; c < NYXHIP_NEIGHBOR_COLS; c++)
                 r.fvals[(int)Feature2D::NUM_NEIGHBORS + c].assign(1, table[i * (size_t)NYXHIP_NEIGHBOR_COLS + (size_t)c]);
+        }
+    }
+};
+
+// HexagonalityPolygonalityFeature (features/hexagonality_polygonality.h): a closing formula over NUM_NEIGHBORS, PERIMETER, CONVEX_HULL_AREA
+// and the Feret diameters of every ROI, so like NeighborsFeature a reduction over the ROIs of one image -- the reference runs it behind the
+// classes it depends on; here nyxhip_hexpoly_batch forms all six inputs itself (one contour chain) and closes them, over the labels in
+// ascending order with LR::aabb's origin at PIXELDISTANCE.  Rows the class gates hold its `novalue`, -1.
+class HexagonalityPolygonalityFeature : public FeatureMethod {
+public:
+    static constexpr int novalue = -1;
+    HexagonalityPolygonalityFeature() : FeatureMethod("HexagonalityPolygonalityFeature")
+    {
+        for (int f = (int)FeatureHexPoly::_FIRST_; f < (int)FeatureHexPoly::_COUNT_; f++) provided.push_back(f);
+    }
+    static bool required(const FeatureSet& fs)
+    {
+        return fs.anyEnabled({FeatureHexPoly::POLYGONALITY_AVE, FeatureHexPoly::HEXAGONALITY_AVE, FeatureHexPoly::HEXAGONALITY_STDDEV});
+    }
+    void calculate(LR&, const Fsettings&) override {}
+    void save_value(std::vector<std::vector<double>>&) override {}
+    static void manual_reduce(Roidata& roiData, const Fsettings& fst, const std::unordered_set<int>& uniqueLabels)
+    {
+        if (uniqueLabels.empty()) return;
+        nyxhip_settings s = make_settings(fst);
+        const int radius = NYXHIP_STNGS_MISSING(fst) ? 5 : fst[(int)NyxSetting::PIXELDISTANCE].ival;   // (the reference's default neighbor distance)
+        ImageRois im("HexagonalityPolygonalityFeature", roiData, uniqueLabels);
+        const std::vector<int>& L = im.L;
+        const size_t n = L.size();
+        std::vector<double> table(n * (size_t)NYXHIP_HEXPOLY_COLS);
+        nyxhip_ctx* ctx = context();
+        if (nyxhip_hexpoly_batch(ctx, &im.b, im.ox.data(), im.oy.data(), nullptr, 0, radius, &s, table.data(), (size_t)NYXHIP_HEXPOLY_COLS) != NYXHIP_OK)
+            throw std::runtime_error(std::string("nyxhip_hexpoly_batch: ") + nyxhip_last_error(ctx));
+        for (size_t i = 0; i < n; i++) {
+            LR& r = roiData.at(L[i]);
+            for (int c = 0; c < NYXHIP_HEXPOLY_COLS; c++)
+                r.fvals[(int)FeatureHexPoly::_FIRST_ + c].assign(1, table[i * (size_t)NYXHIP_HEXPOLY_COLS + (size_t)c]);
         }
     }
 };

@@ -61,6 +61,7 @@ SLIDE_MONTAGE, SLIDE_PER_TILE, SLIDE_GIVEN = 0, 1, 2
 FAM_WHOLE_SLIDE = 0x3FF     # the families nyxhip_featurize_slides serves: bits 0-9, FAM_ALL without the two moment classes
 MAX_GLCM_ANGLES = 4
 NEIGHBOR_COLS = 9            # NYXHIP_NEIGHBOR_COLS: the table of nyxhip_neighbors_batch / _tiles (no family bit: the class relates the ROIs of an image)
+HEXPOLY_COLS = 3             # NYXHIP_HEXPOLY_COLS: the table of nyxhip_hexpoly_batch / _tiles (no family bit: the class reads the neighbor count)
 IH_COLS = 46                 # NYXHIP_IH_COLS: the table of nyxhip_ih_batch / _tiles (no family bit: every bit of the mask is spoken for)
 IMQ_COLS = 4          # NYXHIP_IMQ_COLS: FOCUS_SCORE, LOCAL_FOCUS_SCORE, MAX_SATURATION, MIN_SATURATION
 MAX_GABOR_FILTERS = 16

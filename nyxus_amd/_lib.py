@@ -38,6 +38,7 @@ ABI_SYMBOLS = [
     "nyxhip_voldzone_n_columns", "nyxhip_voldzone_column_name", "nyxhip_featurize_volumes_dzones",
     "nyxhip_vshape_n_columns", "nyxhip_vshape_column_name", "nyxhip_featurize_volumes_shape",
     "nyxhip_morph_n_columns", "nyxhip_morph_column_name", "nyxhip_morph_batch", "nyxhip_morph_tiles",
+    "nyxhip_hexpoly_column_name", "nyxhip_hexpoly_batch", "nyxhip_hexpoly_tiles",
 ]
 
 
@@ -190,6 +191,15 @@ def load() -> C.CDLL:
         lib.nyxhip_morph_tiles.argtypes = [C.c_void_p, P(_abi.Tiles), C.c_uint32, P(_abi.Settings), C.c_void_p, C.c_void_p, C.c_uint64,
                                            C.c_void_p, C.c_size_t, P(C.c_uint64)]
         lib.nyxhip_morph_tiles.restype = C.c_int
+    if hasattr(lib, "nyxhip_hexpoly_batch"):     # (absent from older builds of the ABI selected through NYXHIP_LIB for A/B runs)
+        lib.nyxhip_hexpoly_column_name.argtypes = [C.c_int, C.c_char_p, C.c_size_t]
+        lib.nyxhip_hexpoly_column_name.restype = C.c_int
+        lib.nyxhip_hexpoly_batch.argtypes = [C.c_void_p, P(_abi.Batch), C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int32, P(_abi.Settings),
+                                             C.c_void_p, C.c_size_t]
+        lib.nyxhip_hexpoly_batch.restype = C.c_int
+        lib.nyxhip_hexpoly_tiles.argtypes = [C.c_void_p, P(_abi.Tiles), C.c_int32, P(_abi.Settings), C.c_void_p, C.c_void_p, C.c_uint64,
+                                             C.c_void_p, C.c_size_t, P(C.c_uint64)]
+        lib.nyxhip_hexpoly_tiles.restype = C.c_int
     if hasattr(lib, "nyxhip_featurize_slides"):  # (absent from older builds of the ABI selected through NYXHIP_LIB for A/B runs)
         lib.nyxhip_featurize_slides.argtypes = [C.c_void_p, P(_abi.Tiles), C.c_uint32, P(_abi.Settings), C.c_void_p, C.c_size_t]
         lib.nyxhip_featurize_slides.restype = C.c_int
@@ -226,6 +236,11 @@ def column_names(mask: int, s: _abi.Settings) -> List[str]:
 def neighbor_column_names() -> List[str]:
     """The nine columns of nyxhip_neighbors_batch / _tiles, enum order."""
     return _catalogue(_abi.NEIGHBOR_COLS, load().nyxhip_neighbor_column_name, (), "neighbor column")
+
+
+def hexpoly_column_names() -> List[str]:
+    """The three columns of nyxhip_hexpoly_batch / _tiles, enum order."""
+    return _catalogue(_abi.HEXPOLY_COLS, load().nyxhip_hexpoly_column_name, (), "hexagonality / polygonality column")
 
 
 def ih_column_names() -> List[str]:
@@ -370,6 +385,50 @@ class Context:
         t.max_device_bytes = int(max_device_bytes)
         n = C.c_uint64(0)
         self._check(self._lib.nyxhip_neighbors_tiles(self._h, C.byref(t), int(distance), C.byref(s), None, None, 0, None, 0, C.byref(n)))
+        labels = np.zeros(n.value, np.uint32); tiles = np.zeros(n.value, np.uint32); table = np.empty((n.value, ncol), np.float64)
+        self._check(self._lib.nyxhip_fetch_result(self._h, labels.ctypes.data, tiles.ctypes.data, table.ctypes.data, ncol))
+        return tiles, labels, table
+
+    def hexpoly_host(self, batch: _abi.HostBatch, distance: int, s: _abi.Settings) -> np.ndarray:
+        """POLYGONALITY_AVE, HEXAGONALITY_AVE, HEXAGONALITY_STDDEV [n_roi x 3] of a host batch (nyxhip_hexpoly_batch); -1, NaN and inf are
+        left in place.  batch.image_offset, the label order and the origins as in neighbors_host."""
+        if batch.origin_unrepresentable:
+            raise ValueError("the hexagonality / polygonality class needs the ROIs' origins, and this batch's lie below 0 or beyond 32 bits")
+        out = np.empty((batch.n_roi, _abi.HEXPOLY_COLS), np.float64)
+        cb = batch.c_struct()
+        io = batch.image_offset
+        self._check(self._lib.nyxhip_hexpoly_batch(
+            self._h, C.byref(cb), batch.origin_x.ctypes.data if batch.origin_x is not None else None,
+            batch.origin_y.ctypes.data if batch.origin_y is not None else None, io.ctypes.data if io is not None else None,
+            len(io) - 1 if io is not None else 0, int(distance), C.byref(s), out.ctypes.data, _abi.HEXPOLY_COLS))
+        return out
+
+    def hexpoly_device(self, cb: _abi.Batch, origin_x_ptr: Optional[int], origin_y_ptr: Optional[int], image_offset_ptr: Optional[int], n_images: int,
+                       distance: int, s: _abi.Settings, out_ptr: int, ld: int):
+        """Device pointers in ``cb`` (roi_label, px_offset, x, y, inten, bbox_w, bbox_h), device origins and image offsets (or None) and a
+        device table; synchronous (nyxhip_hexpoly_batch)."""
+        self._check(self._lib.nyxhip_hexpoly_batch(self._h, C.byref(cb), C.c_void_p(origin_x_ptr), C.c_void_p(origin_y_ptr), C.c_void_p(image_offset_ptr),
+                                                   int(n_images), int(distance), C.byref(s), C.c_void_p(out_ptr), ld))
+
+    def hexpoly_tiles_host(self, inten: np.ndarray, label: np.ndarray, distance: int, s: _abi.Settings, max_device_bytes: int = 0):
+        """The three columns of a stack [n_tiles, H, W] of host tiles, one image per tile (nyxhip_hexpoly_tiles).  Returns (tile_index, labels,
+        table [n_roi x 3]) in the (tile, label) row order of featurize_tiles_host."""
+        if inten.shape != label.shape or inten.ndim != 3:
+            raise ValueError("stacks must be 3-D arrays [n_tiles, H, W] of the same shape")
+        dt = {np.dtype(np.uint8): _abi.U8, np.dtype(np.uint16): _abi.U16, np.dtype(np.uint32): _abi.U32}
+        inten = np.ascontiguousarray(inten if inten.dtype in dt else inten.astype(np.uint32))
+        label = np.ascontiguousarray(label if label.dtype in dt else label.astype(np.uint32))
+        nt, h, w = inten.shape
+        ncol = _abi.HEXPOLY_COLS
+        if nt == 0:
+            return np.zeros(0, np.uint32), np.zeros(0, np.uint32), np.zeros((0, ncol))
+        t = _abi.Tiles()
+        t.inten = inten.ctypes.data; t.label = label.ctypes.data
+        t.inten_dtype = dt[inten.dtype]; t.label_dtype = dt[label.dtype]
+        t.width = w; t.height = h; t.n_tiles = nt; t.memory = _abi.MEM_HOST; t.slide_mode = _abi.SLIDE_MONTAGE
+        t.max_device_bytes = int(max_device_bytes)
+        n = C.c_uint64(0)
+        self._check(self._lib.nyxhip_hexpoly_tiles(self._h, C.byref(t), int(distance), C.byref(s), None, None, 0, None, 0, C.byref(n)))
         labels = np.zeros(n.value, np.uint32); tiles = np.zeros(n.value, np.uint32); table = np.empty((n.value, ncol), np.float64)
         self._check(self._lib.nyxhip_fetch_result(self._h, labels.ctypes.data, tiles.ctypes.data, table.ctypes.data, ncol))
         return tiles, labels, table

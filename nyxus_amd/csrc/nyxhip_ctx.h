@@ -10,6 +10,7 @@
 //   nyxhip_ih.hip        the intensity-histogram entries: column names, the launches over a device-resident batch, nyxhip_ih_batch
 //   nyxhip_imq.hip       the image-quality entries: column names, the launches over a device-resident batch, nyxhip_imq_batch / _slides
 //   nyxhip_morph.hip     the 2-D morphology entries: column catalogue of a morphology mask, the launches over a device-resident batch, nyxhip_morph_batch
+//   nyxhip_hexpoly.hip   the hexagonality / polygonality entries: column names, one contour chain for three producers and the closing kernel, nyxhip_hexpoly_batch
 //   nyxhip_vol.hip       the volume entries: column catalogue of the volume mask, chunks under the budget, nyxhip_featurize_volumes
 #pragma once
 #include <hip/hip_runtime.h>
@@ -35,6 +36,7 @@
 #include "roi_circle.h"
 #include "roi_neighbors.h"
 #include "roi_morph.h"
+#include "roi_hexpoly.h"
 #include "roi_ih.h"
 #include "roi_imq.h"
 #include "roi_vol.h"
@@ -182,6 +184,10 @@ struct nyxhip_ctx {
     // morphology entries (roi_morph.hip): derived batch extrema | the boxes beyond the LDS column table / intensity plane and their workspace
     DevBuf d_morph_ext;
     DeferredBufs d_morph;
+    // hexagonality / polygonality entries (roi_hexpoly.hip): the scratch table [n_roi x kHexpolyInLd] of the six inputs | tan(M_PI / k) of the
+    // host's libm, k <= kHexpolyTanCap, filled on the context's first call
+    DevBuf d_hexpoly;
+    DevBuf d_hexpoly_tan;
     const uint32_t* origin_x_next = nullptr;   // set by nyxhip_featurize_batch[_async]_at and the tile path for their next launch_device call:
     const uint32_t* origin_y_next = nullptr;   // device arrays [n_roi] of the ROIs' box origins (NULL: (0, 0))
     // grow-only workspaces of the fused tile path: scan tables + rows | clouds | two staging slots for host tiles
@@ -322,11 +328,31 @@ extern const char* const kImqWidthMessage;
 // max_px / max_area / max_side: the batch extrema (any 0: derived on the device).
 int morph_device(nyxhip_ctx* ctx, const nyxhip_batch* b, const uint32_t* d_ox, const uint32_t* d_oy, uint32_t morph, const nyxhip_settings* s,
                  double* d_out, size_t ld, uint32_t max_px, uint32_t max_area, uint32_t max_side);
+// The parts of neighbors_device and morph_device behind the contour chain: the same launches over a chain that has already run (`m`: the
+// argument block launch_contour_families handed back).  morph_from_contours reads no contour when `morph` holds neither CONTOUR nor HULL.
+int neighbors_from_contours(nyxhip_ctx* ctx, const nyxhip_batch* b, const uint32_t* d_ox, const uint32_t* d_oy, const uint64_t* d_image_offset,
+                            uint64_t n_images, const uint32_t* d_image_id, int32_t pixel_distance, const MomArgs& m, double* d_out, size_t ld);
+int morph_from_contours(nyxhip_ctx* ctx, const nyxhip_batch* b, const uint32_t* d_ox, const uint32_t* d_oy, uint32_t morph, const MomArgs& m, double* d_out,
+                        size_t ld, uint32_t max_area, uint32_t max_side);
+int derive_batch_extrema(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t* max_px, uint32_t* max_area, uint32_t* max_side);   // each at least 1; one read-back
+// nyxhip_hexpoly.hip: the kHexpolyCols columns of HexagonalityPolygonalityFeature of a device-resident batch -> d_out [n_roi x ld] (enqueued on
+// the context's stream).  Arguments as neighbors_device.  ONE contour chain feeds the neighbor kernels and roi_morph_kernel; with the
+// Feret kernel they fill the context's scratch table (roi_hexpoly.h), which the closing kernel reads.
+int hexpoly_device(nyxhip_ctx* ctx, const nyxhip_batch* b, const uint32_t* d_ox, const uint32_t* d_oy, const uint64_t* d_image_offset, uint64_t n_images,
+                   const uint32_t* d_image_id, int32_t pixel_distance, const nyxhip_settings* s, double* d_out, size_t ld, uint32_t max_px,
+                   uint32_t max_area, uint32_t max_side);
+// nyxhip_neighbors.hip: the batch entry shared by the classes that relate the ROIs of an image (neighbors_device, hexpoly_device)
+using ImageBatchFn = int (*)(nyxhip_ctx*, const nyxhip_batch*, const uint32_t*, const uint32_t*, const uint64_t*, uint64_t, const uint32_t*, int32_t,
+                             const nyxhip_settings*, double*, size_t, uint32_t, uint32_t, uint32_t);
+int image_batch_entry(nyxhip_ctx* ctx, const nyxhip_batch* b, const uint32_t* origin_x, const uint32_t* origin_y, const uint64_t* image_offset,
+                      uint64_t n_images, int32_t pixel_distance, const nyxhip_settings* s, double* out, size_t ld, int n_cols, ImageBatchFn device_fn);
 // the tile path's reducers besides the family kernels (the neighbor_distance slot of tiles_run / tiles_chunk): > 0 the neighbor class at that
 // distance, kTilesReducerIh the intensity-histogram class, kTilesReducerImq the image-quality classes, kTilesReducerMorph the 2-D morphology
-// classes (their mask travels in the family_mask slot)
+// classes (their mask travels in the family_mask slot), kTilesReducerHexpoly the hexagonality / polygonality class (the slot holds the tag,
+// so its pixel distance travels in the family_mask slot, as the morphology mask does)
 constexpr int32_t kTilesReducerIh = -1;
 constexpr int32_t kTilesReducerImq = -2;
 constexpr int32_t kTilesReducerMorph = -3;
+constexpr int32_t kTilesReducerHexpoly = -4;
 
 } // namespace nyxhip

@@ -1,6 +1,6 @@
 // nyxhip_morph.hip -- the 2-D morphology entries of include/nyxhip.h: column catalogue of a morphology mask, the launches over a
-// device-resident batch (morph_device: the contour chain when PERIMETER is read, roi_morph_kernel, its list launch over the boxes beyond
-// the LDS carve), and nyxhip_morph_batch.  The tile entry (nyxhip_morph_tiles) lives with the tile path in nyxhip_tiles.hip.
+// device-resident batch (morph_device: the contour chain when PERIMETER is read, then morph_from_contours: roi_morph_kernel, its list
+// launch over the boxes beyond the LDS carve), and nyxhip_morph_batch.  The tile entry (nyxhip_morph_tiles) lives with the tile path in nyxhip_tiles.hip.
 #include "nyxhip_ctx.h"
 #include "deferred_list.h"
 
@@ -18,29 +18,42 @@ static const char* const kMorphHullNames[kMorphHullCols] = {"CIRCULARITY", "CONV
 
 static bool morph_mask_ok(uint32_t m) { return m != 0 && (m & ~(uint32_t)NYXHIP_MORPH_ALL) == 0; }
 
+int derive_batch_extrema(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t* max_px, uint32_t* max_area, uint32_t* max_side)
+{
+    hipStream_t st = ctx->stream();
+    uint32_t ext[3] = {0, 0, 0};
+    HIP_TRY(ctx, ctx->d_morph_ext.reserve(256, st));
+    uint32_t* const d_ext = ctx->d_morph_ext.as<uint32_t>();
+    HIP_TRY(ctx, hipMemsetAsync(d_ext, 0, 12, st));
+    if (launch_nb_extrema(b->n_roi, b->px_offset, b->bbox_w, b->bbox_h, d_ext, st) != 0)
+        return fail(ctx, NYXHIP_ERR_HIP, "morphology extrema kernel: launch failed");
+    HIP_TRY(ctx, hipMemcpyAsync(ext, d_ext, 12, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    *max_px = std::max(ext[0], 1u); *max_area = std::max(ext[1], 1u); *max_side = std::max(ext[2], 1u);
+    return NYXHIP_OK;
+}
+
 int morph_device(nyxhip_ctx* ctx, const nyxhip_batch* b, const uint32_t* d_ox, const uint32_t* d_oy, uint32_t morph, const nyxhip_settings* s,
                  double* d_out, size_t ld, uint32_t max_px, uint32_t max_area, uint32_t max_side)
+{
+    if (b->n_roi == 0) return NYXHIP_OK;
+    if (max_px == 0 || max_area == 0 || max_side == 0)                        // a device batch without stated extrema: derive them
+        if (int erc = derive_batch_extrema(ctx, b, &max_px, &max_area, &max_side)) return erc;
+    // ---- the contour chain, unchanged and alone (no reader): PERIMETER and the EDGE_* columns read its workspace -------------------
+    MomArgs m;
+    memset(&m, 0, sizeof(m));
+    if (morph & (NYXHIP_MORPH_HULL | NYXHIP_MORPH_CONTOUR))
+        if (int crc = launch_contour_families(ctx, b, 0, s, nullptr, 0, max_px, max_area, max_side, false, &m)) return crc;
+    return morph_from_contours(ctx, b, d_ox, d_oy, morph, m, d_out, ld, max_area, max_side);
+}
+
+int morph_from_contours(nyxhip_ctx* ctx, const nyxhip_batch* b, const uint32_t* d_ox, const uint32_t* d_oy, uint32_t morph, const MomArgs& m, double* d_out,
+                        size_t ld, uint32_t max_area, uint32_t max_side)
 {
     hipStream_t st = ctx->stream();
     const uint64_t n = b->n_roi;
     if (n == 0) return NYXHIP_OK;
-    if (max_px == 0 || max_area == 0 || max_side == 0) {                      // a device batch without stated extrema: derive them
-        uint32_t ext[3] = {0, 0, 0};
-        HIP_TRY(ctx, ctx->d_morph_ext.reserve(256, st));
-        uint32_t* const d_ext = ctx->d_morph_ext.as<uint32_t>();
-        HIP_TRY(ctx, hipMemsetAsync(d_ext, 0, 12, st));
-        if (launch_nb_extrema(n, b->px_offset, b->bbox_w, b->bbox_h, d_ext, st) != 0)
-            return fail(ctx, NYXHIP_ERR_HIP, "morphology extrema kernel: launch failed");
-        HIP_TRY(ctx, hipMemcpyAsync(ext, d_ext, 12, hipMemcpyDeviceToHost, st));
-        HIP_TRY(ctx, hipStreamSynchronize(st));
-        max_px = std::max(ext[0], 1u); max_area = std::max(ext[1], 1u); max_side = std::max(ext[2], 1u);
-    }
     const bool need_tab = (morph & NYXHIP_MORPH_HULL) != 0, need_plane = (morph & NYXHIP_MORPH_CONTOUR) != 0;
-    // ---- the contour chain, unchanged and alone (no reader): PERIMETER and the EDGE_* columns read its workspace -------------------
-    MomArgs m;
-    memset(&m, 0, sizeof(m));
-    if (need_tab || need_plane)
-        if (int crc = launch_contour_families(ctx, b, 0, s, nullptr, 0, max_px, max_area, max_side, false, &m)) return crc;
     MorphArgs a;
     memset(&a, 0, sizeof(a));
     a.n_roi = n;

@@ -1,5 +1,6 @@
 // nyxhip_neighbors.hip -- the neighbor entries of include/nyxhip.h: column names, the launches over a device-resident batch
-// (neighbors_device: contour chain, geometry table, candidate lists, narrow phase, closing), and nyxhip_neighbors_batch.  The tile entry
+// (neighbors_device: the contour chain, then neighbors_from_contours: geometry table, candidate lists, narrow phase, closing), the batch
+// entry of the classes that relate the ROIs of an image (image_batch_entry) and nyxhip_neighbors_batch.  The tile entry
 // (nyxhip_neighbors_tiles) lives with the tile path in nyxhip_tiles.hip.
 #include "nyxhip_ctx.h"
 
@@ -11,6 +12,21 @@ static const char* const kNeighborNames[kNeighborCols] = {
     "NUM_NEIGHBORS", "PERCENT_TOUCHING", "CLOSEST_NEIGHBOR1_DIST", "CLOSEST_NEIGHBOR1_ANG", "CLOSEST_NEIGHBOR2_DIST", "CLOSEST_NEIGHBOR2_ANG",
     "ANG_BW_NEIGHBORS_MEAN", "ANG_BW_NEIGHBORS_STDDEV", "ANG_BW_NEIGHBORS_MODE"};
 
+namespace {
+
+// the carve of nyxhip_ctx::d_nb_geo for n ROIs: geometry table, candidate counts and offsets, the three derived extrema
+struct NbGeo {
+    size_t o_box, o_cen, o_lo, o_hi, o_cnt, o_off, o_ext, need;
+    explicit NbGeo(uint64_t n)
+    {
+        auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
+        o_box = 0; o_cen = al(o_box + 32 * n); o_lo = al(o_cen + 16 * n); o_hi = al(o_lo + 4 * n); o_cnt = al(o_hi + 4 * n);
+        o_off = al(o_cnt + 4 * n); o_ext = al(o_off + 8 * (n + 1)); need = al(o_ext + 16);
+    }
+};
+
+} // namespace
+
 int neighbors_device(nyxhip_ctx* ctx, const nyxhip_batch* b, const uint32_t* d_ox, const uint32_t* d_oy, const uint64_t* d_image_offset, uint64_t n_images,
                      const uint32_t* d_image_id, int32_t pixel_distance, const nyxhip_settings* s, double* d_out, size_t ld, uint32_t max_px,
                      uint32_t max_area, uint32_t max_side)
@@ -18,12 +34,10 @@ int neighbors_device(nyxhip_ctx* ctx, const nyxhip_batch* b, const uint32_t* d_o
     hipStream_t st = ctx->stream();
     const uint64_t n = b->n_roi;
     if (n == 0) return NYXHIP_OK;
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    // ---- geometry table, candidate counts and offsets (sized by the ROI count) ------------------------------------------------
-    const size_t o_box = 0, o_cen = al(o_box + 32 * n), o_lo = al(o_cen + 16 * n), o_hi = al(o_lo + 4 * n), o_cnt = al(o_hi + 4 * n),
-                 o_off = al(o_cnt + 4 * n), o_ext = al(o_off + 8 * (n + 1)), geo_need = al(o_ext + 16);
-    HIP_TRY(ctx, ctx->d_nb_geo.reserve(geo_need, st, geo_need + geo_need / 8));
+    const NbGeo G(n);
+    HIP_TRY(ctx, ctx->d_nb_geo.reserve(G.need, st, G.need + G.need / 8));
     char* const g = ctx->d_nb_geo.as<char>();
+    const size_t o_ext = G.o_ext;
     if (max_px == 0 || max_area == 0 || max_side == 0) {                      // a device batch without stated extrema: derive them
         uint32_t ext[3] = {0, 0, 0};
         HIP_TRY(ctx, hipMemsetAsync(g + o_ext, 0, 12, st));
@@ -36,6 +50,21 @@ int neighbors_device(nyxhip_ctx* ctx, const nyxhip_batch* b, const uint32_t* d_o
     // ---- the contour chain, unchanged: roi_contour_kernel with its big-box list chain, no reader ----------------------------------
     MomArgs m;
     if (int crc = launch_contour_families(ctx, b, 0, s, nullptr, 0, max_px, max_area, max_side, false, &m)) return crc;
+    return neighbors_from_contours(ctx, b, d_ox, d_oy, d_image_offset, n_images, d_image_id, pixel_distance, m, d_out, ld);
+}
+
+int neighbors_from_contours(nyxhip_ctx* ctx, const nyxhip_batch* b, const uint32_t* d_ox, const uint32_t* d_oy, const uint64_t* d_image_offset,
+                            uint64_t n_images, const uint32_t* d_image_id, int32_t pixel_distance, const MomArgs& m, double* d_out, size_t ld)
+{
+    hipStream_t st = ctx->stream();
+    const uint64_t n = b->n_roi;
+    if (n == 0) return NYXHIP_OK;
+    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    // ---- geometry table, candidate counts and offsets (sized by the ROI count) ------------------------------------------------
+    const NbGeo G(n);
+    HIP_TRY(ctx, ctx->d_nb_geo.reserve(G.need, st, G.need + G.need / 8));
+    char* const g = ctx->d_nb_geo.as<char>();
+    const size_t o_box = G.o_box, o_cen = G.o_cen, o_lo = G.o_lo, o_hi = G.o_hi, o_cnt = G.o_cnt, o_off = G.o_off;
     NbArgs a;
     memset(&a, 0, sizeof(a));
     a.n_roi = n;
@@ -66,19 +95,11 @@ int neighbors_device(nyxhip_ctx* ctx, const nyxhip_batch* b, const uint32_t* d_o
     return NYXHIP_OK;
 }
 
-} // namespace nyxhip
-
-extern "C" {
-
-int nyxhip_neighbor_column_name(int col, char* buf, size_t buf_len)
-{
-    if (!buf || buf_len == 0 || col < 0 || col >= kNeighborCols) return NYXHIP_ERR_INVALID_ARG;
-    snprintf(buf, buf_len, "%s", kNeighborNames[col]);
-    return NYXHIP_OK;
-}
-
-int nyxhip_neighbors_batch(nyxhip_ctx* ctx, const nyxhip_batch* b, const uint32_t* origin_x, const uint32_t* origin_y, const uint64_t* image_offset,
-                           uint64_t n_images, int32_t pixel_distance, const nyxhip_settings* s, double* out, size_t ld)
+// The batch entry of a class that relates the ROIs of an image to each other -- nyxhip_neighbors_batch, and nyxhip_hexpoly_batch which
+// reads the neighbor count: argument checks, the device batch as it is, a host batch staged into one slab and its table copied back.
+// n_cols columns come from device_fn.
+int image_batch_entry(nyxhip_ctx* ctx, const nyxhip_batch* b, const uint32_t* origin_x, const uint32_t* origin_y, const uint64_t* image_offset,
+                      uint64_t n_images, int32_t pixel_distance, const nyxhip_settings* s, double* out, size_t ld, int n_cols, ImageBatchFn device_fn)
 {
     if (!ctx) return NYXHIP_ERR_INVALID_ARG;
     if (!b || !s || !out) return fail(ctx, NYXHIP_ERR_INVALID_ARG, "null batch / settings / out_table");
@@ -89,7 +110,7 @@ int nyxhip_neighbors_batch(nyxhip_ctx* ctx, const nyxhip_batch* b, const uint32_
         return fail(ctx, NYXHIP_ERR_INVALID_ARG, "origin_x and origin_y must both be given or both NULL");
     if (b->n_roi && (!b->roi_label || !b->px_offset || !b->x || !b->y || !b->inten || !b->bbox_w || !b->bbox_h))
         return fail(ctx, NYXHIP_ERR_INVALID_ARG, "batch has null array pointers (the neighbor entries read roi_label)");
-    if (ld < (size_t)kNeighborCols) return fail(ctx, NYXHIP_ERR_INVALID_ARG, "out_ld smaller than the column count");
+    if (ld < (size_t)n_cols) return fail(ctx, NYXHIP_ERR_INVALID_ARG, "out_ld smaller than the column count");
     if (b->n_roi > 0x7FFFFFFFull) return fail(ctx, NYXHIP_ERR_INVALID_ARG, "too many ROIs in one batch");
     if (image_offset && n_images == 0) return fail(ctx, NYXHIP_ERR_INVALID_ARG, "image_offset given with n_images == 0");
     if (b->memory != NYXHIP_MEM_DEVICE && b->memory != NYXHIP_MEM_HOST) return fail(ctx, NYXHIP_ERR_INVALID_ARG, "bad batch->memory");
@@ -98,8 +119,8 @@ int nyxhip_neighbors_batch(nyxhip_ctx* ctx, const nyxhip_batch* b, const uint32_
     hipStream_t st = ctx->stream();
     if (b->memory == NYXHIP_MEM_DEVICE) {
         const bool hinted = b->max_px != 0 && b->max_bbox_area != 0 && b->max_bbox_side != 0;
-        if (int rc = neighbors_device(ctx, b, origin_x, origin_y, image_offset, n_images, nullptr, pixel_distance, s, out, ld, hinted ? b->max_px : 0,
-                                      hinted ? b->max_bbox_area : 0, hinted ? b->max_bbox_side : 0))
+        if (int rc = device_fn(ctx, b, origin_x, origin_y, image_offset, n_images, nullptr, pixel_distance, s, out, ld, hinted ? b->max_px : 0,
+                               hinted ? b->max_bbox_area : 0, hinted ? b->max_bbox_side : 0))
             return rc;
         return nyxhip_sync(ctx);
     }
@@ -123,7 +144,7 @@ int nyxhip_neighbors_batch(nyxhip_ctx* ctx, const nyxhip_batch* b, const uint32_
     const size_t o_off = 0, o_x = al(o_off + 8 * (nr + 1)), o_y = al(o_x + 2 * npx), o_i = al(o_y + 2 * npx), o_bw = al(o_i + 4 * npx),
                  o_bh = al(o_bw + 4 * nr), o_lab = al(o_bh + 4 * nr), o_ox = al(o_lab + 4 * nr), o_oy = al(o_ox + (origin_x ? 4 * nr : 0)),
                  o_img = al(o_oy + (origin_x ? 4 * nr : 0)), o_out = al(o_img + (image_offset ? 8 * (n_images + 1) : 0)),
-                 total = al(o_out + 8ull * nr * kNeighborCols);
+                 total = al(o_out + 8ull * nr * (size_t)n_cols);
     if (int rc = ensure_stage(ctx, total)) return rc;
     char* const base = ctx->d_stage.as<char>();
     HIP_TRY(ctx, hipMemcpyAsync(base + o_off, b->px_offset, 8 * (nr + 1), hipMemcpyHostToDevice, st));
@@ -145,14 +166,31 @@ int nyxhip_neighbors_batch(nyxhip_ctx* ctx, const nyxhip_batch* b, const uint32_
     d.x = (const uint16_t*)(base + o_x); d.y = (const uint16_t*)(base + o_y); d.inten = (const uint32_t*)(base + o_i);
     d.bbox_w = (const uint32_t*)(base + o_bw); d.bbox_h = (const uint32_t*)(base + o_bh);
     double* const d_out = (double*)(base + o_out);
-    if (int rc = neighbors_device(ctx, &d, origin_x ? (const uint32_t*)(base + o_ox) : nullptr, origin_x ? (const uint32_t*)(base + o_oy) : nullptr,
-                                  image_offset ? (const uint64_t*)(base + o_img) : nullptr, n_images, nullptr, pixel_distance, s, d_out,
-                                  (size_t)kNeighborCols, max_px, max_area, max_side))
+    if (int rc = device_fn(ctx, &d, origin_x ? (const uint32_t*)(base + o_ox) : nullptr, origin_x ? (const uint32_t*)(base + o_oy) : nullptr,
+                           image_offset ? (const uint64_t*)(base + o_img) : nullptr, n_images, nullptr, pixel_distance, s, d_out,
+                           (size_t)n_cols, max_px, max_area, max_side))
         return rc;
-    HIP_TRY(ctx, hipMemcpy2DAsync(out, ld * sizeof(double), d_out, (size_t)kNeighborCols * sizeof(double), (size_t)kNeighborCols * sizeof(double), nr,
+    HIP_TRY(ctx, hipMemcpy2DAsync(out, ld * sizeof(double), d_out, (size_t)n_cols * sizeof(double), (size_t)n_cols * sizeof(double), nr,
                                   hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, hipStreamSynchronize(st));
     return check_status(ctx);
+}
+
+} // namespace nyxhip
+
+extern "C" {
+
+int nyxhip_neighbor_column_name(int col, char* buf, size_t buf_len)
+{
+    if (!buf || buf_len == 0 || col < 0 || col >= kNeighborCols) return NYXHIP_ERR_INVALID_ARG;
+    snprintf(buf, buf_len, "%s", kNeighborNames[col]);
+    return NYXHIP_OK;
+}
+
+int nyxhip_neighbors_batch(nyxhip_ctx* ctx, const nyxhip_batch* b, const uint32_t* origin_x, const uint32_t* origin_y, const uint64_t* image_offset,
+                           uint64_t n_images, int32_t pixel_distance, const nyxhip_settings* s, double* out, size_t ld)
+{
+    return image_batch_entry(ctx, b, origin_x, origin_y, image_offset, n_images, pixel_distance, s, out, ld, kNeighborCols, neighbors_device);
 }
 
 } // extern "C"

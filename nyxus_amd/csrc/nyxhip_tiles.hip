@@ -39,6 +39,8 @@ static size_t chunk_table_bytes(uint32_t nt, uint32_t cap)
 // neighbor_distance == kTilesReducerImq: the fourth, the kImqCols image-quality columns (imq_device over the chunk's clouds).
 // neighbor_distance == kTilesReducerMorph: the fifth, the columns of the morphology mask in family_mask (morph_device over the chunk's clouds,
 // the boxes' places inside their tile as origins).
+// neighbor_distance == kTilesReducerHexpoly: the sixth, the kHexpolyCols hexagonality / polygonality columns (hexpoly_device over the chunk's
+// clouds, one image per tile like the neighbor class); the slot holds the tag, so the pixel distance travels in family_mask.
 static int tiles_chunk(nyxhip_ctx* ctx, const void* d_inten, int dtI, const void* d_label, int dtL, uint32_t W, uint32_t H, uint32_t nt,
                        int slide_mode, const double* h_smin, const double* h_smax, uint32_t family_mask, const nyxhip_settings* s,
                        uint64_t rows_cap, uint32_t* d_lab, uint32_t* d_til, uint32_t tile_base, double* d_out, size_t d_ld, uint32_t label_limit,
@@ -157,6 +159,8 @@ static int tiles_chunk(nyxhip_ctx* ctx, const void* d_inten, int dtI, const void
         return imq_device(ctx, &b, s, d_out, d_ld, meta[4]);
     if (neighbor_distance == kTilesReducerMorph)
         return morph_device(ctx, &b, R.bbox_x0, R.bbox_y0, family_mask, s, d_out, d_ld, meta[3], meta[4], meta[6]);
+    if (neighbor_distance == kTilesReducerHexpoly)
+        return hexpoly_device(ctx, &b, R.bbox_x0, R.bbox_y0, nullptr, 0, R.tile, (int32_t)family_mask, s, d_out, d_ld, meta[3], meta[4], meta[6]);
     if (neighbor_distance)
         return neighbors_device(ctx, &b, R.bbox_x0, R.bbox_y0, nullptr, 0, R.tile, neighbor_distance, s, d_out, d_ld, meta[3], meta[4], meta[6]);
     OriginScope origins(ctx, R.bbox_x0, R.bbox_y0);
@@ -327,9 +331,10 @@ static int tiles_run(nyxhip_ctx* ctx, const nyxhip_tiles* t, uint32_t family_mas
                      uint64_t max_rows, double* out_table, size_t out_ld, uint64_t* n_roi_out, uint32_t label_limit, uint32_t tile_index_base = 0,
                      const HostPin* prepinned = nullptr, int32_t neighbor_distance = 0)
 {
-    // (a morphology mask is no family mask: the entry has checked it, and no family's settings are read)
-    if (int vrc = tiles_validate(ctx, t, neighbor_distance == kTilesReducerMorph ? 0u : family_mask, s, n_roi_out, neighbor_distance != 0)) return vrc;
-    const int n_cols = neighbor_distance == kTilesReducerMorph ? morph_n_columns(family_mask) : neighbor_distance == kTilesReducerIh ? kIhCols : neighbor_distance == kTilesReducerImq ? kImqCols : neighbor_distance ? kNeighborCols : nyxhip_n_columns(family_mask, s);
+    // (a morphology mask or a pixel distance is no family mask: the entry has checked it, and no family's settings are read)
+    const bool slot_is_mask = neighbor_distance != kTilesReducerMorph && neighbor_distance != kTilesReducerHexpoly;
+    if (int vrc = tiles_validate(ctx, t, slot_is_mask ? family_mask : 0u, s, n_roi_out, neighbor_distance != 0)) return vrc;
+    const int n_cols = neighbor_distance == kTilesReducerHexpoly ? kHexpolyCols : neighbor_distance == kTilesReducerMorph ? morph_n_columns(family_mask) : neighbor_distance == kTilesReducerIh ? kIhCols : neighbor_distance == kTilesReducerImq ? kImqCols : neighbor_distance ? kNeighborCols : nyxhip_n_columns(family_mask, s);
     const bool host = t->memory == NYXHIP_MEM_HOST || t->memory == NYXHIP_MEM_HOST_OWN_MAPPING;
     const bool keep = host && out_table == nullptr;                  // result stays in the context (nyxhip_fetch_result)
     if (!keep && (!out_labels || !out_table)) return fail(ctx, NYXHIP_ERR_INVALID_ARG, "null output pointers");
@@ -521,6 +526,17 @@ int nyxhip_morph_tiles(nyxhip_ctx* ctx, const nyxhip_tiles* tiles, uint32_t morp
     if (!ctx) return NYXHIP_ERR_INVALID_ARG;
     if (nyxhip_morph_n_columns(morph_mask) < 0) return fail(ctx, NYXHIP_ERR_INVALID_ARG, "bad morphology mask");
     return tiles_run(ctx, tiles, morph_mask, s, out_labels, out_tile_index, max_rows, out_table, out_ld, n_roi_out, 0xFFFFFFFFu, 0, nullptr, kTilesReducerMorph);
+}
+
+int nyxhip_hexpoly_tiles(nyxhip_ctx* ctx, const nyxhip_tiles* tiles, int32_t pixel_distance, const nyxhip_settings* s, uint32_t* out_labels,
+                         uint32_t* out_tile_index, uint64_t max_rows, double* out_table, size_t out_ld, uint64_t* n_roi_out)
+{
+    if (!ctx) return NYXHIP_ERR_INVALID_ARG;
+    if (pixel_distance <= 0) return fail(ctx, NYXHIP_ERR_INVALID_ARG, "pixel_distance must be greater than zero");
+    if (pixel_distance > kNbMaxDistance)
+        return fail(ctx, NYXHIP_ERR_UNSUPPORTED, "pixel_distance beyond 46340: its square overflows the reference's int (neighbors.cpp:242)");
+    return tiles_run(ctx, tiles, (uint32_t)pixel_distance, s, out_labels, out_tile_index, max_rows, out_table, out_ld, n_roi_out, 0xFFFFFFFFu, 0, nullptr,
+                     kTilesReducerHexpoly);
 }
 
 int nyxhip_fetch_result(nyxhip_ctx* ctx, uint32_t* out_labels, uint32_t* out_tile_index, double* out_table, size_t out_ld)
