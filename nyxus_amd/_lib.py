@@ -366,16 +366,15 @@ class Context:
             len(io) - 1 if io is not None else 0, int(distance), C.byref(s), out.ctypes.data, _abi.NEIGHBOR_COLS))
         return out
 
-    def neighbors_tiles_host(self, inten: np.ndarray, label: np.ndarray, distance: int, s: _abi.Settings, max_device_bytes: int = 0):
-        """The neighbor columns of a stack [n_tiles, H, W] of host tiles, one image per tile (nyxhip_neighbors_tiles).  Returns
-        (tile_index, labels, table [n_roi x 9]) in the (tile, label) row order of featurize_tiles_host."""
+    def _tiles_table(self, entry, lead: tuple, ncol: int, inten: np.ndarray, label: np.ndarray, s: _abi.Settings, max_device_bytes: int):
+        """(tile_index, labels, table [n_roi x ncol]) of a stack [n_tiles, H, W] of host tiles through the tile entry of a class with entries of
+        its own: entry(ctx, tiles, *lead, settings, outputs...) keeps its rows in the context, nyxhip_fetch_result copies them out."""
         if inten.shape != label.shape or inten.ndim != 3:
             raise ValueError("stacks must be 3-D arrays [n_tiles, H, W] of the same shape")
         dt = {np.dtype(np.uint8): _abi.U8, np.dtype(np.uint16): _abi.U16, np.dtype(np.uint32): _abi.U32}
         inten = np.ascontiguousarray(inten if inten.dtype in dt else inten.astype(np.uint32))
         label = np.ascontiguousarray(label if label.dtype in dt else label.astype(np.uint32))
         nt, h, w = inten.shape
-        ncol = _abi.NEIGHBOR_COLS
         if nt == 0:
             return np.zeros(0, np.uint32), np.zeros(0, np.uint32), np.zeros((0, ncol))
         t = _abi.Tiles()
@@ -384,10 +383,15 @@ class Context:
         t.width = w; t.height = h; t.n_tiles = nt; t.memory = _abi.MEM_HOST; t.slide_mode = _abi.SLIDE_MONTAGE
         t.max_device_bytes = int(max_device_bytes)
         n = C.c_uint64(0)
-        self._check(self._lib.nyxhip_neighbors_tiles(self._h, C.byref(t), int(distance), C.byref(s), None, None, 0, None, 0, C.byref(n)))
+        self._check(entry(self._h, C.byref(t), *lead, C.byref(s), None, None, 0, None, 0, C.byref(n)))
         labels = np.zeros(n.value, np.uint32); tiles = np.zeros(n.value, np.uint32); table = np.empty((n.value, ncol), np.float64)
         self._check(self._lib.nyxhip_fetch_result(self._h, labels.ctypes.data, tiles.ctypes.data, table.ctypes.data, ncol))
         return tiles, labels, table
+
+    def neighbors_tiles_host(self, inten: np.ndarray, label: np.ndarray, distance: int, s: _abi.Settings, max_device_bytes: int = 0):
+        """The neighbor columns of a stack [n_tiles, H, W] of host tiles, one image per tile (nyxhip_neighbors_tiles).  Returns
+        (tile_index, labels, table [n_roi x 9]) in the (tile, label) row order of featurize_tiles_host."""
+        return self._tiles_table(self._lib.nyxhip_neighbors_tiles, (int(distance),), _abi.NEIGHBOR_COLS, inten, label, s, max_device_bytes)
 
     def hexpoly_host(self, batch: _abi.HostBatch, distance: int, s: _abi.Settings) -> np.ndarray:
         """POLYGONALITY_AVE, HEXAGONALITY_AVE, HEXAGONALITY_STDDEV [n_roi x 3] of a host batch (nyxhip_hexpoly_batch); -1, NaN and inf are
@@ -413,25 +417,7 @@ class Context:
     def hexpoly_tiles_host(self, inten: np.ndarray, label: np.ndarray, distance: int, s: _abi.Settings, max_device_bytes: int = 0):
         """The three columns of a stack [n_tiles, H, W] of host tiles, one image per tile (nyxhip_hexpoly_tiles).  Returns (tile_index, labels,
         table [n_roi x 3]) in the (tile, label) row order of featurize_tiles_host."""
-        if inten.shape != label.shape or inten.ndim != 3:
-            raise ValueError("stacks must be 3-D arrays [n_tiles, H, W] of the same shape")
-        dt = {np.dtype(np.uint8): _abi.U8, np.dtype(np.uint16): _abi.U16, np.dtype(np.uint32): _abi.U32}
-        inten = np.ascontiguousarray(inten if inten.dtype in dt else inten.astype(np.uint32))
-        label = np.ascontiguousarray(label if label.dtype in dt else label.astype(np.uint32))
-        nt, h, w = inten.shape
-        ncol = _abi.HEXPOLY_COLS
-        if nt == 0:
-            return np.zeros(0, np.uint32), np.zeros(0, np.uint32), np.zeros((0, ncol))
-        t = _abi.Tiles()
-        t.inten = inten.ctypes.data; t.label = label.ctypes.data
-        t.inten_dtype = dt[inten.dtype]; t.label_dtype = dt[label.dtype]
-        t.width = w; t.height = h; t.n_tiles = nt; t.memory = _abi.MEM_HOST; t.slide_mode = _abi.SLIDE_MONTAGE
-        t.max_device_bytes = int(max_device_bytes)
-        n = C.c_uint64(0)
-        self._check(self._lib.nyxhip_hexpoly_tiles(self._h, C.byref(t), int(distance), C.byref(s), None, None, 0, None, 0, C.byref(n)))
-        labels = np.zeros(n.value, np.uint32); tiles = np.zeros(n.value, np.uint32); table = np.empty((n.value, ncol), np.float64)
-        self._check(self._lib.nyxhip_fetch_result(self._h, labels.ctypes.data, tiles.ctypes.data, table.ctypes.data, ncol))
-        return tiles, labels, table
+        return self._tiles_table(self._lib.nyxhip_hexpoly_tiles, (int(distance),), _abi.HEXPOLY_COLS, inten, label, s, max_device_bytes)
 
     def morph_host(self, batch: _abi.HostBatch, mmask: int, s: _abi.Settings) -> np.ndarray:
         """The columns of morphology mask `mmask` (_abi.MORPH_*) of a host batch (nyxhip_morph_batch); NaN / inf are left in place.
@@ -462,22 +448,7 @@ class Context:
         ncol = self._lib.nyxhip_morph_n_columns(mmask)
         if ncol < 0:
             raise NyxHipError(1, f"bad morphology mask {mmask:#x}")
-        dt = {np.dtype(np.uint8): _abi.U8, np.dtype(np.uint16): _abi.U16, np.dtype(np.uint32): _abi.U32}
-        inten = np.ascontiguousarray(inten if inten.dtype in dt else inten.astype(np.uint32))
-        label = np.ascontiguousarray(label if label.dtype in dt else label.astype(np.uint32))
-        nt, h, w = inten.shape
-        if nt == 0:
-            return np.zeros(0, np.uint32), np.zeros(0, np.uint32), np.zeros((0, ncol))
-        t = _abi.Tiles()
-        t.inten = inten.ctypes.data; t.label = label.ctypes.data
-        t.inten_dtype = dt[inten.dtype]; t.label_dtype = dt[label.dtype]
-        t.width = w; t.height = h; t.n_tiles = nt; t.memory = _abi.MEM_HOST; t.slide_mode = _abi.SLIDE_MONTAGE
-        t.max_device_bytes = int(max_device_bytes)
-        n = C.c_uint64(0)
-        self._check(self._lib.nyxhip_morph_tiles(self._h, C.byref(t), mmask, C.byref(s), None, None, 0, None, 0, C.byref(n)))
-        labels = np.zeros(n.value, np.uint32); tiles = np.zeros(n.value, np.uint32); table = np.empty((n.value, ncol), np.float64)
-        self._check(self._lib.nyxhip_fetch_result(self._h, labels.ctypes.data, tiles.ctypes.data, table.ctypes.data, ncol))
-        return tiles, labels, table
+        return self._tiles_table(self._lib.nyxhip_morph_tiles, (mmask,), ncol, inten, label, s, max_device_bytes)
 
     def ih_host(self, batch: _abi.HostBatch, s: _abi.Settings) -> np.ndarray:
         """The intensity-histogram columns [n_roi x 46] of a host batch (nyxhip_ih_batch); NaN / inf are left in place."""
@@ -493,25 +464,7 @@ class Context:
     def ih_tiles_host(self, inten: np.ndarray, label: np.ndarray, s: _abi.Settings, max_device_bytes: int = 0):
         """The intensity-histogram columns of a stack [n_tiles, H, W] of host tiles (nyxhip_ih_tiles).  Returns (tile_index, labels,
         table [n_roi x 46]) in the (tile, label) row order of featurize_tiles_host."""
-        if inten.shape != label.shape or inten.ndim != 3:
-            raise ValueError("stacks must be 3-D arrays [n_tiles, H, W] of the same shape")
-        dt = {np.dtype(np.uint8): _abi.U8, np.dtype(np.uint16): _abi.U16, np.dtype(np.uint32): _abi.U32}
-        inten = np.ascontiguousarray(inten if inten.dtype in dt else inten.astype(np.uint32))
-        label = np.ascontiguousarray(label if label.dtype in dt else label.astype(np.uint32))
-        nt, h, w = inten.shape
-        ncol = _abi.IH_COLS
-        if nt == 0:
-            return np.zeros(0, np.uint32), np.zeros(0, np.uint32), np.zeros((0, ncol))
-        t = _abi.Tiles()
-        t.inten = inten.ctypes.data; t.label = label.ctypes.data
-        t.inten_dtype = dt[inten.dtype]; t.label_dtype = dt[label.dtype]
-        t.width = w; t.height = h; t.n_tiles = nt; t.memory = _abi.MEM_HOST; t.slide_mode = _abi.SLIDE_MONTAGE
-        t.max_device_bytes = int(max_device_bytes)
-        n = C.c_uint64(0)
-        self._check(self._lib.nyxhip_ih_tiles(self._h, C.byref(t), C.byref(s), None, None, 0, None, 0, C.byref(n)))
-        labels = np.zeros(n.value, np.uint32); tiles = np.zeros(n.value, np.uint32); table = np.empty((n.value, ncol), np.float64)
-        self._check(self._lib.nyxhip_fetch_result(self._h, labels.ctypes.data, tiles.ctypes.data, table.ctypes.data, ncol))
-        return tiles, labels, table
+        return self._tiles_table(self._lib.nyxhip_ih_tiles, (), _abi.IH_COLS, inten, label, s, max_device_bytes)
 
     def _volume_table(self, entry, n_columns, mask_noun: str, batch: _abi.HostBatch3D, mask: int, n_lead: tuple, lead: tuple, stated: bool,
                       max_device_bytes: int) -> np.ndarray:
@@ -586,25 +539,7 @@ class Context:
     def imq_tiles_host(self, inten: np.ndarray, label: np.ndarray, s: _abi.Settings, max_device_bytes: int = 0):
         """The image-quality columns of a stack [n_tiles, H, W] of host tiles (nyxhip_imq_tiles).  Returns (tile_index, labels,
         table [n_roi x 4]) in the (tile, label) row order of featurize_tiles_host."""
-        if inten.shape != label.shape or inten.ndim != 3:
-            raise ValueError("stacks must be 3-D arrays [n_tiles, H, W] of the same shape")
-        dt = {np.dtype(np.uint8): _abi.U8, np.dtype(np.uint16): _abi.U16, np.dtype(np.uint32): _abi.U32}
-        inten = np.ascontiguousarray(inten if inten.dtype in dt else inten.astype(np.uint32))
-        label = np.ascontiguousarray(label if label.dtype in dt else label.astype(np.uint32))
-        nt, h, w = inten.shape
-        ncol = _abi.IMQ_COLS
-        if nt == 0:
-            return np.zeros(0, np.uint32), np.zeros(0, np.uint32), np.zeros((0, ncol))
-        t = _abi.Tiles()
-        t.inten = inten.ctypes.data; t.label = label.ctypes.data
-        t.inten_dtype = dt[inten.dtype]; t.label_dtype = dt[label.dtype]
-        t.width = w; t.height = h; t.n_tiles = nt; t.memory = _abi.MEM_HOST; t.slide_mode = _abi.SLIDE_MONTAGE
-        t.max_device_bytes = int(max_device_bytes)
-        n = C.c_uint64(0)
-        self._check(self._lib.nyxhip_imq_tiles(self._h, C.byref(t), C.byref(s), None, None, 0, None, 0, C.byref(n)))
-        labels = np.zeros(n.value, np.uint32); tiles = np.zeros(n.value, np.uint32); table = np.empty((n.value, ncol), np.float64)
-        self._check(self._lib.nyxhip_fetch_result(self._h, labels.ctypes.data, tiles.ctypes.data, table.ctypes.data, ncol))
-        return tiles, labels, table
+        return self._tiles_table(self._lib.nyxhip_imq_tiles, (), _abi.IMQ_COLS, inten, label, s, max_device_bytes)
 
     def imq_slides_host(self, inten: np.ndarray, s: _abi.Settings, max_device_bytes: int = 0) -> np.ndarray:
         """Whole-slide mode (nyxhip_imq_slides): a stack [n, H, W] of uint8 / uint16 / uint32 host slides, every slide one ROI that

@@ -5,6 +5,7 @@
 // label vector out over std::async threads per feature family (parallel.h:23-42),
 // one fused kernel launch covers every requested family for the whole ROI batch.
 #include "nyxhip_ctx.h"
+#include "batch_stage.h"
 
 using namespace nyxhip;
 
@@ -134,81 +135,17 @@ int nyxhip_featurize_batch(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t mask
 int nyxhip_featurize_batch_at(nyxhip_ctx* ctx, const nyxhip_batch* b, const uint32_t* origin_x, const uint32_t* origin_y,
                               uint32_t mask, const nyxhip_settings* s, double* out, size_t ld)
 {
-    int rc = validate(ctx, b, mask, s, out, ld);
-    if (rc) return rc;
-    if ((origin_x == nullptr) != (origin_y == nullptr))
-        return fail(ctx, NYXHIP_ERR_INVALID_ARG, "origin_x and origin_y must both be given or both NULL");
-    if (b->memory == NYXHIP_MEM_DEVICE) {
-        rc = nyxhip_featurize_batch_async_at(ctx, b, origin_x, origin_y, mask, s, out, ld);
-        if (rc) return rc;
-        return nyxhip_sync(ctx);
-    }
-    if (b->memory != NYXHIP_MEM_HOST) return fail(ctx, NYXHIP_ERR_INVALID_ARG, "bad batch->memory");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (b->n_roi == 0) return NYXHIP_OK;
-
-    // host batch: derive extrema, stage SoA arrays into one device slab, run, copy the table back
-    const uint64_t nr = b->n_roi, npx = b->px_offset[nr];
-    uint32_t max_px = 0, max_area = 0, max_range = 0, max_side = 0;
-    uint64_t n_small = 0;                                  // census of the smallest size class (launch_device_all picks lists or filtered launches by it)
-    for (uint64_t r = 0; r < nr; r++) {
-        if (b->px_offset[r + 1] < b->px_offset[r]) return fail(ctx, NYXHIP_ERR_INVALID_ARG, "px_offset is not monotone");
-        if (b->px_offset[r + 1] - b->px_offset[r] <= kClassPx[0] && b->bbox_w[r] <= kClassSide[0] && b->bbox_h[r] <= kClassSide[0]) n_small++;
-        uint64_t n = b->px_offset[r + 1] - b->px_offset[r];
-        uint64_t a = (uint64_t)b->bbox_w[r] * b->bbox_h[r];
-        if (n > 0xFFFFFFFFull || a > 0xFFFFFFFFull) return fail(ctx, NYXHIP_ERR_ROI_TOO_LARGE, "ROI exceeds 2^32 pixels");
-        if (n > max_px) max_px = (uint32_t)n;
-        if (a > max_area) max_area = (uint32_t)a;
-        if (b->max_inten[r] - b->min_inten[r] > max_range) max_range = b->max_inten[r] - b->min_inten[r];
-        if (b->bbox_w[r] > max_side) max_side = b->bbox_w[r];
-        if (b->bbox_h[r] > max_side) max_side = b->bbox_h[r];
-    }
-    const int n_cols = nyxhip_n_columns(mask, s);
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    size_t o_off = 0, o_x = al(o_off + 8 * (nr + 1)), o_y = al(o_x + 2 * npx), o_i = al(o_y + 2 * npx),
-           o_bw = al(o_i + 4 * npx), o_bh = al(o_bw + 4 * nr), o_mn = al(o_bh + 4 * nr), o_mx = al(o_mn + 4 * nr),
-           o_smin = al(o_mx + 4 * nr), o_smax = al(o_smin + 8 * nr), o_ox = al(o_smax + 8 * nr), o_oy = al(o_ox + (origin_x ? 4 * nr : 0)),
-           o_out = al(o_oy + (origin_x ? 4 * nr : 0)),
-           total = al(o_out + 8ull * nr * n_cols);
-    rc = ensure_stage(ctx, total);
-    if (rc) return rc;
-    char* base = ctx->d_stage.as<char>();
-    hipStream_t st = ctx->stream();
-    HIP_TRY(ctx, hipMemcpyAsync(base + o_off, b->px_offset, 8 * (nr + 1), hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipMemcpyAsync(base + o_x, b->x, 2 * npx, hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipMemcpyAsync(base + o_y, b->y, 2 * npx, hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipMemcpyAsync(base + o_i, b->inten, 4 * npx, hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipMemcpyAsync(base + o_bw, b->bbox_w, 4 * nr, hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipMemcpyAsync(base + o_bh, b->bbox_h, 4 * nr, hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipMemcpyAsync(base + o_mn, b->min_inten, 4 * nr, hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipMemcpyAsync(base + o_mx, b->max_inten, 4 * nr, hipMemcpyHostToDevice, st));
-    if (b->slide_min) {
-        HIP_TRY(ctx, hipMemcpyAsync(base + o_smin, b->slide_min, 8 * nr, hipMemcpyHostToDevice, st));
-        HIP_TRY(ctx, hipMemcpyAsync(base + o_smax, b->slide_max, 8 * nr, hipMemcpyHostToDevice, st));
-    }
-    if (origin_x) {
-        HIP_TRY(ctx, hipMemcpyAsync(base + o_ox, origin_x, 4 * nr, hipMemcpyHostToDevice, st));
-        HIP_TRY(ctx, hipMemcpyAsync(base + o_oy, origin_y, 4 * nr, hipMemcpyHostToDevice, st));
-    }
-    nyxhip_batch d = *b;
-    d.memory = NYXHIP_MEM_DEVICE;
-    d.px_offset = (const uint64_t*)(base + o_off);
-    d.x = (const uint16_t*)(base + o_x); d.y = (const uint16_t*)(base + o_y); d.inten = (const uint32_t*)(base + o_i);
-    d.bbox_w = (const uint32_t*)(base + o_bw); d.bbox_h = (const uint32_t*)(base + o_bh);
-    d.min_inten = (const uint32_t*)(base + o_mn); d.max_inten = (const uint32_t*)(base + o_mx);
-    d.slide_min = b->slide_min ? (const double*)(base + o_smin) : nullptr;
-    d.slide_max = b->slide_max ? (const double*)(base + o_smax) : nullptr;
-    double* d_out = (double*)(base + o_out);
-    ctx->census_small = n_small; ctx->census_total = nr; ctx->census_pending = 0;
-    {
-        OriginScope origins(ctx, origin_x ? (const uint32_t*)(base + o_ox) : nullptr, origin_x ? (const uint32_t*)(base + o_oy) : nullptr);
-        rc = launch_device(ctx, &d, mask, s, d_out, (size_t)n_cols, max_px, max_area, max_range, max_side);
-    }
-    if (rc) return rc;
-    HIP_TRY(ctx, hipMemcpy2DAsync(out, ld * sizeof(double), d_out, (size_t)n_cols * sizeof(double),
-                                  (size_t)n_cols * sizeof(double), nr, hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipStreamSynchronize(st));
-    return check_status(ctx);
+    if (int rc = validate(ctx, b, mask, s, out, ld)) return rc;
+    BatchSpec sp{kReadXY | kReadInten | kReadBox | kReadRange | kReadSlide, "batch has null array pointers", nyxhip_n_columns(mask, s)};
+    sp.origin_x = origin_x; sp.origin_y = origin_y;
+    if (int rc = batch_check(ctx, sp, b, s, out, ld)) return rc;
+    return batch_run(ctx, sp, b, out, ld, [&](const StagedBatch& g) {
+        // a host batch: exact extrema and the census of the smallest size class (launch_device_all picks lists or filtered launches by it).
+        // A device batch: the caller's statement when complete, else the size classifier of launch_device_all derives the extrema
+        if (g.host) { ctx->census_small = g.n_small; ctx->census_total = g.d.n_roi; ctx->census_pending = 0; }
+        OriginScope origins(ctx, g.d_ox, g.d_oy);
+        return launch_device(ctx, &g.d, mask, s, g.d_out, g.ld, g.max_px, g.max_area, g.max_range, g.max_side, g.hinted);
+    });
 }
 
 int nyxhip_timing_enable(nyxhip_ctx* ctx, int on)

@@ -6,6 +6,7 @@
 //   nyxhip_tiles.hip     the fused tile path and its host staging
 //   nyxhip_slides.hip    whole-slide mode: nyxhip_featurize_slides (one ROI per slide, no label image)
 //   nyxhip_api.hip       context life cycle, the batch entry points, timing, launch report
+//   batch_stage.h        what every batch entry shares: argument checks, a host batch staged into one slab, its table copied back
 //   nyxhip_neighbors.hip the neighbor entries: column names, the launches over a device-resident batch, nyxhip_neighbors_batch
 //   nyxhip_ih.hip        the intensity-histogram entries: column names, the launches over a device-resident batch, nyxhip_ih_batch
 //   nyxhip_imq.hip       the image-quality entries: column names, the launches over a device-resident batch, nyxhip_imq_batch / _slides
@@ -346,13 +347,13 @@ using ImageBatchFn = int (*)(nyxhip_ctx*, const nyxhip_batch*, const uint32_t*, 
                              const nyxhip_settings*, double*, size_t, uint32_t, uint32_t, uint32_t);
 int image_batch_entry(nyxhip_ctx* ctx, const nyxhip_batch* b, const uint32_t* origin_x, const uint32_t* origin_y, const uint64_t* image_offset,
                       uint64_t n_images, int32_t pixel_distance, const nyxhip_settings* s, double* out, size_t ld, int n_cols, ImageBatchFn device_fn);
-// the tile path's reducers besides the family kernels (the neighbor_distance slot of tiles_run / tiles_chunk): > 0 the neighbor class at that
-// distance, kTilesReducerIh the intensity-histogram class, kTilesReducerImq the image-quality classes, kTilesReducerMorph the 2-D morphology
-// classes (their mask travels in the family_mask slot), kTilesReducerHexpoly the hexagonality / polygonality class (the slot holds the tag,
-// so its pixel distance travels in the family_mask slot, as the morphology mask does)
-constexpr int32_t kTilesReducerIh = -1;
-constexpr int32_t kTilesReducerImq = -2;
-constexpr int32_t kTilesReducerMorph = -3;
-constexpr int32_t kTilesReducerHexpoly = -4;
+int pixel_distance_check(nyxhip_ctx* ctx, int32_t pixel_distance);     // NYXHIP_ERR_INVALID_ARG at or below 0, NYXHIP_ERR_UNSUPPORTED beyond kNbMaxDistance
+// What reduces the ROIs the tile path assembles to rows (tiles_run / tiles_chunk of nyxhip_tiles.hip): the family kernels, or a class with
+// entries of its own.  mask: the family mask of Families, the morphology mask of Morph, else 0.  pixel_distance: of Neighbors and Hexpoly.
+struct TileReducer {
+    enum Kind { Families, Neighbors, Ih, Imq, Morph, Hexpoly } kind;
+    uint32_t mask;
+    int32_t pixel_distance;
+};
 
 } // namespace nyxhip

@@ -1,6 +1,7 @@
 // nyxhip_ih.hip -- the intensity-histogram entries of include/nyxhip.h: column names, the launches over a device-resident batch (ih_device) and
 // nyxhip_ih_batch.  The tile entry (nyxhip_ih_tiles) lives with the tile path in nyxhip_tiles.hip.
 #include "nyxhip_ctx.h"
+#include "batch_stage.h"
 
 using namespace nyxhip;
 
@@ -56,50 +57,14 @@ int nyxhip_ih_column_name(int col, char* buf, size_t buf_len)
 
 int nyxhip_ih_batch(nyxhip_ctx* ctx, const nyxhip_batch* b, const nyxhip_settings* s, double* out, size_t ld)
 {
-    if (!ctx) return NYXHIP_ERR_INVALID_ARG;
-    if (!b || !s || !out) return fail(ctx, NYXHIP_ERR_INVALID_ARG, "null batch / settings / out_table");
-    if (b->n_roi && (!b->px_offset || !b->inten || !b->min_inten || !b->max_inten))
-        return fail(ctx, NYXHIP_ERR_INVALID_ARG, "batch has null array pointers (the intensity-histogram entries read px_offset, inten, min_inten, max_inten)");
-    if (ld < (size_t)kIhCols) return fail(ctx, NYXHIP_ERR_INVALID_ARG, "out_ld smaller than the column count");
-    if (b->n_roi > 0x7FFFFFFFull) return fail(ctx, NYXHIP_ERR_INVALID_ARG, "too many ROIs in one batch");
-    if (b->memory != NYXHIP_MEM_DEVICE && b->memory != NYXHIP_MEM_HOST) return fail(ctx, NYXHIP_ERR_INVALID_ARG, "bad batch->memory");
+    const BatchSpec sp{kReadInten | kReadRange,
+                       "batch has null array pointers (the intensity-histogram entries read px_offset, inten, min_inten, max_inten)", kIhCols};
+    if (int rc = batch_check(ctx, sp, b, s, out, ld)) return rc;
     if (int rc = ih_settings_check(ctx, s)) return rc;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (b->n_roi == 0) return NYXHIP_OK;
-    hipStream_t st = ctx->stream();
-    if (b->memory == NYXHIP_MEM_DEVICE) {
-        if (int rc = ih_device(ctx, b, s, out, ld, b->max_px)) return rc;
-        return nyxhip_sync(ctx);
-    }
-    // host batch: check the CSR array, stage the four arrays into one device slab, run, copy the table back
-    const uint64_t nr = b->n_roi, npx = b->px_offset[nr];
-    uint32_t max_px = 0;
-    for (uint64_t r = 0; r < nr; r++) {
-        if (b->px_offset[r + 1] < b->px_offset[r]) return fail(ctx, NYXHIP_ERR_INVALID_ARG, "px_offset is not monotone");
-        const uint64_t n = b->px_offset[r + 1] - b->px_offset[r];
-        if (n > 0xFFFFFFFFull) return fail(ctx, NYXHIP_ERR_ROI_TOO_LARGE, "ROI exceeds 2^32 pixels");
-        max_px = std::max(max_px, (uint32_t)n);
-    }
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    const size_t o_off = 0, o_i = al(o_off + 8 * (nr + 1)), o_mn = al(o_i + 4 * npx), o_mx = al(o_mn + 4 * nr), o_out = al(o_mx + 4 * nr),
-                 total = al(o_out + 8ull * nr * kIhCols);
-    if (int rc = ensure_stage(ctx, total)) return rc;
-    char* const base = ctx->d_stage.as<char>();
-    HIP_TRY(ctx, hipMemcpyAsync(base + o_off, b->px_offset, 8 * (nr + 1), hipMemcpyHostToDevice, st));
-    if (npx) HIP_TRY(ctx, hipMemcpyAsync(base + o_i, b->inten, 4 * npx, hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipMemcpyAsync(base + o_mn, b->min_inten, 4 * nr, hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipMemcpyAsync(base + o_mx, b->max_inten, 4 * nr, hipMemcpyHostToDevice, st));
-    nyxhip_batch d;
-    memset(&d, 0, sizeof(d));
-    d.n_roi = nr; d.memory = NYXHIP_MEM_DEVICE;
-    d.px_offset = (const uint64_t*)(base + o_off); d.inten = (const uint32_t*)(base + o_i);
-    d.min_inten = (const uint32_t*)(base + o_mn); d.max_inten = (const uint32_t*)(base + o_mx);
-    double* const d_out = (double*)(base + o_out);
-    if (int rc = ih_device(ctx, &d, s, d_out, (size_t)kIhCols, std::max(max_px, 1u))) return rc;
-    HIP_TRY(ctx, hipMemcpy2DAsync(out, ld * sizeof(double), d_out, (size_t)kIhCols * sizeof(double), (size_t)kIhCols * sizeof(double), nr,
-                                  hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipStreamSynchronize(st));
-    return check_status(ctx);
+    return batch_run(ctx, sp, b, out, ld, [&](const StagedBatch& g) {
+        // the largest ROI: a host batch's at least 1 (known), a device batch's as stated (0: not known)
+        return ih_device(ctx, &g.d, s, g.d_out, g.ld, g.host ? std::max(g.max_px, 1u) : g.max_px);
+    });
 }
 
 } // extern "C"

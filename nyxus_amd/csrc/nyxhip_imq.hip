@@ -2,6 +2,7 @@
 // nyxhip_imq_batch and nyxhip_imq_slides.  The tile entry (nyxhip_imq_tiles) lives with the tile path in nyxhip_tiles.hip.
 #include "nyxhip_ctx.h"
 #include "deferred_list.h"
+#include "batch_stage.h"
 
 using namespace nyxhip;
 
@@ -50,7 +51,7 @@ int imq_device(nyxhip_ctx* ctx, const nyxhip_batch* b, const nyxhip_settings* s,
 
 namespace {
 
-constexpr uint32_t kSlideMaxSide = 65534;          // the batch ABI's coordinates are 16-bit (nyxhip_featurize_slides)
+constexpr uint32_t kSlideMaxSide = 65534;         // the batch ABI's coordinates are 16-bit (nyxhip_featurize_slides)
 
 size_t imq_want(size_t need) { return need + need / 8 + (1 << 16); }
 
@@ -91,59 +92,21 @@ int nyxhip_imq_column_name(int col, char* buf, size_t buf_len)
 
 int nyxhip_imq_batch(nyxhip_ctx* ctx, const nyxhip_batch* b, const nyxhip_settings* s, double* out, size_t ld)
 {
-    if (!ctx) return NYXHIP_ERR_INVALID_ARG;
-    if (!b || !s || !out) return fail(ctx, NYXHIP_ERR_INVALID_ARG, "null batch / settings / out_table");
-    if (b->n_roi && (!b->px_offset || !b->x || !b->y || !b->inten || !b->bbox_w || !b->bbox_h || !b->min_inten || !b->max_inten))
-        return fail(ctx, NYXHIP_ERR_INVALID_ARG, "batch has null array pointers (the image-quality entries read px_offset, x, y, inten, bbox_w, bbox_h, min_inten, max_inten)");
-    if (ld < (size_t)kImqCols) return fail(ctx, NYXHIP_ERR_INVALID_ARG, "out_ld smaller than the column count");
-    if (b->n_roi > 0x7FFFFFFFull) return fail(ctx, NYXHIP_ERR_INVALID_ARG, "too many ROIs in one batch");
-    if (b->memory != NYXHIP_MEM_DEVICE && b->memory != NYXHIP_MEM_HOST) return fail(ctx, NYXHIP_ERR_INVALID_ARG, "bad batch->memory");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (b->n_roi == 0) return NYXHIP_OK;
-    hipStream_t st = ctx->stream();
-    if (b->memory == NYXHIP_MEM_DEVICE) {
-        if (int rc = imq_device(ctx, b, s, out, ld, b->max_px ? b->max_bbox_area : 0u)) return rc;
-        HIP_TRY(ctx, hipStreamSynchronize(st));
-        return imq_check_status(ctx);
-    }
-    // host batch: check the arrays, stage them into one device slab, run, copy the table back
-    const uint64_t nr = b->n_roi, npx = b->px_offset[nr];
-    uint32_t max_area = 1;
-    for (uint64_t r = 0; r < nr; r++) {
-        if (b->px_offset[r + 1] < b->px_offset[r]) return fail(ctx, NYXHIP_ERR_INVALID_ARG, "px_offset is not monotone");
-        if (b->px_offset[r + 1] - b->px_offset[r] > 0xFFFFFFFFull) return fail(ctx, NYXHIP_ERR_ROI_TOO_LARGE, "ROI exceeds 2^32 pixels");
+    BatchSpec sp{kReadXY | kReadInten | kReadBox | kReadRange,
+                 "batch has null array pointers (the image-quality entries read px_offset, x, y, inten, bbox_w, bbox_h, min_inten, max_inten)", kImqCols};
+    sp.status = imq_check_status;
+    if (int rc = batch_check(ctx, sp, b, s, out, ld)) return rc;
+    // ROI r of a host batch: the box within 16-bit coordinates, and the width bound the kernels of roi_imq.hip raise on a device batch
+    auto roi_check = [&](uint64_t r) {
         if (b->bbox_w[r] > 65535u || b->bbox_h[r] > 65535u) return fail(ctx, NYXHIP_ERR_ROI_TOO_LARGE, "an ROI's bounding box is wider or taller than 65535 pixels");
         const uint64_t cells = (uint64_t)b->bbox_w[r] * b->bbox_h[r];
         if (b->px_offset[r + 1] > b->px_offset[r] && cells && (uint64_t)b->max_inten[r] * cells >= (1ull << 61)) return fail(ctx, NYXHIP_ERR_UNSUPPORTED, kImqWidthMessage);
-        max_area = (uint32_t)std::max<uint64_t>(max_area, std::min<uint64_t>(cells, 0xFFFFFFFFull));
-    }
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    const size_t o_off = 0, o_x = al(o_off + 8 * (nr + 1)), o_y = al(o_x + 2 * npx), o_i = al(o_y + 2 * npx), o_w = al(o_i + 4 * npx), o_h = al(o_w + 4 * nr),
-                 o_mn = al(o_h + 4 * nr), o_mx = al(o_mn + 4 * nr), o_out = al(o_mx + 4 * nr), total = al(o_out + 8ull * nr * kImqCols);
-    if (int rc = ensure_stage(ctx, total)) return rc;
-    char* const base = ctx->d_stage.as<char>();
-    HIP_TRY(ctx, hipMemcpyAsync(base + o_off, b->px_offset, 8 * (nr + 1), hipMemcpyHostToDevice, st));
-    if (npx) {
-        HIP_TRY(ctx, hipMemcpyAsync(base + o_x, b->x, 2 * npx, hipMemcpyHostToDevice, st));
-        HIP_TRY(ctx, hipMemcpyAsync(base + o_y, b->y, 2 * npx, hipMemcpyHostToDevice, st));
-        HIP_TRY(ctx, hipMemcpyAsync(base + o_i, b->inten, 4 * npx, hipMemcpyHostToDevice, st));
-    }
-    HIP_TRY(ctx, hipMemcpyAsync(base + o_w, b->bbox_w, 4 * nr, hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipMemcpyAsync(base + o_h, b->bbox_h, 4 * nr, hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipMemcpyAsync(base + o_mn, b->min_inten, 4 * nr, hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipMemcpyAsync(base + o_mx, b->max_inten, 4 * nr, hipMemcpyHostToDevice, st));
-    nyxhip_batch d;
-    memset(&d, 0, sizeof(d));
-    d.n_roi = nr; d.memory = NYXHIP_MEM_DEVICE;
-    d.px_offset = (const uint64_t*)(base + o_off); d.x = (const uint16_t*)(base + o_x); d.y = (const uint16_t*)(base + o_y);
-    d.inten = (const uint32_t*)(base + o_i); d.bbox_w = (const uint32_t*)(base + o_w); d.bbox_h = (const uint32_t*)(base + o_h);
-    d.min_inten = (const uint32_t*)(base + o_mn); d.max_inten = (const uint32_t*)(base + o_mx);
-    double* const d_out = (double*)(base + o_out);
-    if (int rc = imq_device(ctx, &d, s, d_out, (size_t)kImqCols, max_area)) return rc;
-    HIP_TRY(ctx, hipMemcpy2DAsync(out, ld * sizeof(double), d_out, (size_t)kImqCols * sizeof(double), (size_t)kImqCols * sizeof(double), nr,
-                                  hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipStreamSynchronize(st));
-    return imq_check_status(ctx);
+        return (int)NYXHIP_OK;
+    };
+    return batch_run(ctx, sp, b, out, ld, [&](const StagedBatch& g) {
+        // the largest box: a host batch's at least 1 (known), a device batch's as stated beside max_px (0: not known)
+        return imq_device(ctx, &g.d, s, g.d_out, g.ld, g.host ? std::max(g.max_area, 1u) : g.max_px ? g.max_area : 0u);
+    }, roi_check);
 }
 
 int nyxhip_imq_slides(nyxhip_ctx* ctx, const nyxhip_tiles* t, const nyxhip_settings* s, double* out_table, size_t out_ld)

@@ -3,6 +3,7 @@
 // launch over the boxes beyond the LDS carve), and nyxhip_morph_batch.  The tile entry (nyxhip_morph_tiles) lives with the tile path in nyxhip_tiles.hip.
 #include "nyxhip_ctx.h"
 #include "deferred_list.h"
+#include "batch_stage.h"
 
 using namespace nyxhip;
 
@@ -122,68 +123,15 @@ int nyxhip_morph_column_name(uint32_t morph_mask, int col, char* buf, size_t buf
 int nyxhip_morph_batch(nyxhip_ctx* ctx, const nyxhip_batch* b, const uint32_t* origin_x, const uint32_t* origin_y, uint32_t morph_mask,
                        const nyxhip_settings* s, double* out, size_t ld)
 {
-    if (!ctx) return NYXHIP_ERR_INVALID_ARG;
-    if (!b || !s || !out) return fail(ctx, NYXHIP_ERR_INVALID_ARG, "null batch / settings / out_table");
-    if (!morph_mask_ok(morph_mask)) return fail(ctx, NYXHIP_ERR_INVALID_ARG, "bad morphology mask");
-    if ((origin_x == nullptr) != (origin_y == nullptr))
-        return fail(ctx, NYXHIP_ERR_INVALID_ARG, "origin_x and origin_y must both be given or both NULL");
-    if (b->n_roi && (!b->px_offset || !b->x || !b->y || !b->inten || !b->bbox_w || !b->bbox_h))
-        return fail(ctx, NYXHIP_ERR_INVALID_ARG, "batch has null array pointers");
-    const int n_cols = morph_n_columns(morph_mask);
-    if (ld < (size_t)n_cols) return fail(ctx, NYXHIP_ERR_INVALID_ARG, "out_ld smaller than the column count");
-    if (b->n_roi > 0x7FFFFFFFull) return fail(ctx, NYXHIP_ERR_INVALID_ARG, "too many ROIs in one batch");
-    if (b->memory != NYXHIP_MEM_DEVICE && b->memory != NYXHIP_MEM_HOST) return fail(ctx, NYXHIP_ERR_INVALID_ARG, "bad batch->memory");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (b->n_roi == 0) return NYXHIP_OK;
-    hipStream_t st = ctx->stream();
-    if (b->memory == NYXHIP_MEM_DEVICE) {
-        const bool hinted = b->max_px != 0 && b->max_bbox_area != 0 && b->max_bbox_side != 0;
-        if (int rc = morph_device(ctx, b, origin_x, origin_y, morph_mask, s, out, ld, hinted ? b->max_px : 0, hinted ? b->max_bbox_area : 0,
-                                  hinted ? b->max_bbox_side : 0))
-            return rc;
-        return nyxhip_sync(ctx);
-    }
-    // host batch: derive extrema, check the CSR arrays, stage the arrays into one device slab, run, copy the table back
-    const uint64_t nr = b->n_roi, npx = b->px_offset[nr];
-    uint32_t max_px = 1, max_area = 1, max_side = 1;
-    for (uint64_t r = 0; r < nr; r++) {
-        if (b->px_offset[r + 1] < b->px_offset[r]) return fail(ctx, NYXHIP_ERR_INVALID_ARG, "px_offset is not monotone");
-        const uint64_t n = b->px_offset[r + 1] - b->px_offset[r], ar = (uint64_t)b->bbox_w[r] * b->bbox_h[r];
-        if (n > 0xFFFFFFFFull || ar > 0xFFFFFFFFull) return fail(ctx, NYXHIP_ERR_ROI_TOO_LARGE, "ROI exceeds 2^32 pixels");
-        max_px = std::max(max_px, (uint32_t)n);
-        max_area = std::max(max_area, (uint32_t)ar);
-        max_side = std::max(max_side, std::max(b->bbox_w[r], b->bbox_h[r]));
-    }
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    const size_t o_off = 0, o_x = al(o_off + 8 * (nr + 1)), o_y = al(o_x + 2 * npx), o_i = al(o_y + 2 * npx), o_bw = al(o_i + 4 * npx),
-                 o_bh = al(o_bw + 4 * nr), o_ox = al(o_bh + 4 * nr), o_oy = al(o_ox + (origin_x ? 4 * nr : 0)),
-                 o_out = al(o_oy + (origin_x ? 4 * nr : 0)), total = al(o_out + 8ull * nr * (size_t)n_cols);
-    if (int rc = ensure_stage(ctx, total)) return rc;
-    char* const base = ctx->d_stage.as<char>();
-    HIP_TRY(ctx, hipMemcpyAsync(base + o_off, b->px_offset, 8 * (nr + 1), hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipMemcpyAsync(base + o_x, b->x, 2 * npx, hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipMemcpyAsync(base + o_y, b->y, 2 * npx, hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipMemcpyAsync(base + o_i, b->inten, 4 * npx, hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipMemcpyAsync(base + o_bw, b->bbox_w, 4 * nr, hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipMemcpyAsync(base + o_bh, b->bbox_h, 4 * nr, hipMemcpyHostToDevice, st));
-    if (origin_x) {
-        HIP_TRY(ctx, hipMemcpyAsync(base + o_ox, origin_x, 4 * nr, hipMemcpyHostToDevice, st));
-        HIP_TRY(ctx, hipMemcpyAsync(base + o_oy, origin_y, 4 * nr, hipMemcpyHostToDevice, st));
-    }
-    nyxhip_batch d;
-    memset(&d, 0, sizeof(d));
-    d.n_roi = nr; d.memory = NYXHIP_MEM_DEVICE;
-    d.px_offset = (const uint64_t*)(base + o_off);
-    d.x = (const uint16_t*)(base + o_x); d.y = (const uint16_t*)(base + o_y); d.inten = (const uint32_t*)(base + o_i);
-    d.bbox_w = (const uint32_t*)(base + o_bw); d.bbox_h = (const uint32_t*)(base + o_bh);
-    double* const d_out = (double*)(base + o_out);
-    if (int rc = morph_device(ctx, &d, origin_x ? (const uint32_t*)(base + o_ox) : nullptr, origin_x ? (const uint32_t*)(base + o_oy) : nullptr,
-                              morph_mask, s, d_out, (size_t)n_cols, max_px, max_area, max_side))
-        return rc;
-    HIP_TRY(ctx, hipMemcpy2DAsync(out, ld * sizeof(double), d_out, (size_t)n_cols * sizeof(double), (size_t)n_cols * sizeof(double), nr,
-                                  hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipStreamSynchronize(st));
-    return check_status(ctx);
+    if (ctx && !morph_mask_ok(morph_mask)) return fail(ctx, NYXHIP_ERR_INVALID_ARG, "bad morphology mask");
+    BatchSpec sp{kReadXY | kReadInten | kReadBox, "batch has null array pointers", morph_n_columns(morph_mask)};
+    sp.origin_x = origin_x; sp.origin_y = origin_y;
+    if (int rc = batch_check(ctx, sp, b, s, out, ld)) return rc;
+    return batch_run(ctx, sp, b, out, ld, [&](const StagedBatch& g) {
+        // the extrema: a host batch's at least 1 each (known), a device batch's complete statement, else 0 (morph_device derives them)
+        auto known = [&](uint32_t v) { return g.hinted ? std::max(v, 1u) : 0u; };
+        return morph_device(ctx, &g.d, g.d_ox, g.d_oy, morph_mask, s, g.d_out, g.ld, known(g.max_px), known(g.max_area), known(g.max_side));
+    });
 }
 
 } // extern "C"

@@ -3,6 +3,7 @@
 // entry of the classes that relate the ROIs of an image (image_batch_entry) and nyxhip_neighbors_batch.  The tile entry
 // (nyxhip_neighbors_tiles) lives with the tile path in nyxhip_tiles.hip.
 #include "nyxhip_ctx.h"
+#include "batch_stage.h"
 
 using namespace nyxhip;
 
@@ -96,84 +97,27 @@ int neighbors_from_contours(nyxhip_ctx* ctx, const nyxhip_batch* b, const uint32
 }
 
 // The batch entry of a class that relates the ROIs of an image to each other -- nyxhip_neighbors_batch, and nyxhip_hexpoly_batch which
-// reads the neighbor count: argument checks, the device batch as it is, a host batch staged into one slab and its table copied back.
-// n_cols columns come from device_fn.
+// reads the neighbor count: the checks and the staging of batch_stage.h around device_fn, which gives n_cols columns.
 int image_batch_entry(nyxhip_ctx* ctx, const nyxhip_batch* b, const uint32_t* origin_x, const uint32_t* origin_y, const uint64_t* image_offset,
                       uint64_t n_images, int32_t pixel_distance, const nyxhip_settings* s, double* out, size_t ld, int n_cols, ImageBatchFn device_fn)
 {
-    if (!ctx) return NYXHIP_ERR_INVALID_ARG;
-    if (!b || !s || !out) return fail(ctx, NYXHIP_ERR_INVALID_ARG, "null batch / settings / out_table");
+    BatchSpec sp{kReadLabel | kReadXY | kReadInten | kReadBox, "batch has null array pointers (the neighbor entries read roi_label)", n_cols};
+    sp.origin_x = origin_x; sp.origin_y = origin_y; sp.image_offset = image_offset; sp.n_images = n_images;
+    if (int rc = batch_check(ctx, sp, b, s, out, ld)) return rc;
+    if (int rc = pixel_distance_check(ctx, pixel_distance)) return rc;
+    return batch_run(ctx, sp, b, out, ld, [&](const StagedBatch& g) {
+        // the extrema: a host batch's as walked, a device batch's complete statement; any 0: device_fn derives them
+        return device_fn(ctx, &g.d, g.d_ox, g.d_oy, g.d_image_offset, n_images, nullptr, pixel_distance, s, g.d_out, g.ld, g.hinted ? g.max_px : 0,
+                         g.hinted ? g.max_area : 0, g.hinted ? g.max_side : 0);
+    });
+}
+
+int pixel_distance_check(nyxhip_ctx* ctx, int32_t pixel_distance)
+{
     if (pixel_distance <= 0) return fail(ctx, NYXHIP_ERR_INVALID_ARG, "pixel_distance must be greater than zero");
     if (pixel_distance > kNbMaxDistance)
         return fail(ctx, NYXHIP_ERR_UNSUPPORTED, "pixel_distance beyond 46340: its square overflows the reference's int (neighbors.cpp:242)");
-    if ((origin_x == nullptr) != (origin_y == nullptr))
-        return fail(ctx, NYXHIP_ERR_INVALID_ARG, "origin_x and origin_y must both be given or both NULL");
-    if (b->n_roi && (!b->roi_label || !b->px_offset || !b->x || !b->y || !b->inten || !b->bbox_w || !b->bbox_h))
-        return fail(ctx, NYXHIP_ERR_INVALID_ARG, "batch has null array pointers (the neighbor entries read roi_label)");
-    if (ld < (size_t)n_cols) return fail(ctx, NYXHIP_ERR_INVALID_ARG, "out_ld smaller than the column count");
-    if (b->n_roi > 0x7FFFFFFFull) return fail(ctx, NYXHIP_ERR_INVALID_ARG, "too many ROIs in one batch");
-    if (image_offset && n_images == 0) return fail(ctx, NYXHIP_ERR_INVALID_ARG, "image_offset given with n_images == 0");
-    if (b->memory != NYXHIP_MEM_DEVICE && b->memory != NYXHIP_MEM_HOST) return fail(ctx, NYXHIP_ERR_INVALID_ARG, "bad batch->memory");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (b->n_roi == 0) return NYXHIP_OK;
-    hipStream_t st = ctx->stream();
-    if (b->memory == NYXHIP_MEM_DEVICE) {
-        const bool hinted = b->max_px != 0 && b->max_bbox_area != 0 && b->max_bbox_side != 0;
-        if (int rc = device_fn(ctx, b, origin_x, origin_y, image_offset, n_images, nullptr, pixel_distance, s, out, ld, hinted ? b->max_px : 0,
-                               hinted ? b->max_bbox_area : 0, hinted ? b->max_bbox_side : 0))
-            return rc;
-        return nyxhip_sync(ctx);
-    }
-    // host batch: derive extrema, check the CSR arrays, stage the arrays into one device slab, run, copy the table back
-    const uint64_t nr = b->n_roi, npx = b->px_offset[nr];
-    uint32_t max_px = 0, max_area = 0, max_side = 0;
-    for (uint64_t r = 0; r < nr; r++) {
-        if (b->px_offset[r + 1] < b->px_offset[r]) return fail(ctx, NYXHIP_ERR_INVALID_ARG, "px_offset is not monotone");
-        const uint64_t n = b->px_offset[r + 1] - b->px_offset[r], ar = (uint64_t)b->bbox_w[r] * b->bbox_h[r];
-        if (n > 0xFFFFFFFFull || ar > 0xFFFFFFFFull) return fail(ctx, NYXHIP_ERR_ROI_TOO_LARGE, "ROI exceeds 2^32 pixels");
-        max_px = std::max(max_px, (uint32_t)n);
-        max_area = std::max(max_area, (uint32_t)ar);
-        max_side = std::max(max_side, std::max(b->bbox_w[r], b->bbox_h[r]));
-    }
-    if (image_offset) {
-        if (image_offset[0] != 0 || image_offset[n_images] != nr) return fail(ctx, NYXHIP_ERR_INVALID_ARG, "image_offset must run from 0 to n_roi");
-        for (uint64_t k = 0; k < n_images; k++)
-            if (image_offset[k + 1] < image_offset[k]) return fail(ctx, NYXHIP_ERR_INVALID_ARG, "image_offset is not monotone");
-    }
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    const size_t o_off = 0, o_x = al(o_off + 8 * (nr + 1)), o_y = al(o_x + 2 * npx), o_i = al(o_y + 2 * npx), o_bw = al(o_i + 4 * npx),
-                 o_bh = al(o_bw + 4 * nr), o_lab = al(o_bh + 4 * nr), o_ox = al(o_lab + 4 * nr), o_oy = al(o_ox + (origin_x ? 4 * nr : 0)),
-                 o_img = al(o_oy + (origin_x ? 4 * nr : 0)), o_out = al(o_img + (image_offset ? 8 * (n_images + 1) : 0)),
-                 total = al(o_out + 8ull * nr * (size_t)n_cols);
-    if (int rc = ensure_stage(ctx, total)) return rc;
-    char* const base = ctx->d_stage.as<char>();
-    HIP_TRY(ctx, hipMemcpyAsync(base + o_off, b->px_offset, 8 * (nr + 1), hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipMemcpyAsync(base + o_x, b->x, 2 * npx, hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipMemcpyAsync(base + o_y, b->y, 2 * npx, hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipMemcpyAsync(base + o_i, b->inten, 4 * npx, hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipMemcpyAsync(base + o_bw, b->bbox_w, 4 * nr, hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipMemcpyAsync(base + o_bh, b->bbox_h, 4 * nr, hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipMemcpyAsync(base + o_lab, b->roi_label, 4 * nr, hipMemcpyHostToDevice, st));
-    if (origin_x) {
-        HIP_TRY(ctx, hipMemcpyAsync(base + o_ox, origin_x, 4 * nr, hipMemcpyHostToDevice, st));
-        HIP_TRY(ctx, hipMemcpyAsync(base + o_oy, origin_y, 4 * nr, hipMemcpyHostToDevice, st));
-    }
-    if (image_offset) HIP_TRY(ctx, hipMemcpyAsync(base + o_img, image_offset, 8 * (n_images + 1), hipMemcpyHostToDevice, st));
-    nyxhip_batch d;
-    memset(&d, 0, sizeof(d));
-    d.n_roi = nr; d.memory = NYXHIP_MEM_DEVICE;
-    d.roi_label = (const uint32_t*)(base + o_lab); d.px_offset = (const uint64_t*)(base + o_off);
-    d.x = (const uint16_t*)(base + o_x); d.y = (const uint16_t*)(base + o_y); d.inten = (const uint32_t*)(base + o_i);
-    d.bbox_w = (const uint32_t*)(base + o_bw); d.bbox_h = (const uint32_t*)(base + o_bh);
-    double* const d_out = (double*)(base + o_out);
-    if (int rc = device_fn(ctx, &d, origin_x ? (const uint32_t*)(base + o_ox) : nullptr, origin_x ? (const uint32_t*)(base + o_oy) : nullptr,
-                           image_offset ? (const uint64_t*)(base + o_img) : nullptr, n_images, nullptr, pixel_distance, s, d_out,
-                           (size_t)n_cols, max_px, max_area, max_side))
-        return rc;
-    HIP_TRY(ctx, hipMemcpy2DAsync(out, ld * sizeof(double), d_out, (size_t)n_cols * sizeof(double), (size_t)n_cols * sizeof(double), nr,
-                                  hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipStreamSynchronize(st));
-    return check_status(ctx);
+    return NYXHIP_OK;
 }
 
 } // namespace nyxhip

@@ -32,20 +32,14 @@ static size_t chunk_table_bytes(uint32_t nt, uint32_t cap)
 }
 
 // One chunk of tiles resident on the device -> rows in d_lab / d_til / d_out (device).  *n_roi_out rows are produced; more than
-// rows_cap -> nothing is written beyond rows_cap and the caller reports the shortage.
-// neighbor_distance > 0: the rows are the kNeighborCols neighbor columns (neighbors_device over the chunk's clouds, one image per tile;
-// family_mask is not read) instead of the family columns -- label scan, ROI assembly and row order are the same piece of code.
-// neighbor_distance == kTilesReducerIh: the third reducer, the kIhCols intensity-histogram columns (ih_device over the chunk's clouds).
-// neighbor_distance == kTilesReducerImq: the fourth, the kImqCols image-quality columns (imq_device over the chunk's clouds).
-// neighbor_distance == kTilesReducerMorph: the fifth, the columns of the morphology mask in family_mask (morph_device over the chunk's clouds,
-// the boxes' places inside their tile as origins).
-// neighbor_distance == kTilesReducerHexpoly: the sixth, the kHexpolyCols hexagonality / polygonality columns (hexpoly_device over the chunk's
-// clouds, one image per tile like the neighbor class); the slot holds the tag, so the pixel distance travels in family_mask.
+// rows_cap -> nothing is written beyond rows_cap and the caller reports the shortage.  `red` says whose columns the rows are: label
+// scan, ROI assembly and row order are the same piece of code for every reducer.
 static int tiles_chunk(nyxhip_ctx* ctx, const void* d_inten, int dtI, const void* d_label, int dtL, uint32_t W, uint32_t H, uint32_t nt,
-                       int slide_mode, const double* h_smin, const double* h_smax, uint32_t family_mask, const nyxhip_settings* s,
+                       int slide_mode, const double* h_smin, const double* h_smax, const TileReducer& red, const nyxhip_settings* s,
                        uint64_t rows_cap, uint32_t* d_lab, uint32_t* d_til, uint32_t tile_base, double* d_out, size_t d_ld, uint32_t label_limit,
-                       uint64_t* n_roi_out, hipStream_t st, int32_t neighbor_distance = 0)
+                       uint64_t* n_roi_out, hipStream_t st)
 {
+    const uint32_t family_mask = red.mask;                               // (read on the Families paths only)
     auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
     uint32_t cap = ctx->tile_cap_hint ? ctx->tile_cap_hint : first_tile_cap((uint64_t)W * H);
     const uint64_t tile_px = (uint64_t)W * H;
@@ -117,7 +111,7 @@ static int tiles_chunk(nyxhip_ctx* ctx, const void* d_inten, int dtI, const void
     const uint64_t npx = ((uint64_t)meta[2] << 32) | meta[1];
     // INTENSITY / GLCM alone, every ROI LDS-sized: the feature kernel reads the ROIs' windows of the tiles itself and no cloud is
     // materialised (8 B per ROI pixel written and read back otherwise).  Any other family, or ROIs beyond LDS: clouds.
-    bool window = !knob::no_window() && !neighbor_distance && (family_mask & ~(uint32_t)(NYXHIP_FAM_INTENSITY | NYXHIP_FAM_GLCM)) == 0;   // (no_window: A/B and tests)
+    bool window = !knob::no_window() && red.kind == TileReducer::Families && (family_mask & ~(uint32_t)(NYXHIP_FAM_INTENSITY | NYXHIP_FAM_GLCM)) == 0;   // (no_window: A/B and tests)
     if (window) {
         LdsLayout Lt; std::string why_t;
         window = make_layout(family_mask, s, nyxhip_n_columns(family_mask, s), meta[3], meta[4], meta[5], Lt, why_t) == NYXHIP_OK;
@@ -152,17 +146,18 @@ static int tiles_chunk(nyxhip_ctx* ctx, const void* d_inten, int dtI, const void
     {
         ctx->win_next = WindowSrc{d_inten, d_label, dtI, dtL, W, H, R.tile, R.label, R.bbox_x0, R.bbox_y0, knob::no_xcd_swizzle() ? 0u : 1u};   // (A/B knob)
     }
-    // the box origins inside the tile: one tile is one image, so they are the reference's coordinates (the caliper classes read them)
-    if (neighbor_distance == kTilesReducerIh)
-        return ih_device(ctx, &b, s, d_out, d_ld, meta[3]);
-    if (neighbor_distance == kTilesReducerImq)
-        return imq_device(ctx, &b, s, d_out, d_ld, meta[4]);
-    if (neighbor_distance == kTilesReducerMorph)
-        return morph_device(ctx, &b, R.bbox_x0, R.bbox_y0, family_mask, s, d_out, d_ld, meta[3], meta[4], meta[6]);
-    if (neighbor_distance == kTilesReducerHexpoly)
-        return hexpoly_device(ctx, &b, R.bbox_x0, R.bbox_y0, nullptr, 0, R.tile, (int32_t)family_mask, s, d_out, d_ld, meta[3], meta[4], meta[6]);
-    if (neighbor_distance)
-        return neighbors_device(ctx, &b, R.bbox_x0, R.bbox_y0, nullptr, 0, R.tile, neighbor_distance, s, d_out, d_ld, meta[3], meta[4], meta[6]);
+    // the box origins inside the tile: one tile is one image, so they are the reference's coordinates (the caliper classes read them);
+    // the image-relating classes take the tile index as the image of a row
+    switch (red.kind) {
+    case TileReducer::Ih: return ih_device(ctx, &b, s, d_out, d_ld, meta[3]);
+    case TileReducer::Imq: return imq_device(ctx, &b, s, d_out, d_ld, meta[4]);
+    case TileReducer::Morph: return morph_device(ctx, &b, R.bbox_x0, R.bbox_y0, red.mask, s, d_out, d_ld, meta[3], meta[4], meta[6]);
+    case TileReducer::Hexpoly:
+        return hexpoly_device(ctx, &b, R.bbox_x0, R.bbox_y0, nullptr, 0, R.tile, red.pixel_distance, s, d_out, d_ld, meta[3], meta[4], meta[6]);
+    case TileReducer::Neighbors:
+        return neighbors_device(ctx, &b, R.bbox_x0, R.bbox_y0, nullptr, 0, R.tile, red.pixel_distance, s, d_out, d_ld, meta[3], meta[4], meta[6]);
+    case TileReducer::Families: break;
+    }
     OriginScope origins(ctx, R.bbox_x0, R.bbox_y0);
     int lrc = launch_device(ctx, &b, family_mask, s, d_out, d_ld, meta[3], meta[4], meta[5], meta[6]);
     ctx->win_next = WindowSrc{};
@@ -175,15 +170,32 @@ static int tiles_chunk(nyxhip_ctx* ctx, const void* d_inten, int dtI, const void
     return lrc;
 }
 
-static int tiles_validate(nyxhip_ctx* ctx, const nyxhip_tiles* t, uint32_t family_mask, const nyxhip_settings* s, uint64_t* n_roi_out, bool neighbors)
+// The column count of a reducer's rows.
+static int reducer_n_cols(const TileReducer& red, const nyxhip_settings* s)
 {
+    switch (red.kind) {
+    case TileReducer::Neighbors: return kNeighborCols;
+    case TileReducer::Ih: return kIhCols;
+    case TileReducer::Imq: return kImqCols;
+    case TileReducer::Morph: return morph_n_columns(red.mask);
+    case TileReducer::Hexpoly: return kHexpolyCols;
+    case TileReducer::Families: break;
+    }
+    return nyxhip_n_columns(red.mask, s);
+}
+
+static int tiles_validate(nyxhip_ctx* ctx, const nyxhip_tiles* t, const TileReducer& red, const nyxhip_settings* s, uint64_t* n_roi_out)
+{
+    // (a class with entries of its own has checked its mask or distance there, and no family's settings are read for it)
+    const bool families = red.kind == TileReducer::Families;
+    const uint32_t family_mask = families ? red.mask : 0u;
     if (!ctx) return NYXHIP_ERR_INVALID_ARG;
     if (!t || !s || !n_roi_out) return fail(ctx, NYXHIP_ERR_INVALID_ARG, "null tiles / settings / n_roi_out");
     if (t->n_tiles == 0) return fail(ctx, NYXHIP_ERR_INVALID_ARG, "n_tiles must be >= 1");
     if (!t->inten || !t->label || t->width == 0 || t->height == 0) return fail(ctx, NYXHIP_ERR_INVALID_ARG, "null pointer or empty tile");
     auto dt_ok = [](int d) { return d == NYXHIP_U8 || d == NYXHIP_U16 || d == NYXHIP_U32; };
     if (!dt_ok(t->inten_dtype) || !dt_ok(t->label_dtype)) return fail(ctx, NYXHIP_ERR_INVALID_ARG, "tile element types must be NYXHIP_U8 / U16 / U32");
-    if (!neighbors && (family_mask == 0 || (family_mask & ~kImplemented))) return fail(ctx, NYXHIP_ERR_INVALID_ARG, "bad family mask");
+    if (families && (family_mask == 0 || (family_mask & ~kImplemented))) return fail(ctx, NYXHIP_ERR_INVALID_ARG, "bad family mask");
     if (t->memory != NYXHIP_MEM_HOST && t->memory != NYXHIP_MEM_DEVICE && t->memory != NYXHIP_MEM_HOST_OWN_MAPPING) return fail(ctx, NYXHIP_ERR_INVALID_ARG, "bad memory kind");
     if (t->slide_mode < NYXHIP_SLIDE_MONTAGE || t->slide_mode > NYXHIP_SLIDE_GIVEN) return fail(ctx, NYXHIP_ERR_INVALID_ARG, "bad slide_mode");
     if (t->slide_mode == NYXHIP_SLIDE_GIVEN && (!t->slide_min || !t->slide_max)) return fail(ctx, NYXHIP_ERR_INVALID_ARG, "NYXHIP_SLIDE_GIVEN needs slide_min and slide_max");
@@ -327,14 +339,12 @@ struct HostPin {
 };
 
 // The whole stack in chunks.  label_limit: v1's max_label (validated only).  prepinned: the caller has pinned the arrays.
-static int tiles_run(nyxhip_ctx* ctx, const nyxhip_tiles* t, uint32_t family_mask, const nyxhip_settings* s, uint32_t* out_labels, uint32_t* out_tile_index,
-                     uint64_t max_rows, double* out_table, size_t out_ld, uint64_t* n_roi_out, uint32_t label_limit, uint32_t tile_index_base = 0,
-                     const HostPin* prepinned = nullptr, int32_t neighbor_distance = 0)
+static int tiles_run(nyxhip_ctx* ctx, const nyxhip_tiles* t, const TileReducer& red, const nyxhip_settings* s, uint32_t* out_labels, uint32_t* out_tile_index,
+                     uint64_t max_rows, double* out_table, size_t out_ld, uint64_t* n_roi_out, uint32_t label_limit, uint32_t tile_index_base,
+                     const HostPin* prepinned)
 {
-    // (a morphology mask or a pixel distance is no family mask: the entry has checked it, and no family's settings are read)
-    const bool slot_is_mask = neighbor_distance != kTilesReducerMorph && neighbor_distance != kTilesReducerHexpoly;
-    if (int vrc = tiles_validate(ctx, t, slot_is_mask ? family_mask : 0u, s, n_roi_out, neighbor_distance != 0)) return vrc;
-    const int n_cols = neighbor_distance == kTilesReducerHexpoly ? kHexpolyCols : neighbor_distance == kTilesReducerMorph ? morph_n_columns(family_mask) : neighbor_distance == kTilesReducerIh ? kIhCols : neighbor_distance == kTilesReducerImq ? kImqCols : neighbor_distance ? kNeighborCols : nyxhip_n_columns(family_mask, s);
+    if (int vrc = tiles_validate(ctx, t, red, s, n_roi_out)) return vrc;
+    const int n_cols = reducer_n_cols(red, s);
     const bool host = t->memory == NYXHIP_MEM_HOST || t->memory == NYXHIP_MEM_HOST_OWN_MAPPING;
     const bool keep = host && out_table == nullptr;                  // result stays in the context (nyxhip_fetch_result)
     if (!keep && (!out_labels || !out_table)) return fail(ctx, NYXHIP_ERR_INVALID_ARG, "null output pointers");
@@ -387,9 +397,8 @@ static int tiles_run(nyxhip_ctx* ctx, const nyxhip_tiles* t, uint32_t family_mas
             const uint64_t room = rows_done < max_rows ? max_rows - rows_done : 0;
             uint64_t n = 0;
             int rc = tiles_chunk(ctx, di, t->inten_dtype, dl, t->label_dtype, W, H, nt, t->slide_mode, t->slide_min ? t->slide_min + t0 : nullptr,
-                                 t->slide_max ? t->slide_max + t0 : nullptr, family_mask, s, short_out ? 0 : room, out_labels + rows_done,
-                                 out_tile_index ? out_tile_index + rows_done : nullptr, (uint32_t)t0, out_table + rows_done * out_ld, out_ld, label_limit, &n, st,
-                                 neighbor_distance);
+                                 t->slide_max ? t->slide_max + t0 : nullptr, red, s, short_out ? 0 : room, out_labels + rows_done,
+                                 out_tile_index ? out_tile_index + rows_done : nullptr, (uint32_t)t0, out_table + rows_done * out_ld, out_ld, label_limit, &n, st);
             if (rc) return rc;
             if (n > room) short_out = true;
             rows_done += n;
@@ -454,8 +463,8 @@ static int tiles_run(nyxhip_ctx* ctx, const nyxhip_tiles* t, uint32_t family_mas
                 d_til = d_lab + cap_rows;
             }
             rc = tiles_chunk(ctx, slot_inten(k), t->inten_dtype, slot_label(k, nt), t->label_dtype, W, H, nt, t->slide_mode,
-                             t->slide_min ? t->slide_min + t0 : nullptr, t->slide_max ? t->slide_max + t0 : nullptr, family_mask, s, cap_rows, d_lab, d_til,
-                             tile_index_base + (uint32_t)t0, d_out, (size_t)n_cols, label_limit, &n, st, neighbor_distance);
+                             t->slide_min ? t->slide_min + t0 : nullptr, t->slide_max ? t->slide_max + t0 : nullptr, red, s, cap_rows, d_lab, d_til,
+                             tile_index_base + (uint32_t)t0, d_out, (size_t)n_cols, label_limit, &n, st);
             if (rc) return rc;
             if (n > cap_rows) { HIP_TRY(ctx, hipStreamSynchronize(st)); need = (size_t)n * (8 * (size_t)n_cols + 8) + 4096; continue; }
             HIP_TRY(ctx, hipEventRecord(ctx->slot_free[k], st));
@@ -490,17 +499,15 @@ static int tiles_run(nyxhip_ctx* ctx, const nyxhip_tiles* t, uint32_t family_mas
 int nyxhip_featurize_tiles_v2(nyxhip_ctx* ctx, const nyxhip_tiles* tiles, uint32_t family_mask, const nyxhip_settings* s, uint32_t* out_labels,
                               uint32_t* out_tile_index, uint64_t max_rows, double* out_table, size_t out_ld, uint64_t* n_roi_out)
 {
-    return tiles_run(ctx, tiles, family_mask, s, out_labels, out_tile_index, max_rows, out_table, out_ld, n_roi_out, 0xFFFFFFFFu);
+    return tiles_run(ctx, tiles, {TileReducer::Families, family_mask, 0}, s, out_labels, out_tile_index, max_rows, out_table, out_ld, n_roi_out, 0xFFFFFFFFu, 0, nullptr);
 }
 
 int nyxhip_neighbors_tiles(nyxhip_ctx* ctx, const nyxhip_tiles* tiles, int32_t pixel_distance, const nyxhip_settings* s, uint32_t* out_labels,
                            uint32_t* out_tile_index, uint64_t max_rows, double* out_table, size_t out_ld, uint64_t* n_roi_out)
 {
     if (!ctx) return NYXHIP_ERR_INVALID_ARG;
-    if (pixel_distance <= 0) return fail(ctx, NYXHIP_ERR_INVALID_ARG, "pixel_distance must be greater than zero");
-    if (pixel_distance > kNbMaxDistance)
-        return fail(ctx, NYXHIP_ERR_UNSUPPORTED, "pixel_distance beyond 46340: its square overflows the reference's int (neighbors.cpp:242)");
-    return tiles_run(ctx, tiles, 0, s, out_labels, out_tile_index, max_rows, out_table, out_ld, n_roi_out, 0xFFFFFFFFu, 0, nullptr, pixel_distance);
+    if (int rc = pixel_distance_check(ctx, pixel_distance)) return rc;
+    return tiles_run(ctx, tiles, {TileReducer::Neighbors, 0, pixel_distance}, s, out_labels, out_tile_index, max_rows, out_table, out_ld, n_roi_out, 0xFFFFFFFFu, 0, nullptr);
 }
 
 int nyxhip_ih_tiles(nyxhip_ctx* ctx, const nyxhip_tiles* tiles, const nyxhip_settings* s, uint32_t* out_labels, uint32_t* out_tile_index, uint64_t max_rows,
@@ -509,14 +516,14 @@ int nyxhip_ih_tiles(nyxhip_ctx* ctx, const nyxhip_tiles* tiles, const nyxhip_set
     if (!ctx) return NYXHIP_ERR_INVALID_ARG;
     if (!s) return fail(ctx, NYXHIP_ERR_INVALID_ARG, "null tiles / settings / n_roi_out");
     if (int rc = ih_settings_check(ctx, s)) return rc;
-    return tiles_run(ctx, tiles, 0, s, out_labels, out_tile_index, max_rows, out_table, out_ld, n_roi_out, 0xFFFFFFFFu, 0, nullptr, kTilesReducerIh);
+    return tiles_run(ctx, tiles, {TileReducer::Ih, 0, 0}, s, out_labels, out_tile_index, max_rows, out_table, out_ld, n_roi_out, 0xFFFFFFFFu, 0, nullptr);
 }
 
 int nyxhip_imq_tiles(nyxhip_ctx* ctx, const nyxhip_tiles* tiles, const nyxhip_settings* s, uint32_t* out_labels, uint32_t* out_tile_index, uint64_t max_rows,
                      double* out_table, size_t out_ld, uint64_t* n_roi_out)
 {
     if (!ctx) return NYXHIP_ERR_INVALID_ARG;
-    const int rc = tiles_run(ctx, tiles, 0, s, out_labels, out_tile_index, max_rows, out_table, out_ld, n_roi_out, 0xFFFFFFFFu, 0, nullptr, kTilesReducerImq);
+    const int rc = tiles_run(ctx, tiles, {TileReducer::Imq, 0, 0}, s, out_labels, out_tile_index, max_rows, out_table, out_ld, n_roi_out, 0xFFFFFFFFu, 0, nullptr);
     return rc == NYXHIP_ERR_UNSUPPORTED ? fail(ctx, rc, kImqWidthMessage) : rc;
 }
 
@@ -525,18 +532,15 @@ int nyxhip_morph_tiles(nyxhip_ctx* ctx, const nyxhip_tiles* tiles, uint32_t morp
 {
     if (!ctx) return NYXHIP_ERR_INVALID_ARG;
     if (nyxhip_morph_n_columns(morph_mask) < 0) return fail(ctx, NYXHIP_ERR_INVALID_ARG, "bad morphology mask");
-    return tiles_run(ctx, tiles, morph_mask, s, out_labels, out_tile_index, max_rows, out_table, out_ld, n_roi_out, 0xFFFFFFFFu, 0, nullptr, kTilesReducerMorph);
+    return tiles_run(ctx, tiles, {TileReducer::Morph, morph_mask, 0}, s, out_labels, out_tile_index, max_rows, out_table, out_ld, n_roi_out, 0xFFFFFFFFu, 0, nullptr);
 }
 
 int nyxhip_hexpoly_tiles(nyxhip_ctx* ctx, const nyxhip_tiles* tiles, int32_t pixel_distance, const nyxhip_settings* s, uint32_t* out_labels,
                          uint32_t* out_tile_index, uint64_t max_rows, double* out_table, size_t out_ld, uint64_t* n_roi_out)
 {
     if (!ctx) return NYXHIP_ERR_INVALID_ARG;
-    if (pixel_distance <= 0) return fail(ctx, NYXHIP_ERR_INVALID_ARG, "pixel_distance must be greater than zero");
-    if (pixel_distance > kNbMaxDistance)
-        return fail(ctx, NYXHIP_ERR_UNSUPPORTED, "pixel_distance beyond 46340: its square overflows the reference's int (neighbors.cpp:242)");
-    return tiles_run(ctx, tiles, (uint32_t)pixel_distance, s, out_labels, out_tile_index, max_rows, out_table, out_ld, n_roi_out, 0xFFFFFFFFu, 0, nullptr,
-                     kTilesReducerHexpoly);
+    if (int rc = pixel_distance_check(ctx, pixel_distance)) return rc;
+    return tiles_run(ctx, tiles, {TileReducer::Hexpoly, 0, pixel_distance}, s, out_labels, out_tile_index, max_rows, out_table, out_ld, n_roi_out, 0xFFFFFFFFu, 0, nullptr);
 }
 
 int nyxhip_fetch_result(nyxhip_ctx* ctx, uint32_t* out_labels, uint32_t* out_tile_index, double* out_table, size_t out_ld)
@@ -591,7 +595,7 @@ int nyxhip_featurize_tiles_sharded(nyxhip_ctx* const* ctxs, int n_ctx, const nyx
             if (tiles->slide_min) part.slide_min = tiles->slide_min + lo[g];
             if (tiles->slide_max) part.slide_max = tiles->slide_max + lo[g];
             if (part.n_tiles == 0) { rcs[g] = 0; return; }
-            rcs[g] = tiles_run(ctxs[g], &part, family_mask, s, nullptr, nullptr, 0, nullptr, 0, &cnt[g], 0xFFFFFFFFu, (uint32_t)lo[g], &pin);   // tile indices of the whole stack
+            rcs[g] = tiles_run(ctxs[g], &part, {TileReducer::Families, family_mask, 0}, s, nullptr, nullptr, 0, nullptr, 0, &cnt[g], 0xFFFFFFFFu, (uint32_t)lo[g], &pin);   // tile indices of the whole stack
         });
     for (auto& t : th) t.join();
     for (int g = 0; g < G; g++)
@@ -642,7 +646,7 @@ int nyxhip_featurize_tiles(nyxhip_ctx* ctx, const uint32_t* inten, const uint32_
     memset(&t, 0, sizeof(t));
     t.inten = inten; t.label = label; t.inten_dtype = NYXHIP_U32; t.label_dtype = NYXHIP_U32;
     t.width = width; t.height = height; t.n_tiles = n_tiles; t.memory = memory; t.slide_mode = NYXHIP_SLIDE_MONTAGE;
-    return tiles_run(ctx, &t, family_mask, s, out_labels, out_tile_index, max_rows, out_table, out_ld, n_roi_out, max_label);
+    return tiles_run(ctx, &t, {TileReducer::Families, family_mask, 0}, s, out_labels, out_tile_index, max_rows, out_table, out_ld, n_roi_out, max_label, 0, nullptr);
 }
 
 } // extern "C"
