@@ -336,13 +336,76 @@ __device__ __forceinline__ void glcm_features_wave16(const uint32_t* Pslots, int
 // glcm_features_wave16; only the grouping of the lane sums differs (1e-15 level).
 __device__ __forceinline__ uint32_t grp8_sum(uint32_t v) { v += dpp_perm<0xB1>(v); v += dpp_perm<0x4E>(v); v += dpp_perm<0x141>(v); return v; }
 __device__ __forceinline__ double grp8_sum(double v) { v += dpp_perm<0xB1>(v); v += dpp_perm<0x4E>(v); v += dpp_perm<0x141>(v); return v; }
+//
+// O8, the fixed-order form (order 8, four angles: every live ROI of a four-angle call at grey depth 8): nothing of the marginals and the
+// cell pass depends on run-time bounds, so the loops, the `l < Ng` tests and the RowCol walker go.  Lane l of a group owns column l: its
+// column sum is eight reads at constant offsets (P[u][l]; the cell pass reads them again -- eight registers held across it cost the
+// kernel spills, a read at a constant offset no vector instruction), its row sum one 32-byte read; the two diagonal families come from
+// WRAPPED reads, one element of every row each:
+//   |x - y|:  P[x][(x - l) & 7], x = 0..7.  Rows x >= l lie on the lower diagonal l (sum A_l), the others on the upper diagonal 8 - l
+//             (sum B_l; B_0 = 0).  dc_l = A_l + B_{8 - l}: the partner comes through row_half_mirror (B_{7 - l}) and a shift by one lane --
+//             lane 0 of a DPP row receives 0, lane 8 the lower group's B_0 = 0, so l = 0 needs no select, and l = 4 is its own partner.
+//   x + y:    P[x][(l - x) & 7].  Rows x <= l belong to k = l, the others to k = l + 8 (k = 15 never occurs): both sums of the lane from
+//             one pass, no cross-lane step.
+// Which rows wrap depends on l alone, so every predicate is a constant lane mask in scalar registers (lanes_l_above / lanes_l_below).
+// Integers are exact in any order and every double is formed and summed as in the general form: the same bits.  A dead half of the wave
+// (order 0) computes on whatever its count block holds and never stores, as idle groups do.
+__device__ __forceinline__ bool lanes_l_above(int x)   // l > x, l = lane & 7
+{
+    return __builtin_amdgcn_inverse_ballot_w64(((0xFFull << (x + 1)) & 0xFFull) * 0x0101010101010101ull);
+}
+__device__ __forceinline__ bool lanes_l_below(int x)   // l < x
+{
+    return __builtin_amdgcn_inverse_ballot_w64(((1ull << x) - 1ull) * 0x0101010101010101ull);
+}
+__device__ __forceinline__ void glcm_marginal_counts_o8(const uint32_t* P, int l, uint32_t& cc, uint32_t& rc, uint32_t& dc, uint32_t (&ac)[2])
+{
+    cc = 0;
+#pragma unroll
+    for (int u = 0; u < 8; u++) cc += P[8 * u + l];
+    const uint4 r0 = ((const uint4*)(P + 8 * l))[0], r1 = ((const uint4*)(P + 8 * l))[1];
+    rc = ((r0.x + r0.y) + (r0.z + r0.w)) + ((r1.x + r1.y) + (r1.z + r1.w));
+    // row x at word 9 x - l (+ 8 where it wraps, l > x); row 0 apart, so that both bases stay inside the count block
+    const uint32_t* d_lo = P + 9 - l;
+    const uint32_t* d_hi = d_lo + 8;
+    const uint32_t d0 = P[(8 - l) & 7];
+    uint32_t tot = d0, up = lanes_l_above(0) ? d0 : 0u;
+#pragma unroll
+    for (int x = 1; x < 8; x++) {
+        const bool wrap = x < 7 && lanes_l_above(x);
+        const uint32_t d = (wrap ? d_hi : d_lo)[9 * (x - 1)];
+        tot += d;
+        if (x < 7) up += wrap ? d : 0u;
+    }
+    dc = (tot - up) + dpp_perm<0x111>(dpp_perm<0x141>(up));          // row_half_mirror, then row_shr:1 (bound_ctrl: 0 into lane 0)
+    // row x at word 7 x + l (+ 8 where it wraps, l < x)
+    const uint32_t* a_lo = P + l;
+    const uint32_t* a_hi = a_lo + 8;
+    uint32_t atot = 0, ahi = 0;
+#pragma unroll
+    for (int x = 0; x < 8; x++) {
+        const bool wrap = x > 0 && lanes_l_below(x);
+        const uint32_t a = (wrap ? a_hi : a_lo)[7 * x];
+        atot += a;
+        if (x > 0) ahi += wrap ? a : 0u;
+    }
+    ac[0] = atot - ahi;
+    ac[1] = ahi;
+}
+
+#ifndef NYX_G8_O8_PARTS
+#define NYX_G8_O8_PARTS 3
+#endif
+template <bool O8>
 __device__ __forceinline__ void glcm_features_wave8(const uint32_t* P_a, const uint32_t* P_b, int n_slots, int Ng_a, int Ng_b, double* scr_base, int scr_stride,
                                                     double soft_nan, double* fslots, size_t f_gap, double* sums, int lane)
 {
+    // (diagnostic builds: -DNYX_G8_O8_PARTS=1 fixes the marginals alone, =2 the cell pass alone)
+    constexpr bool O8M = O8 && (NYX_G8_O8_PARTS & 1), O8C = O8 && (NYX_G8_O8_PARTS & 2);
     const int grp = lane >> 3, l = lane & 7, sel = grp >> 2, slot_raw = grp & 3;
-    const int Ng = sel ? Ng_b : Ng_a;
+    const int Ng_roi = sel ? Ng_b : Ng_a, Ng = O8 ? 8 : Ng_roi;
     const int NN = Ng * Ng;
-    const bool live = slot_raw < n_slots && Ng != 0;
+    const bool live = slot_raw < n_slots && Ng_roi != 0;
     const int slot = slot_raw < n_slots ? slot_raw : 0;            // idle groups shadow slot 0 of their ROI and never store
     const uint32_t* P = (sel ? P_b : P_a) + mul24((uint32_t)slot, (uint32_t)NN);
     const int gslot = sel * kMaxAngles + slot;
@@ -353,7 +416,10 @@ __device__ __forceinline__ void glcm_features_wave8(const uint32_t* P_a, const u
 
     // ---- marginal counts: lane i < Ng owns column i, row i and the diagonal pair |x - y| = i
     uint32_t cc = 0, rc = 0, dc = 0;
-    if (l < Ng) {
+    uint32_t ac8[2];                                               // (O8: the lane's two anti-diagonal counts)
+    if constexpr (O8M) {
+        glcm_marginal_counts_o8(P, l, cc, rc, dc, ac8);
+    } else if (l < Ng) {
         const uint32_t lN = mul24((uint32_t)l, (uint32_t)Ng);
         uint32_t ic = (uint32_t)l;
 #pragma unroll 1
@@ -382,12 +448,16 @@ __device__ __forceinline__ void glcm_features_wave8(const uint32_t* P_a, const u
 #pragma unroll
     for (int u = 0; u < 2; u++) {
         const int k = l + 8 * u;
-        if (k < 2 * Ng - 1) {
+        if (k < 2 * Ng - 1) {                                      // (O8: k != 15)
             uint32_t c = 0;
-            const int x0 = k - (Ng - 1) > 0 ? k - (Ng - 1) : 0, x1 = k < Ng - 1 ? k : Ng - 1;
-            uint32_t ix = mad24((uint32_t)x0, (uint32_t)Ng, (uint32_t)(k - x0));
+            if constexpr (O8M) {
+                c = ac8[u];
+            } else {
+                const int x0 = k - (Ng - 1) > 0 ? k - (Ng - 1) : 0, x1 = k < Ng - 1 ? k : Ng - 1;
+                uint32_t ix = mad24((uint32_t)x0, (uint32_t)Ng, (uint32_t)(k - x0));
 #pragma unroll 1
-            for (int x = x0; x <= x1; x++, ix += (uint32_t)Ng - 1u) c += P[ix];
+                for (int x = x0; x <= x1; x++, ix += (uint32_t)Ng - 1u) c += P[ix];
+            }
             pxpy[u] = fdiv((double)c, sum_p);
         }
     }
@@ -401,7 +471,34 @@ __device__ __forceinline__ void glcm_features_wave8(const uint32_t* P_a, const u
     double ent = 0, hxy1 = 0, hxy2 = 0, asm_d = 0;
     uint32_t acor_i = 0, asm_i = 0, cmax = 0;
     const bool big = csum >= 65536u;
-    {
+    if constexpr (O8C) {                                             // cell u of the lane is (row u, column l): pcol is the lane's own
+        const uint32_t* Pl = P + l;
+        // the double form of ASM in a pass of its own, in front (same terms, same order): a branch per cell splits the pass into blocks,
+        // and the compiler then gathers the float work of all eight cells behind them, every cell's operands live at once
+        if (big) {
+#pragma unroll
+            for (int u = 0; u < 8; u++) {
+                const double p = (double)Pl[8 * u] * inv_sum_p;
+                asm_d = __builtin_fma(p, p, asm_d);
+            }
+        }
+        uint32_t wgt = l1;                                           // (u + 1)(l + 1)
+#pragma unroll
+        for (int u = 0; u < 8; u++) {
+            const uint32_t cnt = Pl[8 * u];
+            const double p = (double)cnt * inv_sum_p;
+            asm_i = mad24(cnt, cnt, asm_i);                          // (wraps where `big`: not read then)
+            acor_i = mad24(cnt, wgt, acor_i);
+            wgt += l1;
+            cmax = cnt > cmax ? cnt : cmax;
+            ent = __builtin_fma(p, (double)fast_log2f(p + 0.000000001), ent);
+            const double pp = pcol * prow_s[u];
+            const double lg = (double)fast_log2f(pp + 0.000000001);
+            hxy1 = __builtin_fma(p, lg, hxy1);
+            hxy2 = __builtin_fma(pp, lg, hxy2);
+            __builtin_amdgcn_sched_barrier(0);                       // a cell at a time: eight cells in flight cost registers the kernel does not have
+        }
+    } else {
         RowCol rcw((uint32_t)l, 8u, (uint32_t)(Ng ? Ng : 1), RowCol::small_t{});
         for (int e = l; e < NN; e += 8, rcw.advance()) {
             const uint32_t r = rcw.row, c = rcw.col, cnt = P[e];
@@ -3036,7 +3133,12 @@ __global__ __launch_bounds__(kBlock, 8) void glcm_features_kernel8(const RoiArgs
     }
     wav_sync<false>();
     // (group g = ROI g >> 2, angle g & 3 writes f = fslots + g * 32 doubles: the ROI's own count block)
-    glcm_features_wave8(s_P[0], s_P[1], na, Ng[0], Ng[1], s_scr, 16, A.soft_nan, (double*)base, (size_t)(cnt_bytes >> 3) - 4 * 32, s_sum, lane);
+    // four angles and both orders 0 or 8 (one of them is 8 here): the fixed-order form.  The orders are facts of the ROIs, read per wave:
+    // depths 2..7, fewer angles and producers that take the order from the data run the general form beside it in the same launch.
+    if (na != 4 || ((Ng[0] | Ng[1]) & ~8) != 0)
+        glcm_features_wave8<false>(s_P[0], s_P[1], na, Ng[0], Ng[1], s_scr, 16, A.soft_nan, (double*)base, (size_t)(cnt_bytes >> 3) - 4 * 32, s_sum, lane);
+    else
+        glcm_features_wave8<true>(s_P[0], s_P[1], 4, Ng[0], Ng[1], s_scr, 16, A.soft_nan, (double*)base, (size_t)(cnt_bytes >> 3) - 4 * 32, s_sum, lane);
     wav_sync<false>();
     const int sh = na == 4 ? 2 : na == 2 ? 1 : na == 1 ? 0 : -1;
 #pragma unroll
