@@ -704,6 +704,42 @@ int nyxhip_vshape_column_name(uint32_t shape_mask, int col, char* buf, size_t bu
 int nyxhip_featurize_volumes_shape(nyxhip_ctx* ctx, const nyxhip_batch3d* batch, uint32_t shape_mask, const nyxhip_settings* s,
                                    double* out_table, size_t out_ld);
 
+/* ---- volumes (3-D): the label scan on the device ------------------------------
+ * The step in front of the five volume entries: a stack of intensity / label volumes -> the nyxhip_batch3d of its ROIs, assembled on the
+ * device (the 3-D counterpart of the label scan inside nyxhip_featurize_tiles_v2).
+ *
+ * ROWS.  One ROI per (volume, non-zero label value), in (volume, ascending label) order: the same label in two volumes makes two ROIs.
+ * The box is the tight bounding box of the label's voxels, coordinates are relative to its corner, the voxels of an ROI stand in raster
+ * order (z, then y, then x).  Voxels of intensity 0 under a label are included.  min_inten / max_inten are taken over the ROI's voxels.
+ * Labels are any non-zero value of the label type: nothing is sized by the label magnitude.
+ *
+ * out_batch is a DEVICE batch (memory == NYXHIP_MEM_DEVICE, every pointer filled, slide_min / slide_max NULL, max_device_bytes copied from
+ * `v`) that the CONTEXT owns: it stays valid until the next nyxhip_assemble_volumes (a refused one too), nyxhip_release_volumes or
+ * nyxhip_destroy on the context and can be passed unchanged to any of the five volume entries with a device table.  The stated extrema max_px,
+ * max_bbox_cells (saturating at 2^32 - 1; the entries refuse such boxes themselves) and max_inten_range are filled exactly.
+ * out_volume_index (may be NULL) receives a device array [n_roi]: the volume of every row.  A stack without any label is NYXHIP_OK with
+ * n_roi == 0 and NULL arrays.  Synchronous.
+ *
+ * LIMITS, checked before anything is launched where that is possible; none gives a wrong row.  NULL ctx / v / out_batch / inten / label,
+ * an unknown dtype or memory kind, a zero side or n_volumes: NYXHIP_ERR_INVALID_ARG.  A side above 65534: NYXHIP_ERR_ROI_TOO_LARGE.
+ * width * height * depth >= 2^32: NYXHIP_ERR_UNSUPPORTED.  One volume that does not fit max_device_bytes with its label table:
+ * NYXHIP_ERR_ROI_TOO_LARGE.  More than 2^24 labels in one volume, or more than 2^31 - 1 ROIs in the stack: NYXHIP_ERR_UNSUPPORTED. */
+typedef struct nyxhip_volumes {
+    const void* inten;            /* [n_volumes][depth][height][width] of inten_dtype            */
+    const void* label;            /* same shape, label_dtype; 0 = no ROI                          */
+    int32_t inten_dtype, label_dtype;      /* NYXHIP_U8 | NYXHIP_U16 | NYXHIP_U32               */
+    uint32_t width, height, depth, n_volumes;
+    int32_t memory;               /* NYXHIP_MEM_HOST | NYXHIP_MEM_DEVICE: where inten / label live */
+    uint64_t max_device_bytes;    /* staging + scan workspace budget; 0 = half of free device memory */
+} nyxhip_volumes;
+
+int nyxhip_assemble_volumes(nyxhip_ctx* ctx, const nyxhip_volumes* v, nyxhip_batch3d* out_batch,
+                            const uint32_t** out_volume_index /* device [n_roi], may be NULL */);
+/* Host copies of the labels and volume indices of the assembled batch (either may be NULL); max_rows < n_roi: NYXHIP_ERR_INVALID_ARG. */
+int nyxhip_assembled_rows(nyxhip_ctx* ctx, uint32_t* out_labels, uint32_t* out_volume_index, uint64_t max_rows);
+/* Frees the assembled batch and the workspaces of the scan. */
+int nyxhip_release_volumes(nyxhip_ctx* ctx);
+
 /* ---- 2-D morphology: basic morphology, contour, convex hull, extrema -------------------
  * Four classes of the reference's 2-D shape block (featureset.h:46-60, :71-82, :136-143), 41 columns:
  *   NYXHIP_MORPH_BASIC    BasicMorphologyFeatures (features/basic_morphology.cpp:19-92): AREA_PIXELS_COUNT, AREA_UM2, CENTROID_X,

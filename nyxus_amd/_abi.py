@@ -354,6 +354,37 @@ class Batch3D(C.Structure):
     ]
 
 
+class Volumes(C.Structure):
+    """``nyxhip_volumes`` (include/nyxhip.h)."""
+
+    _fields_ = [
+        ("inten", C.c_void_p),
+        ("label", C.c_void_p),
+        ("inten_dtype", C.c_int32),
+        ("label_dtype", C.c_int32),
+        ("width", C.c_uint32),
+        ("height", C.c_uint32),
+        ("depth", C.c_uint32),
+        ("n_volumes", C.c_uint32),
+        ("memory", C.c_int32),
+        ("max_device_bytes", C.c_uint64),
+    ]
+
+
+def volume_dtype(dt) -> int:
+    """The element type (U8 / U16 / U32) of a NumPy dtype of the volume scan."""
+    dt = np.dtype(dt)
+    if dt.kind != "u" or dt.itemsize not in (1, 2, 4):
+        raise ValueError(f"volumes must be uint8, uint16 or uint32 arrays, not {dt}")
+    return dt.itemsize
+
+
+def volumes_struct(inten_ptr: int, inten_dtype: int, label_ptr: int, label_dtype: int, shape, memory: int, max_device_bytes: int = 0) -> Volumes:
+    """A ``nyxhip_volumes`` over two contiguous [n, z, y, x] arrays."""
+    n, d, h, w = (int(k) for k in shape)
+    return Volumes(inten_ptr, label_ptr, int(inten_dtype), int(label_dtype), w, h, d, n, int(memory), int(max_device_bytes))
+
+
 @dataclass
 class HostBatch3D:
     """A host-memory batch of volumetric ROIs: keeps the NumPy arrays alive next to the C struct."""

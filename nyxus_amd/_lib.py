@@ -10,7 +10,7 @@ import ctypes as C
 import os
 import sys
 import weakref
-from typing import List, Optional
+from typing import List, NamedTuple, Optional
 
 import numpy as np
 
@@ -39,6 +39,7 @@ ABI_SYMBOLS = [
     "nyxhip_vshape_n_columns", "nyxhip_vshape_column_name", "nyxhip_featurize_volumes_shape",
     "nyxhip_morph_n_columns", "nyxhip_morph_column_name", "nyxhip_morph_batch", "nyxhip_morph_tiles",
     "nyxhip_hexpoly_column_name", "nyxhip_hexpoly_batch", "nyxhip_hexpoly_tiles",
+    "nyxhip_assemble_volumes", "nyxhip_assembled_rows", "nyxhip_release_volumes",
 ]
 
 
@@ -181,7 +182,14 @@ def load() -> C.CDLL:
         lib.nyxhip_vshape_column_name.restype = C.c_int
         lib.nyxhip_featurize_volumes_shape.argtypes = [C.c_void_p, P(_abi.Batch3D), C.c_uint32, P(_abi.Settings), C.c_void_p, C.c_size_t]
         lib.nyxhip_featurize_volumes_shape.restype = C.c_int
-    if hasattr(lib, "nyxhip_morph_batch"):       # (absent from older builds of the ABI selected through NYXHIP_LIB for A/B runs)
+    if hasattr(lib, "nyxhip_assemble_volumes"):
+        lib.nyxhip_assemble_volumes.argtypes = [C.c_void_p, P(_abi.Volumes), P(_abi.Batch3D), P(C.c_void_p)]
+        lib.nyxhip_assemble_volumes.restype = C.c_int
+        lib.nyxhip_assembled_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]
+        lib.nyxhip_assembled_rows.restype = C.c_int
+        lib.nyxhip_release_volumes.argtypes = [C.c_void_p]
+        lib.nyxhip_release_volumes.restype = C.c_int
+    if hasattr(lib, "nyxhip_morph_batch"):      # (absent from older builds of the ABI selected through NYXHIP_LIB for A/B runs)
         lib.nyxhip_morph_n_columns.argtypes = [C.c_uint32]
         lib.nyxhip_morph_n_columns.restype = C.c_int
         lib.nyxhip_morph_column_name.argtypes = [C.c_uint32, C.c_int, C.c_char_p, C.c_size_t]
@@ -298,6 +306,16 @@ def _close_live_contexts():
 
 
 atexit.register(_close_live_contexts)
+
+
+class AssembledVolumes(NamedTuple):
+    """What Context.assemble_volumes_* returns: the device batch (valid until the context's next assemble / release_volumes / close), its
+    row count, host copies of the rows' labels and volume indices, and the device pointer of the volume indices (None: no rows)."""
+    batch: _abi.Batch3D
+    n_roi: int
+    labels: np.ndarray
+    volume_index: np.ndarray
+    volume_index_ptr: Optional[int]
 
 
 class Context:
@@ -523,6 +541,32 @@ class Context:
     def volumes_shape_device(self, cb: _abi.Batch3D, smask: int, s: _abi.Settings, out_ptr: int, ld: int):
         """Device pointers in ``cb`` and a device table; synchronous (nyxhip_featurize_volumes_shape)."""
         self._check(self._lib.nyxhip_featurize_volumes_shape(self._h, C.byref(cb), smask, C.byref(s), C.c_void_p(out_ptr), ld))
+
+    def _assembled(self, vols: _abi.Volumes) -> "AssembledVolumes":
+        cb, vi = _abi.Batch3D(), C.c_void_p()
+        self._check(self._lib.nyxhip_assemble_volumes(self._h, C.byref(vols), C.byref(cb), C.byref(vi)))
+        n = int(cb.n_roi)
+        labels, vol = np.empty(n, np.uint32), np.empty(n, np.uint32)
+        self._check(self._lib.nyxhip_assembled_rows(self._h, labels.ctypes.data, vol.ctypes.data, n))
+        return AssembledVolumes(cb, n, labels, vol, vi.value)
+
+    def assemble_volumes_host(self, inten: np.ndarray, label: np.ndarray, max_device_bytes: int = 0) -> "AssembledVolumes":
+        """The ROIs of host volumes [n, z, y, x] (uint8 / uint16 / uint32 each) as a device batch the context owns until the next
+        assemble, release_volumes() or close() (nyxhip_assemble_volumes): rows in (volume, label) order."""
+        if inten.ndim != 4 or inten.shape != label.shape:
+            raise ValueError("inten and label must be [n, z, y, x] arrays of one shape")
+        inten, label = np.ascontiguousarray(inten), np.ascontiguousarray(label)
+        return self._assembled(_abi.volumes_struct(inten.ctypes.data, _abi.volume_dtype(inten.dtype), label.ctypes.data, _abi.volume_dtype(label.dtype),
+                                                   inten.shape, _abi.MEM_HOST, max_device_bytes))
+
+    def assemble_volumes_device(self, inten_ptr: int, inten_dtype: int, label_ptr: int, label_dtype: int, shape, max_device_bytes: int = 0) -> "AssembledVolumes":
+        """As assemble_volumes_host for volumes that lie in device memory: the pointers and element types (U8 / U16 / U32) of two contiguous
+        [n, z, y, x] arrays, for example torch tensors' data_ptr()."""
+        return self._assembled(_abi.volumes_struct(inten_ptr, inten_dtype, label_ptr, label_dtype, shape, _abi.MEM_DEVICE, max_device_bytes))
+
+    def release_volumes(self):
+        """Frees the assembled batch and the workspaces of the scan (nyxhip_release_volumes)."""
+        self._check(self._lib.nyxhip_release_volumes(self._h))
 
     def imq_host(self, batch: _abi.HostBatch, s: _abi.Settings) -> np.ndarray:
         """The image-quality columns [n_roi x 4] of a host batch (nyxhip_imq_batch); NaN / inf are left in place."""

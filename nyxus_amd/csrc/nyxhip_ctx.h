@@ -13,6 +13,7 @@
 //   nyxhip_morph.hip     the 2-D morphology entries: column catalogue of a morphology mask, the launches over a device-resident batch, nyxhip_morph_batch
 //   nyxhip_hexpoly.hip   the hexagonality / polygonality entries: column names, one contour chain for three producers and the closing kernel, nyxhip_hexpoly_batch
 //   nyxhip_vol.hip       the volume entries: column catalogue of the volume mask, chunks under the budget, nyxhip_featurize_volumes
+//   nyxhip_volscan.hip   the device label scan for volumes: nyxhip_assemble_volumes, nyxhip_assembled_rows, nyxhip_release_volumes (vol_assembly.hip)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -130,6 +131,22 @@ struct DenseSrc {              // whole-slide mode: the dense images the next ru
 };
 constexpr int NYXHIP_INTERNAL_NEEDS_CLOUDS = -1000;   // run_class: a launch group of a window-mode call needs the materialised clouds
 
+// nyxhip_assemble_volumes (nyxhip_volscan.hip): the assembled batch, which the context owns until the next nyxhip_assemble_volumes,
+// nyxhip_release_volumes or nyxhip_destroy, and the grow-only workspaces of the scan.
+struct VolScanBufs {
+    DevBuf rows;                       // the batch's per-ROI arrays: volume index, label, voxel count, box origin, box, extrema | px_offset
+    DevBuf cloud;                      // x | y | z | inten
+    DevBuf table;                      // the label tables of a chunk | occupied slots per block; later the hits per slab of the cloud launch
+    DevBuf unsorted;                   // the rows in slot order
+    DevBuf sort;                       // keys and indices of the row sort (two of each), digit counts, slabs per row, block sums, slab offsets
+    DevBuf stage;                      // a chunk of host volumes
+    DevBuf meta;                       // VS_META_WORDS words (volscan_plan.h)
+    nyxhip_batch3d batch = {};
+    const uint32_t* volume_index = nullptr;
+    uint32_t cap_hint = 0;             // per-volume table size that served the last call
+    bool valid = false;
+};
+
 struct nyxhip_ctx {
     int device = 0;
     hipStream_t own_stream = nullptr;
@@ -189,6 +206,7 @@ struct nyxhip_ctx {
     // host's libm, k <= kHexpolyTanCap, filled on the context's first call
     DevBuf d_hexpoly;
     DevBuf d_hexpoly_tan;
+    VolScanBufs volscan;               // nyxhip_assemble_volumes: the assembled device batch and the workspaces of the label scan
     const uint32_t* origin_x_next = nullptr;   // set by nyxhip_featurize_batch[_async]_at and the tile path for their next launch_device call:
     const uint32_t* origin_y_next = nullptr;   // device arrays [n_roi] of the ROIs' box origins (NULL: (0, 0))
     // grow-only workspaces of the fused tile path: scan tables + rows | clouds | two staging slots for host tiles

@@ -172,25 +172,59 @@ class Nyxus3D:
             try:
                 parts.append(getattr(ctx, blk.entry)(b, mask, self._settings, *([t] if t is not None else []), max_device_bytes=max_device_bytes))
             except _lib.NyxHipError as e:
-                zero = [k for k, f, bit, radius in blk.depths if getattr(t, f) == 0 and mask & bit and not (radius and getattr(t, radius) == 0)]
-                if e.code == _abi.ERR_UNSUPPORTED and zero and not self._settings.ibsi:
-                    raise _lib.NyxHipError(e.code, f"{e.args[0]} -- a grey depth of 0 leaves the intensities unbinned: set " +
-                                           " and ".join(f'set_metaparam("{k}=<levels>")' for k in zero) +
-                                           f" with at most {blk.cap} levels (negative: radiomics binning)") from e
-                raise
+                raise self._hinted(blk, mask, t, e) from e
         return parts[0] if len(parts) == 1 else np.hstack(parts)
 
+    def _hinted(self, blk: _Block, mask: int, t, e: _lib.NyxHipError) -> _lib.NyxHipError:
+        """The refusal `e` of a block's entry, with the hint at the unbinned grey depths where they explain it (else `e` itself)."""
+        zero = [k for k, f, bit, radius in blk.depths if getattr(t, f) == 0 and mask & bit and not (radius and getattr(t, radius) == 0)]
+        if e.code == _abi.ERR_UNSUPPORTED and zero and not self._settings.ibsi:
+            return _lib.NyxHipError(e.code, f"{e.args[0]} -- a grey depth of 0 leaves the intensities unbinned: set " +
+                                    " and ".join(f'set_metaparam("{k}=<levels>")' for k in zero) +
+                                    f" with at most {blk.cap} levels (negative: radiomics binning)")
+        return e
+
+    def _tables_device(self, inten: np.ndarray, label: np.ndarray, max_device_bytes: int):
+        """assembly="device": the volumes assembled once on the device (nyxhip_assemble_volumes), the served blocks written side by side
+        into one device table through the `volumes_*_device` methods on that one resident batch, one copy back.  Returns the table, the
+        labels and the volume indices of the rows."""
+        import torch
+        ctx = self._context()
+        if label.dtype.kind != "u" or label.dtype.itemsize > 4:
+            if label.size and (label.min() < 0 or label.max() > 0xFFFFFFFF):
+                raise ValueError("label values must fit 32 unsigned bits")
+            label = label.astype(np.uint32)
+        a = ctx.assemble_volumes_host(inten, label, max_device_bytes)
+        todo = [(blk, getattr(self, blk.mask_attr)) for blk in self._BLOCKS if getattr(self, blk.mask_attr)]
+        widths = [len(blk.names(mask, self._settings)) for blk, mask in todo]
+        ld = sum(widths)
+        if a.n_roi == 0:
+            return np.zeros((0, ld)), a.labels, a.volume_index
+        table = torch.empty((a.n_roi, ld), dtype=torch.float64, device=torch.device("cuda", self._device))
+        col = 0
+        for (blk, mask), width in zip(todo, widths):
+            t = getattr(self, blk.settings_attr) if blk.settings_attr else None
+            try:
+                getattr(ctx, blk.entry.replace("_host", "_device"))(a.batch, mask, self._settings, *([t] if t is not None else []), table.data_ptr() + 8 * col, ld)
+            except _lib.NyxHipError as e:
+                raise self._hinted(blk, mask, t, e) from e
+            col += width
+        return table.cpu().numpy(), a.labels, a.volume_index
+
     def featurize(self, intensity_volumes: np.ndarray, label_volumes: np.ndarray, intensity_names: Optional[list] = None,
-                  label_names: Optional[list] = None):
+                  label_names: Optional[list] = None, assembly: str = "host"):
         """Features of the labelled ROIs of a volume [z, y, x] or of a stack of volumes [n, z, y, x].
 
         Returns a DataFrame: `intensity_image`, `mask_image`, `ROI_label`, `t_index` as `Nyxus.featurize` returns them, then one column
         per requested code, rows in (volume, label) order.  The reference's table writer gives a 3-D code exactly one value
         (output_2_buffer.cpp:576-577): an angled `3GLCM_*` column is the value of direction shifts[0] = (1, 1, 1), the `_AVE` column
         the average over the 13 directions; all 13 are in the C table (nyxhip_featurize_volumes).  Values that are not finite are
-        replaced by soft_nan, as the writer does.  The voxel clouds are assembled from the label volume on the host; no slide
-        extrema exist in memory, so 3COVERED_IMAGE_INTENSITY_RANGE is 1 (3d_intensity.cpp:64-65)."""
-        import pandas as pd
+        replaced by soft_nan, as the writer does.  The voxel clouds are assembled from the label volume on the host
+        (`assembly="host"`, the default) or by the device label scan (`assembly="device"`: nyxhip_assemble_volumes, then every block on
+        the one resident batch; the same DataFrame); no slide extrema exist in memory, so 3COVERED_IMAGE_INTENSITY_RANGE is 1
+        (3d_intensity.cpp:64-65)."""
+        if assembly not in ("host", "device"):
+            raise ValueError(f'assembly must be "host" or "device", not {assembly!r}')
         if not isinstance(intensity_volumes, np.ndarray):
             raise ValueError("intensity_volumes parameter must be numpy.ndarray")
         if not isinstance(label_volumes, np.ndarray):
@@ -223,6 +257,15 @@ class Nyxus3D:
         if I.dtype != np.uint32:
             I = I.astype(np.uint32)
         cols, sel = self._columns()
+        if assembly == "device":
+            rl = self._env.get("ram_limit", -1)
+            table, labels, vol_of = self._tables_device(I, label_volumes, int(rl) << 20 if rl and rl > 0 else 0)
+            if len(labels):
+                table = np.ascontiguousarray(table)
+                _lib.load().nyxhip_finalize_table(table.ctypes.data, table.shape[0], table.shape[1], table.shape[1], C.c_double(self._settings.soft_nan))
+            else:
+                table = np.zeros((0, max(sel) + 1 if sel else 0))
+            return self._frame(table, labels, vol_of, cols, sel, intensity_names, label_names)
         rois, vol_of = [], []
         for v in range(nv):
             cl = clouds_from_volume(I[v], label_volumes[v])
@@ -237,6 +280,11 @@ class Nyxus3D:
         else:
             table = np.zeros((0, max(sel) + 1 if sel else 0))
             labels = np.zeros(0, np.uint32)
+        return self._frame(table, labels, vol_of, cols, sel, intensity_names, label_names)
+
+    @staticmethod
+    def _frame(table, labels, vol_of, cols, sel, intensity_names, label_names):
+        import pandas as pd
         ti = np.asarray(vol_of, dtype=np.intp)
         df = pd.DataFrame(table[:, sel], columns=cols)
         df.insert(0, "t_index", np.zeros(len(labels)))
