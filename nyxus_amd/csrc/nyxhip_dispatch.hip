@@ -1,5 +1,6 @@
 // nyxhip_dispatch.hip -- from a device-resident batch to kernel launches: LDS / workspace layouts, argument blocks, size classes.
 #include "nyxhip_ctx.h"
+#include "features_plan.h"
 
 using namespace nyxhip;
 
@@ -509,6 +510,13 @@ static void set_slots(SpillArgs& sp, const uint32_t* list, uint32_t n_slots)
     sp.roi_index = list; sp.n_slots = n_slots;
 }
 
+// The GLCM-only view of a launch's arguments: the GLCM block (ncol columns, col_glcm onwards) as a table of its own
+static void glcm_view(RoiArgs& a, int ncol)
+{
+    a.out += a.col_glcm;
+    a.mask = NYXHIP_FAM_GLCM; a.n_cols = ncol; a.col_glcm = 0; a.col_intensity = -1;
+}
+
 // Extrema every member of size class cls / 2 stays below (roi_class): what "does this class run from LDS?" is decided on, so that
 // the answer is a function of the class -- i.e. of the ROI -- and the settings, never of the members a call happens to hold.
 static Extrema class_bounds(int cls, const nyxhip_settings* s)
@@ -897,7 +905,7 @@ int run_class(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t mask, const nyxhi
                 if (make_layout(NYXHIP_FAM_INTENSITY, s, kIntensityCols, E.px, E.area, E.range, ai.L, w2) == NYXHIP_OK &&
                     make_layout(NYXHIP_FAM_GLCM, s, ncol_g, E.px, E.area, E.range, ag.L, w2) == NYXHIP_OK && ag.L.g16) {
                     ai.mask = NYXHIP_FAM_INTENSITY; ai.n_cols = kIntensityCols; ai.col_intensity = 0; ai.col_glcm = -1;
-                    ag.mask = NYXHIP_FAM_GLCM; ag.n_cols = ncol_g; ag.col_glcm = 0; ag.col_intensity = -1; ag.out = a.out + a.col_glcm;
+                    glcm_view(ag, ncol_g);
                     ag.census = nullptr;                               // (the intensity launch counts)
                     if (int r1 = launch_roi_features(ag, st, grid)) return r1;
                     return launch_roi_features(ai, st, grid);
@@ -922,7 +930,7 @@ int run_class(nyxhip_ctx* ctx, const nyxhip_batch* b, uint32_t mask, const nyxhi
                 std::string w2;
                 const int ncol_g = a.n_cols - a.col_glcm;
                 if (make_layout(NYXHIP_FAM_GLCM, s, ncol_g, E.px, E.area, std::min(E.range, 0xFFFFu), ag.L, w2, 0, E.vmax) != NYXHIP_OK) return 0;
-                ag.mask = NYXHIP_FAM_GLCM; ag.n_cols = ncol_g; ag.col_glcm = 0; ag.col_intensity = -1; ag.out = a.out + a.col_glcm;
+                glcm_view(ag, ncol_g);
                 if (a.glcm_ws && ag.L.ng_cap != a.L.ng_cap) return 0;          // (the count workspace was sized for the fused layout)
             }
             if (!b->inten) return NYXHIP_INTERNAL_NEEDS_CLOUDS;               // window-mode chunk: this kernel reads the clouds
@@ -1346,7 +1354,7 @@ int make_layout(uint32_t mask, const nyxhip_settings* s, int n_cols, uint32_t ma
         const bool split_pred = do_glcm && !spill && gi > 0 && gi <= 16 && s->glcm_n_angles > 0;
         L.dense8 = ((c16_pred || !do_int) && split_pred) ? 1u : 0u;           // (GLCM alone: nothing of the intensity block constrains the plane)
     }
-    {   // the reference's default grey depth on LDS launches: 16-bit matrices + 8-bit plane (roi_features_kernel_g16)
+    {   // the reference's default grey depth on LDS launches: 16-bit matrices + 8-bit plane (the TIER 9 builds of roi_features_kernel)
         const int gi = s->ibsi ? 0 : s->grey_depth;
         const bool c16_pred = (!do_int || (uint64_t)max_range + 1 <= kCountCapMax) && max_range < 65536u;
         L.g16 = (do_glcm && !spill && gi > 16 && gi <= 64 && max_px < 32768u && c16_pred && s->glcm_n_angles > 0) ? 1u : 0u;
@@ -1431,8 +1439,7 @@ int make_layout(uint32_t mask, const nyxhip_settings* s, int n_cols, uint32_t ma
         // the launch no workgroup per CU (eight at the most: 64-VGPR builds of four waves) -- the benchmark ROI, a 4096-entry
         // table: G = 8, 2 KiB, 20 192 B of the 20 480 B that eight workgroups leave each; a 16384-entry table next to a small
         // ROI: G = 16.  Like [val | cnt] the words are dead after the intensity block: the GLCM regions may lie over them.
-        const uint32_t lds_cu = (uint32_t)roi_features_max_lds();
-        auto wgs = [&](uint32_t total) -> uint32_t { return std::min<uint32_t>(8u, lds_cu / (total ? total : 1u)); };
+        auto wgs = lds_workgroups_per_cu;
         uint32_t sh = 3, with = off;
         for (;; sh++) {
             with = std::max(off, align16(cnt_end + 4u * ((L.count_cap + (1u << sh) - 1u) >> sh)));

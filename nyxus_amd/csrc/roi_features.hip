@@ -30,6 +30,7 @@
 #include "knobs.h"
 #include "device_math.h"
 #include "roi_kernel.h"
+#include "features_plan.h"
 #include "launch_util.h"
 #include "glcm_rows.h"
 #include "glcm_w64.h"
@@ -658,7 +659,7 @@ __device__ __forceinline__ void glcm_features_wave8(const uint32_t* P_a, const u
 //    group's log (scaled by 1 / sum_p once at the end).  Rows with an empty marginal hold no pair and are skipped.  The group loop
 //    runs on the scalar unit (ballot, s_ff1, bit clears).
 // Round 6: matrices of pitch `pitch` (even) whose data cells are word-aligned pairs.
-// Layout (roi_features_kernel_g16): u16 cells, rows 0..Ng (row = centre level, row 0 unused), element (centre a, neighbour b) at
+// Layout (the TIER 9 builds of roi_features_kernel): u16 cells, rows 0..Ng (row = centre level, row 0 unused), element (centre a, neighbour b) at
 // P[a * pitch + b - 1], pitch = (Ng + 3) & ~1: data columns 0..Ng-1 hold neighbour levels 1..Ng, a skipped neighbour (level 0)
 // lands in the LAST column of the previous row (never read), and column Ng of every row stays zero.  A row starts on a word, so
 // two cells travel in one register: row sums with v_pk_add_u16, the per-cell terms of two rows at once (lanes 0..31 one row, lanes
@@ -673,7 +674,7 @@ typedef unsigned short us2_t __attribute__((ext_vector_type(2)));
 #else
 #define G16_EXIT(k, keep) do { } while (0)
 #endif
-// ROLE (the eight-wave launch, roi_features_kernel_g16w8): 0 = an angle's whole pass on one wave.  1 / 2 = the pass on TWO waves: wave 2 forms
+// ROLE (the eight-wave launch, NW = 8): 0 = an angle's whole pass on one wave.  1 / 2 = the pass on TWO waves: wave 2 forms
 // the row and column sums it needs itself and runs the HXY1 / HXY2 row groups -- half of the pass's instructions -- while wave 1 does
 // everything else; wave 2's per-lane sums cross over through the angle's block (T2 | f, sm: dead between the two workgroup barriers) and
 // wave 1 closes with them: the same per-lane values in the same reductions as ROLE 0, bit for bit.  Waves without an angle take the two
@@ -895,7 +896,7 @@ __constant__ const double kPctFrac[8] = {0.01, 0.1, 0.25, 0.75, 0.9, 0.99, 0.5, 
 // GS: per-workgroup scratch in the global workspace instead of LDS (large-ROI launches).
 // C16: the counting table holds 16-bit entries and the value buffer 16-bit offsets from the ROI minimum (every ROI of the
 // launch has fewer than 65536 pixels and an intensity range the counting engine covers): half the LDS, so
-// that -- in the build that asks the compiler for <= 96 VGPRs (roi_features_kernel_occ5) -- five workgroups instead of four
+// that -- in the build that asks the compiler for <= 96 VGPRs (tier 5) -- five workgroups instead of four
 // share a CU.
 // SPLIT: the launch exports the GLCM counts for glcm_features_kernel; the in-kernel feature code is compiled out.
 // D8: the binned bounding-box plane holds 8-bit levels (grey depth <= 254); with C16 and SPLIT this brings the benchmark's
@@ -931,6 +932,44 @@ struct KView {
         else return &a;
     }
 };
+// The GLCM columns of a ROI from its per-angle features f[a * 32 + k], by thread t of n: feature-major, angle-minor
+// (output_2_buffer.cpp:336-346), then the _AVE columns.
+__device__ __forceinline__ void glcm_write_columns(double* o, const double* f, const int na, const int t, const int n)
+{
+    const int sh = na == 4 ? 2 : na == 2 ? 1 : na == 1 ? 0 : -1;  // the usual angle counts split c = k * na + a by a shift
+    for (int c = t; c < kGlcmAngled * na; c += n) {
+        const int k = sh >= 0 ? c >> sh : c / na, a = c - k * na;
+        o[c] = f[a * 32 + k];
+    }
+    for (int j = t; j < kGlcmAve; j += n) {                       // calc_ave (glcm.cpp:1205-1214): std::reduce folds four at a time
+        const int k = c_glcm_ave_order[j];
+        double init = 0.0;
+        int a = 0;
+        for (; na - a >= 4; a += 4) {
+            const double v1 = f[a * 32 + k] + f[(a + 1) * 32 + k];
+            const double v2 = f[(a + 2) * 32 + k] + f[(a + 3) * 32 + k];
+            init = init + (v1 + v2);
+        }
+        for (; a < na; a++)
+            init = init + f[a * 32 + k];
+        // (dividing by 4, 2 or 1 is a multiplication by the exact reciprocal: the same rounding, a tenth of the instructions)
+        o[kGlcmAngled * na + j] = na == 4 ? init * 0.25 : na == 2 ? init * 0.5 : na ? init / (double)na : 0.0;
+    }
+}
+
+// The exported co-occurrence counts of a ROI (nw words at src) into the wave's LDS: 16 bytes per lane and trip where the alignment
+// allows (na * Ng^2 = 256 words for four 8 x 8 matrices: one load per lane)
+__device__ __forceinline__ void glcm_load_counts(uint32_t* dst, const uint32_t* src, const int nw, const uint32_t stride, const int lane)
+{
+    if (((nw | (int)stride) & 3) == 0) {
+#pragma unroll 1
+        for (int i = lane; i < (nw >> 2); i += 64) ((uint4*)dst)[i] = ((const uint4*)src)[i];
+    } else {
+#pragma unroll 1
+        for (int i = lane; i < nw; i += 64) dst[i] = src[i];
+    }
+}
+
 // DEFER_P: the single-lane code that only turns finished sums into output columns is left to intensity_close_kernel (a lane per ROI,
 // launched behind this kernel): lane 0 writes the sums to the ROI's record (RoiArgs::close_rec) and raises its flag.  The 64-VGPR
 // builds only -- their limit is vector issue, and an instruction on one lane takes the slot of one on sixty-four.
@@ -2943,27 +2982,8 @@ __device__ __forceinline__ void roi_features_body(const RoiArgs& A, const uint64
             }
             grp_sync<GS, NW>();
             STAMP(12);
-            // lay out: feature-major, angle-minor (output_2_buffer.cpp:336-346), then _AVE
             if (!SPLIT)
-            for (int c = tid; c < kGlcmAngled * na; c += BS) {
-                int k = c / na, a = c - k * na;
-                o[c] = s_f[a * 32 + k];
-            }
-            if (!SPLIT)
-            for (int j = tid; j < kGlcmAve; j += BS) {
-                // calc_ave (glcm.cpp:1205-1214): libstdc++ std::reduce folds four at a time
-                int k = c_glcm_ave_order[j];
-                double init = 0.0;
-                int a = 0;
-                for (; na - a >= 4; a += 4) {
-                    double v1 = s_f[a * 32 + k] + s_f[(a + 1) * 32 + k];
-                    double v2 = s_f[(a + 2) * 32 + k] + s_f[(a + 3) * 32 + k];
-                    init = init + (v1 + v2);
-                }
-                for (; a < na; a++)
-                    init = init + s_f[a * 32 + k];
-                o[kGlcmAngled * na + j] = na ? init / (double)na : 0.0;
-            }
+                glcm_write_columns(o, s_f, na, tid, BS);
         }
     }
 
@@ -2971,59 +2991,14 @@ __device__ __forceinline__ void roi_features_body(const RoiArgs& A, const uint64
     STAMP(14);
 }
 
-template <bool GS, bool C16, bool SPLIT, bool D8>
-__global__ __launch_bounds__(kBlock, 4) void roi_features_kernel(const RoiArgs A)
+// The one entry of the body: a build is a row of NYX_FEATURE_BUILDS (features_plan.h) -- the body's template arguments and the
+// workgroups per CU it is compiled for (the VGPR budget: 8 / 7 / 6 / 5 / 4 under 64 / 72 / 80 / 96 / 128).  TIER tells the body which
+// budget it runs under; the two builds for grey depths 17 .. 64 (TIER 9) are compiled for four (256 threads) and eight (512) per CU.
+// Window launches under WindowSrc::xcd_swz walk the slots per XCD; the generic builds (WIN = 2) and the cloud builds serve slot = workgroup.
+template <bool GS, bool C16, bool SPLIT, bool D8, int FAM, int TIER, bool G16, int WIN, int NW, bool DEFER_P, int MINWG>
+__global__ __launch_bounds__(NW * 64, MINWG) void roi_features_kernel(const RoiArgs A)
 {
-    roi_features_body<GS, C16, SPLIT, D8>(A, blockIdx.x);
-}
-
-// the same body under tighter VGPR budgets (96 / 80): five or six workgroups per CU when their LDS fits (16-bit tables)
-template <bool C16, bool SPLIT, bool D8>
-__global__ __launch_bounds__(kBlock, 5) void roi_features_kernel_occ5(const RoiArgs A)
-{
-    roi_features_body<false, C16, SPLIT, D8, 0, 5>(A, blockIdx.x);
-}
-template <bool C16, bool SPLIT, bool D8>
-__global__ __launch_bounds__(kBlock, 6) void roi_features_kernel_occ6(const RoiArgs A)
-{
-    roi_features_body<false, C16, SPLIT, D8, 0, 6>(A, blockIdx.x);
-}
-template <bool C16, bool SPLIT, bool D8>
-__global__ __launch_bounds__(kBlock, 7) void roi_features_kernel_occ7(const RoiArgs A)
-{
-    roi_features_body<false, C16, SPLIT, D8, 0, 7>(A, blockIdx.x);
-}
-template <int FAM, int WIN>
-__global__ __launch_bounds__(kBlock, 8) void roi_features_kernel_occ8(const RoiArgs A)   // 64 VGPRs: the fully compact build only
-{
-    roi_features_body<false, true, FAM == 1 || FAM == 3, true, FAM, 8, false, WIN, 4, FAM == 1 || FAM == 2>(A, (WIN == 1 && A.win.xcd_swz) ? xcd_slot(blockIdx.x, gridDim.x) : (uint64_t)blockIdx.x);
-}
-// The same compile-time family sets and loaders at seven and six workgroups per CU: batches whose largest ROI needs a bigger
-// carve-out than the benchmark's (mixed-size data: the launch is sized by its largest ROI) keep the specialised body instead of
-// falling back to the generic one with its run-time switches and scalar-register spills.
-template <int FAM, int WIN>
-__global__ __launch_bounds__(kBlock, 7) void roi_features_kernel_fam7(const RoiArgs A)
-{
-    roi_features_body<false, true, FAM == 1 || FAM == 3, true, FAM, 7, false, WIN>(A, (WIN == 1 && A.win.xcd_swz) ? xcd_slot(blockIdx.x, gridDim.x) : (uint64_t)blockIdx.x);
-}
-template <int FAM, int WIN>
-__global__ __launch_bounds__(kBlock, 6) void roi_features_kernel_fam6(const RoiArgs A)
-{
-    roi_features_body<false, true, FAM == 1 || FAM == 3, true, FAM, 6, false, WIN>(A, (WIN == 1 && A.win.xcd_swz) ? xcd_slot(blockIdx.x, gridDim.x) : (uint64_t)blockIdx.x);
-}
-
-// the reference's default grey depth: 16-bit matrices, marginal-based features (three workgroups per CU)
-template <int WIN>
-__global__ __launch_bounds__(kBlock, 4) void roi_features_kernel_g16(const RoiArgs A)
-{
-    roi_features_body<false, true, false, true, 0, 9, true, WIN>(A, (WIN == 1 && A.win.xcd_swz) ? xcd_slot(blockIdx.x, gridDim.x) : (uint64_t)blockIdx.x);
-}
-
-// ... and its GLCM-only form on eight waves (512 threads) per ROI
-template <int WIN>
-__global__ __launch_bounds__(512, 8) void roi_features_kernel_g16w8(const RoiArgs A)
-{
-    roi_features_body<false, true, false, true, 4, 9, true, WIN, 8>(A, (WIN == 1 && A.win.xcd_swz) ? xcd_slot(blockIdx.x, gridDim.x) : (uint64_t)blockIdx.x);
+    roi_features_body<GS, C16, SPLIT, D8, FAM, TIER, G16, WIN, NW, DEFER_P>(A, (WIN == 1 && A.win.xcd_swz) ? xcd_slot(blockIdx.x, gridDim.x) : (uint64_t)blockIdx.x);
 }
 
 // A launch that serves some classes only (SpillArgs::class_mask, whole-batch launches): is this ROI one of them?  (The feature kernels
@@ -3050,51 +3025,18 @@ __global__ __launch_bounds__(kBlock, 4) void glcm_features_kernel(const RoiArgs 
         return;                                       // degenerate / skipped ROI: roi_features_kernel wrote the columns
     const int na = A.glcm_na, ngc = (int)A.L.ng_cap, NN = Ng * Ng;
     // per-wave carve-out: counts [na * ngc^2] u32 | (unused) [ngc] | marginals [4][6 * ngc] | features [4][32] | sums [4][32]  (doubles)
-    const size_t per_wave = (((size_t)4 * kMaxAngles * ngc * ngc + 15) & ~(size_t)15) + 8ull * (ngc + kMaxAngles * 6 * ngc + 2 * kMaxAngles * 32);
-    unsigned char* base = lds_raw + (size_t)wave * per_wave;
+    unsigned char* base = lds_raw + (size_t)wave * glcm_wave_lds(ngc);
     uint32_t* s_P = (uint32_t*)base;
-    double* s_scr = (double*)(base + (((size_t)4 * kMaxAngles * ngc * ngc + 15) & ~(size_t)15)) + ngc;
+    double* s_scr = (double*)(base + glcm_cnt_bytes(ngc)) + ngc;
     double* s_f = s_scr + kMaxAngles * 6 * ngc;
     const uint32_t* src = A.glcm_ws + roi * A.glcm_ws_stride;
-    // the ROI's counts: 16 bytes per lane and trip (na * Ng^2 = 256 words for four 8 x 8 matrices: one load per lane)
-    const int nw = na * NN;
-    if (((nw | (int)A.glcm_ws_stride) & 3) == 0) {
-#pragma unroll 1
-        for (int i = lane; i < (nw >> 2); i += 64) ((uint4*)s_P)[i] = ((const uint4*)src)[i];
-    } else {
-#pragma unroll 1
-        for (int i = lane; i < nw; i += 64) s_P[i] = src[i];
-    }
+    glcm_load_counts(s_P, src, na * NN, A.glcm_ws_stride, lane);
     wav_sync<false>();
     glcm_features_wave16(s_P, na, Ng, s_scr, 6 * ngc, A.soft_nan, s_f, s_f + kMaxAngles * 32, lane);   // level values I[i] = i + 1 (glcm.cpp:400-408)
     wav_sync<false>();
-    double* o = A.out + roi * A.ld + A.col_glcm;
-    const int sh = na == 4 ? 2 : na == 2 ? 1 : na == 1 ? 0 : -1;  // the usual angle counts split c = k * na + a by a shift
-    for (int c = lane; c < kGlcmAngled * na; c += 64) {           // feature-major, angle-minor (output_2_buffer.cpp:336-346)
-        const int k = sh >= 0 ? c >> sh : c / na, a = c - k * na;
-        o[c] = s_f[a * 32 + k];
-    }
-    for (int j = lane; j < kGlcmAve; j += 64) {                   // calc_ave (glcm.cpp:1205-1214): std::reduce folds four at a time
-        const int k = c_glcm_ave_order[j];
-        double init = 0.0;
-        int a = 0;
-        for (; na - a >= 4; a += 4) {
-            const double v1 = s_f[a * 32 + k] + s_f[(a + 1) * 32 + k];
-            const double v2 = s_f[(a + 2) * 32 + k] + s_f[(a + 3) * 32 + k];
-            init = init + (v1 + v2);
-        }
-        for (; a < na; a++)
-            init = init + s_f[a * 32 + k];
-        // (dividing by 4, 2 or 1 is a multiplication by the exact reciprocal: the same rounding, a tenth of the instructions)
-        o[kGlcmAngled * na + j] = na == 4 ? init * 0.25 : na == 2 ? init * 0.5 : na ? init / (double)na : 0.0;
-    }
+    glcm_write_columns(A.out + roi * A.ld + A.col_glcm, s_f, na, lane, 64);
 }
 
-__host__ __device__ inline size_t glcm8_cnt_bytes(uint32_t ngc)   // a count block, at least the 1 KiB the ROI's features take in its place
-{
-    const size_t c = ((size_t)4 * kMaxAngles * ngc * ngc + 15) & ~(size_t)15, fbytes = 8ull * kMaxAngles * 32;
-    return c > fbytes ? c : fbytes;
-}
 // The same for matrices of up to 8 levels: two ROIs per wave (glcm_features_wave8), eight per workgroup.
 __global__ __launch_bounds__(kBlock, 8) void glcm_features_kernel8(const RoiArgs A)
 {
@@ -3113,23 +3055,14 @@ __global__ __launch_bounds__(kBlock, 8) void glcm_features_kernel8(const RoiArgs
     // holds at 8 levels) | per group (8): pcol [8] prow [8] | sums [8][32]  (doubles) -- 5 KiB per wave (round 6; 8 KiB before: five
     // workgroups per CU, now the register count's six waves per SIMD)
     const size_t cnt_bytes = glcm8_cnt_bytes((uint32_t)ngc);
-    const size_t per_wave = 2 * cnt_bytes + 8ull * (2 * kMaxAngles * 16 + 2 * kMaxAngles * 32);
-    unsigned char* base = lds_raw + (size_t)wave * per_wave;
+    unsigned char* base = lds_raw + (size_t)wave * glcm8_wave_lds((uint32_t)ngc);
     uint32_t* s_P[2] = {(uint32_t*)base, (uint32_t*)(base + cnt_bytes)};
     double* s_scr = (double*)(base + 2 * cnt_bytes);
     double* s_sum = s_scr + 2 * kMaxAngles * 16;
 #pragma unroll
     for (int q = 0; q < 2; q++) {
         if (Ng[q] == 0) continue;
-        const uint32_t* src = A.glcm_ws + roi[q] * A.glcm_ws_stride;
-        const int nw = na * Ng[q] * Ng[q];
-        if (((nw | (int)A.glcm_ws_stride) & 3) == 0) {
-#pragma unroll 1
-            for (int i = lane; i < (nw >> 2); i += 64) ((uint4*)s_P[q])[i] = ((const uint4*)src)[i];
-        } else {
-#pragma unroll 1
-            for (int i = lane; i < nw; i += 64) s_P[q][i] = src[i];
-        }
+        glcm_load_counts(s_P[q], A.glcm_ws + roi[q] * A.glcm_ws_stride, na * Ng[q] * Ng[q], A.glcm_ws_stride, lane);
     }
     wav_sync<false>();
     // (group g = ROI g >> 2, angle g & 3 writes f = fslots + g * 32 doubles: the ROI's own count block)
@@ -3140,29 +3073,10 @@ __global__ __launch_bounds__(kBlock, 8) void glcm_features_kernel8(const RoiArgs
     else
         glcm_features_wave8<true>(s_P[0], s_P[1], 4, Ng[0], Ng[1], s_scr, 16, A.soft_nan, (double*)base, (size_t)(cnt_bytes >> 3) - 4 * 32, s_sum, lane);
     wav_sync<false>();
-    const int sh = na == 4 ? 2 : na == 2 ? 1 : na == 1 ? 0 : -1;
 #pragma unroll
-    for (int q = 0; q < 2; q++) {
-        if (Ng[q] == 0) continue;
-        double* o = A.out + roi[q] * A.ld + A.col_glcm;
-        const double* fq = (const double*)(base + (size_t)q * cnt_bytes);
-        for (int c = lane; c < kGlcmAngled * na; c += 64) {           // feature-major, angle-minor (output_2_buffer.cpp:336-346)
-            const int k = sh >= 0 ? c >> sh : c / na, a = c - k * na;
-            o[c] = fq[a * 32 + k];
-        }
-        for (int j = lane; j < kGlcmAve; j += 64) {                   // calc_ave (glcm.cpp:1205-1214): std::reduce folds four at a time
-            const int k = c_glcm_ave_order[j];
-            double init = 0.0;
-            int a = 0;
-            for (; na - a >= 4; a += 4) {
-                const double v1 = fq[a * 32 + k] + fq[(a + 1) * 32 + k];
-                const double v2 = fq[(a + 2) * 32 + k] + fq[(a + 3) * 32 + k];
-                init = init + (v1 + v2);
-            }
-            for (; a < na; a++) init = init + fq[a * 32 + k];
-            o[kGlcmAngled * na + j] = na == 4 ? init * 0.25 : na == 2 ? init * 0.5 : na ? init / (double)na : 0.0;
-        }
-    }
+    for (int q = 0; q < 2; q++)
+        if (Ng[q] != 0)
+            glcm_write_columns(A.out + roi[q] * A.ld + A.col_glcm, (const double*)(base + (size_t)q * cnt_bytes), na, lane, 64);
 }
 
 // ---- deferred intensity closing ------------------------------------------------------------------------------------------
@@ -3170,7 +3084,6 @@ __global__ __launch_bounds__(kBlock, 8) void glcm_features_kernel8(const RoiArgs
 // columns the feature kernel closes on a single lane of a four-wave workgroup, through the same functions (intensity_close.h: the sums'
 // own outputs, the central block, the robust outputs, QCOD and IQR), and clears the flag.  The columns go through LDS (packed: the 26
 // deferred ones) so that the wave stores a row's columns side by side.
-constexpr int kCloseBlock = 64;
 constexpr uint64_t kCloseCols =
     (1ull << I_MIN) | (1ull << I_MAX) | (1ull << I_RANGE) | (1ull << I_COVERED_IMAGE_INTENSITY_RANGE) | (1ull << I_MEAN) | (1ull << I_ENERGY) |
     (1ull << I_ROOT_MEAN_SQUARED) | (1ull << I_INTEGRATED_INTENSITY) | (1ull << I_UNIFORMITY_PIU) | (1ull << I_MEAN_ABSOLUTE_DEVIATION) |
@@ -3255,20 +3168,9 @@ __global__ __launch_bounds__(kCloseBlock) void intensity_close_kernel(const RoiA
 #endif
 }
 
-size_t glcm_features8_lds(uint32_t ng_cap)
-{
-    return (2 * glcm8_cnt_bytes(ng_cap) + 8ull * (2 * kMaxAngles * 16 + 2 * kMaxAngles * 32)) * kWaves;
-}
-
-size_t glcm_features_lds(uint32_t ng_cap)
-{
-    const size_t per_wave = (((size_t)4 * kMaxAngles * ng_cap * ng_cap + 15) & ~(size_t)15) + 8ull * (ng_cap + kMaxAngles * 6 * ng_cap + 2 * kMaxAngles * 32);
-    return per_wave * kWaves;
-}
-
 size_t roi_features_max_lds()
 {
-    return 160 * 1024; // gfx950: 160 KiB per CU, all of it usable by one workgroup
+    return kLdsPerCu;
 }
 
 namespace {
@@ -3283,84 +3185,29 @@ int no_static_lds(const void* f)
     return at.sharedSizeBytes == 0 ? 0 : (int)hipErrorInvalidConfiguration;
 }
 
-template <bool C16, bool SPLIT, bool D8>
-int launch_lds_variant(const RoiArgs& a, hipStream_t st, uint32_t grid, bool& deferred)
+// the builds of NYX_FEATURE_BUILDS as kernels, row for row (naming them here instantiates them)
+using FeatureKernel = void (*)(const RoiArgs);
+#define X(GS, C16, SPLIT, D8, FAM, TIER, G16, WIN, NW, DEFER_P, MINWG) roi_features_kernel<GS, C16, SPLIT, D8, FAM, TIER, G16, WIN, NW, DEFER_P, MINWG>,
+constexpr FeatureKernel kFeatureKernels[] = {NYX_FEATURE_BUILDS(X)};
+#undef X
+static_assert(sizeof(kFeatureKernels) / sizeof(kFeatureKernels[0]) == kFeatureBuildCount, "a kernel per row of the table");
+
+// every LDS build may carve out the whole CU, once per device (the workspace builds stay within the default)
+int optin_lds_builds()
 {
-    deferred = false;
     static DeviceOnce optin;
-    if (int orc = optin.run([]() -> int {
-        const void* fns[22] = {(const void*)roi_features_kernel<false, C16, SPLIT, D8>, (const void*)roi_features_kernel_occ5<C16, SPLIT, D8>,
-                               (const void*)roi_features_kernel_occ6<C16, SPLIT, D8>, (const void*)roi_features_kernel_occ7<C16, SPLIT, D8>,
-                               (const void*)roi_features_kernel_occ8<1, 0>, (const void*)roi_features_kernel_occ8<2, 0>,
-                               (const void*)roi_features_kernel_occ8<1, 1>, (const void*)roi_features_kernel_occ8<2, 1>,
-                               (const void*)roi_features_kernel_fam7<1, 0>, (const void*)roi_features_kernel_fam7<2, 0>,
-                               (const void*)roi_features_kernel_fam7<1, 1>, (const void*)roi_features_kernel_fam7<2, 1>,
-                               (const void*)roi_features_kernel_fam6<1, 0>, (const void*)roi_features_kernel_fam6<2, 0>,
-                               (const void*)roi_features_kernel_fam6<1, 1>, (const void*)roi_features_kernel_fam6<2, 1>,
-                               (const void*)roi_features_kernel_occ8<3, 0>, (const void*)roi_features_kernel_occ8<3, 1>,
-                               (const void*)roi_features_kernel_fam7<3, 0>, (const void*)roi_features_kernel_fam7<3, 1>,
-                               (const void*)roi_features_kernel_fam6<3, 0>, (const void*)roi_features_kernel_fam6<3, 1>};
-        for (const void* f : fns) {
-            hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)roi_features_max_lds());
-            if (e != hipSuccess)
+    return optin.run([]() -> int {
+        for (int i = 0; i < kFeatureBuildCount; i++) {
+            if (kFeatureBuilds[i].gs)
+                continue;
+            const void* f = (const void*)kFeatureKernels[i];
+            if (hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)roi_features_max_lds()); e != hipSuccess)
                 return (int)e;
             if (int src = no_static_lds(f))
                 return src;
         }
         return 0;
-    }))
-        return orc;
-    // occupancy follows the carve-out: 8 / 7 / 6 / 5 / 4 workgroups per CU with builds held to 64 / 72 / 80 / 96 / 128 VGPRs
-    const size_t lds = roi_features_max_lds();
-    // the 64-VGPR tier exists for the two compile-time family sets only
-    const bool int_only = !(a.mask & NYXHIP_FAM_GLCM) && (a.mask & NYXHIP_FAM_INTENSITY);
-    const bool int_glcm = (a.mask & NYXHIP_FAM_GLCM) && (a.mask & NYXHIP_FAM_INTENSITY) && a.L.dense8 && a.glcm_ws != nullptr && !a.ibsi &&
-                          a.grey_depth > 0 && a.grey_depth <= 16;
-    const bool glcm_only = (a.mask & NYXHIP_FAM_GLCM) && !(a.mask & NYXHIP_FAM_INTENSITY) && a.L.dense8 && a.glcm_ws != nullptr && !a.ibsi &&
-                           a.grey_depth > 0 && a.grey_depth <= 16;
-    const bool fam_ok = C16 && SPLIT && D8 && (int_only || int_glcm || glcm_only);   // a compile-time family set of the compact builds applies
-    int occ = 4;
-    for (int o = fam_ok ? 8 : 7; o > 4; o--)
-        if ((size_t)o * a.L.total <= lds) { occ = o; break; }
-    occ = knob::cap_occ(occ);   // tuning knob (bench experiments)
-    const bool win = a.win.inten != nullptr;
-    if (win && a.win.xcd_swz) grid = (grid + 7u) & ~7u;               // (xcd_slot: every XCD walks its own eighth of the slots)
-    // the 64-VGPR builds with the intensity block leave their closing math to intensity_close_kernel (launch_roi_features)
-    // (what roi_features_body decides from DEFER_P: occ == 8 implies a compile-time family set, C16 and an LDS launch.  A build with
-    //  -DNYX_NO_DEFER / -DNYX_NO_FUSED closes in-kernel and launches no closing kernel, but launch_device_all still clears the flags:
-    //  for timing against the in-kernel closing it is close to, not the same as, a build without the mechanism)
-#if defined(NYX_NO_FUSED) || defined(NYX_NO_DEFER)
-    deferred = false;
-#else
-    deferred = occ == 8 && (a.mask & NYXHIP_FAM_INTENSITY) != 0;
-#endif
-    if (deferred && !(a.close_rec && a.close_flag))
-        return (int)hipErrorInvalidValue;
-    if (fam_ok && glcm_only && occ >= 6) {
-        if (occ == 8) { if (win) hipLaunchKernelGGL((roi_features_kernel_occ8<3, 1>), dim3(grid), dim3(kBlock), a.L.total, st, a);
-                        else hipLaunchKernelGGL((roi_features_kernel_occ8<3, 0>), dim3(grid), dim3(kBlock), a.L.total, st, a); }
-        else if (occ == 7) { if (win) hipLaunchKernelGGL((roi_features_kernel_fam7<3, 1>), dim3(grid), dim3(kBlock), a.L.total, st, a);
-                             else hipLaunchKernelGGL((roi_features_kernel_fam7<3, 0>), dim3(grid), dim3(kBlock), a.L.total, st, a); }
-        else { if (win) hipLaunchKernelGGL((roi_features_kernel_fam6<3, 1>), dim3(grid), dim3(kBlock), a.L.total, st, a);
-               else hipLaunchKernelGGL((roi_features_kernel_fam6<3, 0>), dim3(grid), dim3(kBlock), a.L.total, st, a); }
-    }
-    else if (occ == 8 && int_only && win) hipLaunchKernelGGL((roi_features_kernel_occ8<2, 1>), dim3(grid), dim3(kBlock), a.L.total, st, a);
-    else if (occ == 8 && int_only) hipLaunchKernelGGL((roi_features_kernel_occ8<2, 0>), dim3(grid), dim3(kBlock), a.L.total, st, a);
-    else if (occ == 8 && win) hipLaunchKernelGGL((roi_features_kernel_occ8<1, 1>), dim3(grid), dim3(kBlock), a.L.total, st, a);
-    else if (occ == 8) hipLaunchKernelGGL((roi_features_kernel_occ8<1, 0>), dim3(grid), dim3(kBlock), a.L.total, st, a);
-    else if (fam_ok && occ == 7 && int_only && win) hipLaunchKernelGGL((roi_features_kernel_fam7<2, 1>), dim3(grid), dim3(kBlock), a.L.total, st, a);
-    else if (fam_ok && occ == 7 && int_only) hipLaunchKernelGGL((roi_features_kernel_fam7<2, 0>), dim3(grid), dim3(kBlock), a.L.total, st, a);
-    else if (fam_ok && occ == 7 && win) hipLaunchKernelGGL((roi_features_kernel_fam7<1, 1>), dim3(grid), dim3(kBlock), a.L.total, st, a);
-    else if (fam_ok && occ == 7) hipLaunchKernelGGL((roi_features_kernel_fam7<1, 0>), dim3(grid), dim3(kBlock), a.L.total, st, a);
-    else if (fam_ok && occ == 6 && int_only && win) hipLaunchKernelGGL((roi_features_kernel_fam6<2, 1>), dim3(grid), dim3(kBlock), a.L.total, st, a);
-    else if (fam_ok && occ == 6 && int_only) hipLaunchKernelGGL((roi_features_kernel_fam6<2, 0>), dim3(grid), dim3(kBlock), a.L.total, st, a);
-    else if (fam_ok && occ == 6 && win) hipLaunchKernelGGL((roi_features_kernel_fam6<1, 1>), dim3(grid), dim3(kBlock), a.L.total, st, a);
-    else if (fam_ok && occ == 6) hipLaunchKernelGGL((roi_features_kernel_fam6<1, 0>), dim3(grid), dim3(kBlock), a.L.total, st, a);
-    else if (occ == 7) hipLaunchKernelGGL((roi_features_kernel_occ7<C16, SPLIT, D8>), dim3(grid), dim3(kBlock), a.L.total, st, a);
-    else if (occ == 6) hipLaunchKernelGGL((roi_features_kernel_occ6<C16, SPLIT, D8>), dim3(grid), dim3(kBlock), a.L.total, st, a);
-    else if (occ == 5) hipLaunchKernelGGL((roi_features_kernel_occ5<C16, SPLIT, D8>), dim3(grid), dim3(kBlock), a.L.total, st, a);
-    else hipLaunchKernelGGL((roi_features_kernel<false, C16, SPLIT, D8>), dim3(grid), dim3(kBlock), a.L.total, st, a);
-    return (int)hipGetLastError();
+    });
 }
 
 } // namespace
@@ -3370,62 +3217,39 @@ int launch_roi_features(const RoiArgs& a, void* stream, uint32_t grid)
     if (grid == 0)
         return 0;
     hipStream_t st = (hipStream_t)stream;
-    const bool c16 = a.L.cnt16 != 0;
-    if (a.sp.scratch) {
-        if (c16) hipLaunchKernelGGL((roi_features_kernel<true, true, false, false>), dim3(grid), dim3(kBlock), a.L.gs_lds_bytes, st, a);
-        else hipLaunchKernelGGL((roi_features_kernel<true, false, false, false>), dim3(grid), dim3(kBlock), a.L.gs_lds_bytes, st, a);
-        return (int)hipGetLastError();
+    // no_small, g16_w4, glcm_no_pairs: A/B knobs | max_occ, g16_w8_min: tuning knobs (bench experiments)
+    const FeaturesKnobs kn = {knob::no_small(), knob::max_occ(), knob::g16_w4(), knob::g16_w8_min(), knob::glcm_no_pairs()};
+    const FeaturesPlan p = plan_features_launch(a, grid, kn, roi_small_supported(a));
+    const FeatureBuild& b = p.build;
+    if (!a.sp.scratch && knob::debug()) {
+        char what[96];
+        if (p.small) snprintf(what, sizeof(what), "small");
+        else snprintf(what, sizeof(what), "tier %d fam %d win %d c16 %d split %d d8 %d nw %d defer %d", b.tier, b.fam, b.win, b.c16, b.split, b.d8, b.nw, b.defer);
+        fprintf(stderr, "[nyxhip] features launch: g16 %u dense8 %u cnt16 %u ng_cap %u app %u total %u mask %u gd %d overlap %u build %s\n", a.L.g16, a.L.dense8, a.L.cnt16, a.L.ng_cap, a.L.app, a.L.total, a.mask, a.grey_depth, a.L.overlap, what);
     }
-    if (knob::debug()) fprintf(stderr, "[nyxhip] features launch: g16 %u dense8 %u cnt16 %u ng_cap %u app %u total %u mask %u gd %d overlap %u\n", a.L.g16, a.L.dense8, a.L.cnt16, a.L.ng_cap, a.L.app, a.L.total, a.mask, a.grey_depth, a.L.overlap);
-    // the smallest size class on its own kernel: a wave per ROI (roi_small.hip).  small_class: 1 = a list / filtered launch of class 0,
-    // 2 = a whole-batch launch whose stated extrema promise class 0 only
-    const bool no_small = knob::no_small();   // A/B knob
-    if (a.L.g16) {
-        if (a.small_class && !no_small && roi_small_supported(a)) return launch_roi_small(a, st, grid, a.small_class == 2);
-        static DeviceOnce optin;
-        if (int orc = optin.run([]() -> int {
-                for (const void* f : {(const void*)roi_features_kernel_g16<0>, (const void*)roi_features_kernel_g16<1>,
-                                      (const void*)roi_features_kernel_g16w8<0>, (const void*)roi_features_kernel_g16w8<1>}) {
-                    if (hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)roi_features_max_lds()); e != hipSuccess)
-                        return (int)e;
-                    if (int src = no_static_lds(f))
-                        return src;
-                }
-                return 0;
-            }))
-            return orc;
-        // g16_w4: A/B knob, four waves per ROI | g16_w8_min: tuning knob, smallest class box for eight waves
-        // (eight waves pay where the load and the sweep are long: 2821-px ROIs 23.0 -> 22.1 ns, 1009-px ROIs 18.5 -> 18.8: by the class's largest box)
-        if (!(a.mask & NYXHIP_FAM_INTENSITY) && !knob::g16_w4() && a.L.dense_cap >= (uint32_t)knob::g16_w8_min()) {
-            if (a.win.inten != nullptr) hipLaunchKernelGGL(roi_features_kernel_g16w8<1>, dim3(a.win.xcd_swz ? (grid + 7u) & ~7u : grid), dim3(512), a.L.total, st, a);
-            else hipLaunchKernelGGL(roi_features_kernel_g16w8<0>, dim3(grid), dim3(512), a.L.total, st, a);
-        } else
-        if (a.win.inten != nullptr) hipLaunchKernelGGL(roi_features_kernel_g16<1>, dim3(a.win.xcd_swz ? (grid + 7u) & ~7u : grid), dim3(kBlock), a.L.total, st, a);
-        else hipLaunchKernelGGL(roi_features_kernel_g16<0>, dim3(grid), dim3(kBlock), a.L.total, st, a);
-        return (int)hipGetLastError();
-    }
-    const bool split = a.glcm_ws != nullptr;
-    // dense8 is set by the host only together with the 16-bit tables and the split; an intensity-only launch never touches
-    // the GLCM code, so it can run the fully compact build (and its 64-VGPR tier) as well
-    const bool d8 = a.L.dense8 != 0 || (c16 && !(a.mask & NYXHIP_FAM_GLCM));
+    if (p.close_args_missing)
+        return (int)hipErrorInvalidValue;
     int rc;
-    bool deferred = false;
-    if (a.small_class && !no_small && (c16 || !(a.mask & NYXHIP_FAM_INTENSITY)) && roi_small_supported(a)) rc = launch_roi_small(a, st, grid, a.small_class == 2);
-    else
-    rc = d8 ? launch_lds_variant<true, true, true>(a, st, grid, deferred)
-           : c16 ? (split ? launch_lds_variant<true, true, false>(a, st, grid, deferred) : launch_lds_variant<true, false, false>(a, st, grid, deferred))
-                 : (split ? launch_lds_variant<false, true, false>(a, st, grid, deferred) : launch_lds_variant<false, false, false>(a, st, grid, deferred));
-    if (rc == 0 && deferred) {                    // the closing math of the ROIs that launch deferred, over the same slots
-        hipLaunchKernelGGL(intensity_close_kernel, dim3((grid + kCloseBlock - 1) / kCloseBlock), dim3(kCloseBlock), 0, st, a);
+    if (p.small)
+        rc = launch_roi_small(a, st, p.grid, p.small_promised);
+    else {
+        const int row = feature_build_row(b);
+        if (row < 0)
+            return (int)hipErrorInvalidDeviceFunction;        // (the plan names a build the table does not have)
+        if (!b.gs)
+            if (int orc = optin_lds_builds())
+                return orc;
+        hipLaunchKernelGGL(kFeatureKernels[row], dim3(p.grid), dim3(p.block), p.lds, st, a);
         rc = (int)hipGetLastError();
     }
-    if (rc == 0 && split && a.glcm_feats != 1) {
+    if (rc == 0 && p.close) {                     // the closing math of the ROIs that launch deferred, over the same slots
+        hipLaunchKernelGGL(intensity_close_kernel, dim3(p.close_grid), dim3(kCloseBlock), 0, st, a);
+        rc = (int)hipGetLastError();
+    }
+    if (rc == 0 && p.glcm != kGlcmNone) {
         RoiArgs af = a;
-        if (a.glcm_feats == 2) af.sp.class_mask = 0;          // (the class-0 group of this call left its counts for this launch: everybody with a matrix order is derived)
-        if (a.L.ng_cap <= 8 && !knob::glcm_no_pairs())   // eight lanes per angle, two ROIs per wave (A/B knob)
-            hipLaunchKernelGGL(glcm_features_kernel8, dim3((grid + 2 * kWaves - 1) / (2 * kWaves)), dim3(kBlock), glcm_features8_lds(a.L.ng_cap), st, af);
-        else
-            hipLaunchKernelGGL(glcm_features_kernel, dim3((grid + kWaves - 1) / kWaves), dim3(kBlock), glcm_features_lds(a.L.ng_cap), st, af);
+        if (p.glcm_all_classes) af.sp.class_mask = 0;
+        hipLaunchKernelGGL(p.glcm == kGlcmPairs8 ? glcm_features_kernel8 : glcm_features_kernel, dim3(p.glcm_grid), dim3(kBlock), p.glcm_lds, st, af);
         rc = (int)hipGetLastError();
     }
     return rc;

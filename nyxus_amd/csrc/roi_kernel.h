@@ -100,7 +100,7 @@ struct LdsLayout {
     uint32_t ng_cap;     // max GLCM matrix order held in LDS
     uint32_t lvl_cap;    // number of radiomics bins
     uint32_t app;        // angles per co-occurrence pass (4, 2 or 1)
-    uint32_t g16;        // 1: matlab binning with 17..64 levels, 16-bit co-occurrence cells, marginal-based features (roi_features_kernel_g16)
+    uint32_t g16;        // 1: matlab binning with 17..64 levels, 16-bit co-occurrence cells, marginal-based features (the TIER 9 builds of roi_features_kernel)
     // workspace launches (state in global memory): regions whose offset lies below this bound still live in the workgroup's LDS
     // -- the small, atomics-heavy ones: reduction scratch, histogram bounds, co-occurrence matrices, the counting table when it
     // fits -- and only the ROI-sized buffers (values, binned plane) in the workspace
@@ -204,7 +204,7 @@ struct RoiArgs {
                              // launch whose stated extrema promise class 0 only -> the wave-per-ROI kernel of roi_small.hip; 0 = roi_features_kernel
     uint32_t glcm_feats;     // split GLCM launches: 0 = glcm_features_kernel follows this launch over the same slots; 1 = not after this launch (the next
                              // launch group of the call derives this group's ROIs as well); 2 = it follows over ALL slots, class filter off
-    // deferred intensity closing (the 64-VGPR builds of roi_features_kernel): one lane leaves the ROI's finished sums in a record,
+    // deferred intensity closing (the tier-8 builds of roi_features_kernel with the intensity block: features_plan.h): one lane leaves the ROI's finished sums in a record,
     // intensity_close_kernel -- a lane per ROI, launched behind the feature kernel -- turns them into the output columns
     double* close_rec;       // [n_roi][kCloseRec] records (CloseRec below)
     uint32_t* close_flag;    // [n_roi] 1 = the ROI's record waits for intensity_close_kernel (which clears it); cleared per call as well

@@ -738,7 +738,7 @@ __global__ __launch_bounds__(256, (SCAN && GLCM != 2) ? 8 : 1) void roi_small_ke
 } // namespace
 
 // Can the wave-per-ROI kernel serve this launch's family set and settings?  (INTENSITY with the 16-bit-table conditions of its class,
-// GLCM only as the split launch of matlab binning with <= 16 levels -- what roi_features_kernel_occ8's compile-time family sets cover.)
+// GLCM only as the split launch of matlab binning with <= 16 levels -- what the compile-time family sets of roi_features_kernel's compact builds cover: features_plan.h.)
 bool roi_small_supported(const RoiArgs& a)
 {
     if (a.sp.scratch) return false;

@@ -8,15 +8,14 @@ the last trip return nothing), one pixel more, one pixel less.  The 2821-px benc
 
 One batch of ROIs with those pixel counts, three value sets (one per compile-time form of the consume half), the three masks of
 the compact builds, on stated extrema (whole-batch launches, the path the benchmark takes) and through the classifier.  Every call
-is held to the eight-per-CU carve-out on the library's own launch line (NYXHIP_DEBUG): that is what selects the occ8 builds, the
-ones with the rotated loader; a batch that slid to a generic tier would only test the serial trip."""
-import re
-
+is held to the eight-per-CU carve-out on the library's own launch line (NYXHIP_DEBUG): that is what selects the tier-8 builds, the
+ones with the rotated loader (the line names the build, and tests/device_call.py::assert_compact_tier holds it to that); a batch that slid to a generic tier would only test the serial trip."""
 import numpy as np
 import pytest
 
 from nyxus_amd import _abi, _lib
 from oracle import pyoracle as po
+from tests import device_call as dc
 from tests import parity
 
 pytestmark = pytest.mark.gpu
@@ -25,7 +24,6 @@ COUNTS = (1, 2, 255, 256, 257, 1023, 1024, 1025, 1279, 1280, 2047, 2048, 2049, 2
 BOX_H = 49                                     # a box of 64 x 49 holds the largest count; the cloud is column-major (x, then y)
 SMALL_H = 16                                   # <= 256 px in a box of 16 x 16: size class 0 (roi_small); in columns of 49: class 1
 INT_EXACT = ("MIN", "MAX", "RANGE", "MEAN", "INTEGRATED_INTENSITY")
-OCC8_LDS = 20480                               # bytes of LDS a workgroup may carve out with eight per CU (launch_lds_variant)
 
 
 def _roi(n, h, values):
@@ -68,47 +66,6 @@ def _case(kind, mask):
     return b, s, tables[mask]
 
 
-def _device_call(ctx, b, mask, s, stated, prime=True):
-    """One featurize_device_async over the batch in device memory -> (table, launch report).  On stated extrema a call of one
-    class-1 ROI goes first: it resets the context's census of the smallest class, which the calls before left in whatever state
-    and which decides between whole-batch launches and exact lists."""
-    import torch
-    if stated and prime:
-        if "prime" not in _cache:
-            _cache["prime"] = _abi.batch_from_rois([_roi(300, BOX_H, np.arange(1, 301))])
-        _device_call(ctx, _cache["prime"], mask, s, True, prime=False)
-    dev = torch.device("cuda", 0)
-    keep = {k: torch.from_numpy(getattr(b, k).view({2: np.int16, 4: np.int32, 8: np.int64}[getattr(b, k).dtype.itemsize])).to(dev)
-            for k in ("px_offset", "x", "y", "inten", "bbox_w", "bbox_h", "min_inten", "max_inten")}
-    cb = b.c_struct()
-    for k, t in keep.items():
-        setattr(cb, k, t.data_ptr())
-    cb.slide_min = None; cb.slide_max = None; cb.memory = _abi.MEM_DEVICE
-    if not stated:
-        cb.max_px = cb.max_bbox_area = cb.max_bbox_side = 0           # no statement: the classifier derives the classes
-    ncol = ctx.n_columns(mask, s)
-    out = torch.full((b.n_roi, ncol), -1.0, dtype=torch.float64, device=dev)
-    ctx.featurize_device_async(cb, mask, s, out.data_ptr(), ncol)
-    rep = ctx.launch_report()
-    ctx.sync()
-    return out.cpu().numpy(), rep
-
-
-_LAUNCH = re.compile(r"features launch: g16 (\d+) dense8 (\d+) cnt16 (\d+) ng_cap \d+ app \d+ total (\d+) mask (\d+)")
-
-
-def _check_tier(err, mask):
-    """The launch lines of a call: 16-bit tables and the 8-bit plane where there are any, and no carve-out beyond the eight-per-CU one --
-    the conditions under which launch_lds_variant picks roi_features_kernel_occ8<FAM, 0> for a cloud launch."""
-    lines = [tuple(int(g) for g in m.groups()) for m in _LAUNCH.finditer(err)]
-    assert lines, err[-2000:]
-    for g16, dense8, cnt16, total, lmask in lines:
-        assert lmask == mask and g16 == 0 and total <= OCC8_LDS, (lines, err[-2000:])
-        assert cnt16 == 1 or not (mask & _abi.FAM_INTENSITY), lines      # (GLCM alone has no counting table to size)
-        assert dense8 == 1 or not (mask & _abi.FAM_GLCM), lines
-    return max(l[3] for l in lines)
-
-
 def _check(G, O, names, b):
     bad = parity.compare_tables(G, O, names, batch=b)
     assert not bad, "\n".join(bad[:20])
@@ -133,8 +90,8 @@ def test_batch_holds_every_count_and_both_classes():
 def test_trip_boundaries_on_stated_extrema(hip_ctx, kind, mask, monkeypatch, capfd):
     b, s, O = _case(kind, mask)
     monkeypatch.setenv("NYXHIP_DEBUG", "1")
-    G, rep = _device_call(hip_ctx, b, mask, s, stated=True)
-    print("largest carve-out", _check_tier(capfd.readouterr().err, mask))
+    G, rep = dc.device_call(hip_ctx, b, mask, s, stated=True)
+    print("largest carve-out", dc.assert_compact_tier(capfd.readouterr().err, mask))
     assert all(r["class"] < 0 for r in rep), rep                      # whole-batch launches, nothing counted
     _check(G, O, _lib.column_names(mask, s), b)
 
@@ -144,7 +101,7 @@ def test_trip_boundaries_through_the_classifier(hip_ctx, kind, monkeypatch, capf
     mask = _abi.FAM_INTENSITY | _abi.FAM_GLCM
     b, s, O = _case(kind, mask)
     monkeypatch.setenv("NYXHIP_DEBUG", "1")
-    G, rep = _device_call(hip_ctx, b, mask, s, stated=False)
-    print("largest carve-out", _check_tier(capfd.readouterr().err, mask))
+    G, rep = dc.device_call(hip_ctx, b, mask, s, stated=False)
+    print("largest carve-out", dc.assert_compact_tier(capfd.readouterr().err, mask))
     assert all(r["class"] >= 0 for r in rep) and sum(r["rois"] for r in rep) == b.n_roi, rep
     _check(G, O, _lib.column_names(mask, s), b)

@@ -775,7 +775,7 @@ def test_gabor_fused_variant_matches_on_noisy_fields():
     assert np.array_equal(out["exact"], out["fused"])
 
 
-# ---- the reference's default grey depth (17..64 matlab levels): 16-bit matrices + marginal-based features (roi_features_kernel_g16) ----
+# ---- the reference's default grey depth (17..64 matlab levels): 16-bit matrices + marginal-based features (the TIER 9 builds of roi_features_kernel) ----
 @pytest.mark.parametrize("irregular", [False, True])
 @pytest.mark.parametrize("gd", [64, 33, 17])
 def test_benchmark_tile_default_grey_depth(hip_ctx, gd, irregular):
@@ -861,7 +861,7 @@ def test_contour_wide_boxes_take_the_position_wise_pass(hip_ctx):
 @pytest.mark.gpu
 def test_eight_wave_64_level_launch_gives_the_bits_of_the_four_wave_one():
     """Grey depths 17..64: classes whose largest box has >= 48 x 48 cells run the GLCM launch on eight waves per ROI with the feature pass on
-    two waves per angle (roi_features_kernel_g16w8); which launch a ROI meets depends on its companions' boxes, so both must give the same
+    two waves per angle (the NW 8 build of TIER 9); which launch a ROI meets depends on its companions' boxes, so both must give the same
     bits.  Two child processes (the A/B knob NYXHIP_G16_W4 is read once per process) over mixed batches, three depths, both symmetries."""
     import os, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

@@ -81,7 +81,7 @@ def test_sixteen_bit_tiles_through_the_tile_path(hip_ctx):
 
 
 def test_glcm_alone_through_the_tile_path_and_the_batch_path(hip_ctx):
-    """GLCM alone has a compile-time build of its own (roi_features_kernel_occ8<3, WIN>): the window loader (tile path) and the cloud
+    """GLCM alone has a compile-time build of its own (FAM 3 of roi_features_kernel's compact builds): the window loader (tile path) and the cloud
     loader (batch path) against the oracle, 8 and 16 levels, and a degenerate (constant) ROI among them."""
     from tests import synth
     rng = np.random.default_rng(41)

@@ -18,7 +18,7 @@ for d in sorted(glob.glob("$OUT/*/"), key=lambda p: (p.rstrip('/').split('/')[-1
     acc = defaultdict(list)
     for f in glob.glob(d + "**/*counter_collection.csv", recursive=True):
         for r in csv.DictReader(open(f)):
-            if 'roi_features_kernel_occ8' in r.get('Kernel_Name', ''):
+            if 'roi_features_kernel<false, true, true, true, 1, 8,' in r.get('Kernel_Name', ''):
                 acc[r['Counter_Name']].append(float(r['Counter_Value']))
     if not acc: continue
     avg = {c: sum(v) / len(v) for c, v in acc.items()}

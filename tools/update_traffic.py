@@ -13,7 +13,7 @@ cf, cw = re.search(r"CLOSE_FETCH_SIZE: n=\d+ mean=([0-9.e+]+)", txt), re.search(
 close_bytes = (float(cf.group(1)) + float(cw.group(1))) * 1024 if cf and cw else 0.0
 kern = re.search(r"launch group: roi_features_kernel ([0-9.]+) ms \+ glcm_features_kernel ([0-9.]+) ms", txt)
 kclose = re.search(r"\+ intensity_close_kernel ([0-9.]+) ms", txt)
-rec = {"round": tag, "kernel": "roi_features_kernel_occ8<1, 0>", "tiles": 1000, "gray_depth": 8,
+rec = {"round": tag, "kernel": "roi_features_kernel<false, true, true, true, 1, 8, false, 0, 4, true, 8>", "tiles": 1000, "gray_depth": 8,
        "FETCH_SIZE_KB": fetch, "WRITE_SIZE_KB": write,
        "correction": "gfx950: FETCH_SIZE counts 64 B per 128-B request on wide coalesced streams -> x2 (MI355X_MICROARCH.md, HBM); WRITE_SIZE exact; "
                      "intensity_close_kernel: FETCH_SIZE + WRITE_SIZE without the x2 (assumed: scattered 128-byte records, not measured)",
@@ -21,7 +21,7 @@ rec = {"round": tag, "kernel": "roi_features_kernel_occ8<1, 0>", "tiles": 1000, 
        "rocprof_kernel_ms": ([float(kern.group(1)), float(kern.group(2))] + ([float(kclose.group(1))] if kclose else [])) if kern else None,
        "rocprof_kernels": ["roi_features_kernel", "glcm_features_kernel"] + (["intensity_close_kernel"] if kclose else []),
        "kernel_source_sha256": hashlib.sha256(b"".join(open(os.path.join(ROOT, "nyxus_amd", "csrc", f_), "rb").read()
-                                                       for f_ in ("roi_features.hip", "glcm_rows.h", "device_math.h", "roi_kernel.h"))).hexdigest(),
+                                                       for f_ in ("roi_features.hip", "features_plan.h", "glcm_rows.h", "device_math.h", "roi_kernel.h"))).hexdigest(),
        "collected": f"rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE in separate passes (tools/profile_bench.sh {tag}), bench.py --steps 5 --warmup 2; "
                     f"metric-workload dispatches only (profiles/{tag}_summary.txt)"}
 # the tile path's traffic per tile from the same round's PMC pass over tools/tile_ab.py (tools/final_prof_r06.sh): all kernels of the call
