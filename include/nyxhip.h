@@ -418,6 +418,39 @@ int nyxhip_ih_tiles(nyxhip_ctx* ctx, const nyxhip_tiles* tiles, const nyxhip_set
 int nyxhip_featurize_slides(nyxhip_ctx* ctx, const nyxhip_tiles* slides, uint32_t family_mask,
                             const nyxhip_settings* s, double* out_table, size_t out_ld);
 
+/* ---- whole-slide mode: the rest of the *WHOLESLIDE* group ------------------------------
+ * The reference's feature group for this mode (env_features.cpp:219-234) names twelve classes.  Nine are family bits 0-9 above; the
+ * other three -- ContourFeature, the two moment classes and RadialDistributionFeature -- mean something else in this mode than behind
+ * nyxhip_featurize_batch, so they have an entry, a mask space and a table of their own, and the entries above keep refusing them.
+ * The ROI is the whole image at origin (0, 0), zero pixels included, in row-major order, and its contour is the four corners
+ * K = (0,0), (w-1,0), (w-1,h-1), (0,h-1), each with the slide's maximum as intensity (features/contour.cpp:917-933):
+ *   NYXHIP_WS_CONTOUR  ContourFeature::calculate over K: PERIMETER, DIAMETER_EQUAL_PERIMETER, EDGE_MEAN_INTENSITY, EDGE_STDDEV_INTENSITY,
+ *                      EDGE_MAX_INTENSITY, EDGE_MIN_INTENSITY, EDGE_INTEGRATED_INTENSITY (the reference's bits)
+ *   NYXHIP_WS_SMOMS / NYXHIP_WS_IMOMS  the 90 columns each of NYXHIP_FAM_SMOMS / NYXHIP_FAM_IMOMS.  The unweighted sets are those of the
+ *                      batch path.  In the weighted sets a pixel of the first / last row or column weighs epsilon = 0.001 whatever its
+ *                      intensity; every other pixel weighs I * log(d + epsilon), d = min(x, w-1-x, y, h-1-y) (the reference's
+ *                      dist_to_segment to the four sides, 2d_geomoments_basic.cpp:58-96), I = the intensity (IMOMS) or 1 (SMOMS).
+ *   NYXHIP_WS_RADIAL   the 24 columns of NYXHIP_FAM_RADIAL: find_center by the reference's hill descent over the FOUR points (its first
+ *                      step is 2: corners 0 and 2 decide whether 1 and 3 are looked at), the first pixel in row-major order wins ties;
+ *                      bins, wedges and tail as behind NYXHIP_FAM_RADIAL.  A 1 x 1 slide (max_sqdist == 0, undefined in the reference)
+ *                      has 24 zeros.  The block is ALWAYS computed against K: the reference's omission of the contour when no contour or
+ *                      moment code is requested (reduce_trivial_rois.cpp:446-457) is the caller's to mirror.
+ * Blocks stand in the order of the bits; names are those of nyxhip_morph_column_name(NYXHIP_MORPH_CONTOUR) and of nyxhip_column_name for
+ * the family bit alone.  The contract is nyxhip_imq_slides': label must be NULL, U8 / U16 / U32 in host or device memory (the images AND
+ * out_table), chunks under max_device_bytes through the staging ring, one row per slide in input order, n_tiles == 0 is NYXHIP_OK, a side
+ * of 0 or above 65534 is NYXHIP_ERR_UNSUPPORTED, a slide beyond the budget NYXHIP_ERR_ROI_TOO_LARGE, a zero mask or a bit above 8
+ * NYXHIP_ERR_INVALID_ARG (nyxhip_wsgroup_n_columns: -1).  NaN / inf are not replaced (nyxhip_finalize_table).  Synchronous.
+ * The image is read in place: once for the maximum (CONTOUR), once for the moments and the centre, once for the radial bins.  Sums are
+ * added in an order fixed by the slide's shape, so a row has the same bits whatever shares its call, its chunk or its place in the stack. */
+#define NYXHIP_WS_CONTOUR 1u   /*  7 */
+#define NYXHIP_WS_SMOMS   2u   /* 90 */
+#define NYXHIP_WS_IMOMS   4u   /* 90 */
+#define NYXHIP_WS_RADIAL  8u   /* 24 */
+int nyxhip_wsgroup_n_columns(uint32_t ws_mask);
+int nyxhip_wsgroup_column_name(uint32_t ws_mask, int col, char* buf, size_t buf_len);
+int nyxhip_wsgroup_slides(nyxhip_ctx* ctx, const nyxhip_tiles* slides, uint32_t ws_mask,
+                          const nyxhip_settings* s, double* out_table, size_t out_ld);
+
 /* ---- image quality: focus score and saturation ---------------------------------------
  * Four of the six codes of the reference's FeatureIMQ (featureset.h:920-931), the classes behind its ImageQuality Python class
  * (reduce_trivial_rois.cpp:388-412, :631-654): FocusScoreFeature (features/focus_score.cpp:188-282) and SaturationFeature

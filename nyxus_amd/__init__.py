@@ -9,6 +9,7 @@ from . import _abi  # noqa: F401
 from .nyxus import Nyxus  # noqa: F401
 from .nyxus_morph import NyxusMorphology  # noqa: F401
 from .nyxus_allmorph import NyxusAllMorphology  # noqa: F401
+from .nyxus_wholeslide import NyxusWholeSlide  # noqa: F401
 from .imq import ImageQuality  # noqa: F401
 from .nyxus3d import Nyxus3D, Nyxus3DZones, Nyxus3DDistanceZones, Nyxus3DShape  # noqa: F401
 

@@ -70,6 +70,12 @@ MORPH_BASIC, MORPH_CONTOUR, MORPH_HULL, MORPH_EXTREMA = 1 << 0, 1 << 1, 1 << 2, 
 MORPH_ALL = 0xF
 MORPH_COLS = {MORPH_BASIC: 15, MORPH_CONTOUR: 7, MORPH_HULL: 3, MORPH_EXTREMA: 16}
 
+# NYXHIP_WS_*: the mask space of nyxhip_wsgroup_slides, the classes of the *WHOLESLIDE* group that nyxhip_featurize_slides refuses
+WS_CONTOUR, WS_SMOMS, WS_IMOMS, WS_RADIAL = 1 << 0, 1 << 1, 1 << 2, 1 << 3
+WS_ALL = 0xF
+WS_COLS = {WS_CONTOUR: 7, WS_SMOMS: 90, WS_IMOMS: 90, WS_RADIAL: 24}
+WS_BAND_PIXELS = 16384      # wsgroup_plan.h: a band of the sweep is the most whole rows with at most this many pixels (at least one row)
+
 
 class Settings(C.Structure):
     """``nyxhip_settings`` (include/nyxhip.h)."""

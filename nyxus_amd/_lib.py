@@ -32,6 +32,7 @@ ABI_SYMBOLS = [
     "nyxhip_ih_column_name", "nyxhip_ih_batch", "nyxhip_ih_tiles",
     "nyxhip_featurize_slides",
     "nyxhip_imq_column_name", "nyxhip_imq_batch", "nyxhip_imq_tiles", "nyxhip_imq_slides",
+    "nyxhip_wsgroup_n_columns", "nyxhip_wsgroup_column_name", "nyxhip_wsgroup_slides",
     "nyxhip_vol_n_columns", "nyxhip_vol_column_name", "nyxhip_featurize_volumes",
     "nyxhip_voltex_n_columns", "nyxhip_voltex_column_name", "nyxhip_featurize_volumes_tex",
     "nyxhip_volzone_n_columns", "nyxhip_volzone_column_name", "nyxhip_featurize_volumes_zones",
@@ -149,6 +150,13 @@ def load() -> C.CDLL:
         lib.nyxhip_imq_tiles.restype = C.c_int
         lib.nyxhip_imq_slides.argtypes = [C.c_void_p, P(_abi.Tiles), P(_abi.Settings), C.c_void_p, C.c_size_t]
         lib.nyxhip_imq_slides.restype = C.c_int
+    if hasattr(lib, "nyxhip_wsgroup_slides"):
+        lib.nyxhip_wsgroup_n_columns.argtypes = [C.c_uint32]
+        lib.nyxhip_wsgroup_n_columns.restype = C.c_int
+        lib.nyxhip_wsgroup_column_name.argtypes = [C.c_uint32, C.c_int, C.c_char_p, C.c_size_t]
+        lib.nyxhip_wsgroup_column_name.restype = C.c_int
+        lib.nyxhip_wsgroup_slides.argtypes = [C.c_void_p, P(_abi.Tiles), C.c_uint32, P(_abi.Settings), C.c_void_p, C.c_size_t]
+        lib.nyxhip_wsgroup_slides.restype = C.c_int
     if hasattr(lib, "nyxhip_featurize_volumes"):  # (absent from older builds of the ABI selected through NYXHIP_LIB for A/B runs)
         lib.nyxhip_vol_n_columns.argtypes = [C.c_uint32, P(_abi.Settings)]
         lib.nyxhip_vol_n_columns.restype = C.c_int
@@ -259,6 +267,11 @@ def ih_column_names() -> List[str]:
 def imq_column_names() -> List[str]:
     """The 4 columns of nyxhip_imq_batch / _tiles / _slides, enum order."""
     return _catalogue(_abi.IMQ_COLS, load().nyxhip_imq_column_name, (), "image-quality column")
+
+
+def wsgroup_column_names(ws_mask: int) -> List[str]:
+    """The columns of nyxhip_wsgroup_slides for a whole-slide group mask (_abi.WS_*): blocks in the order of the bits."""
+    return _catalogue(load().nyxhip_wsgroup_n_columns, load().nyxhip_wsgroup_column_name, (ws_mask,), "whole-slide group column", "whole-slide group mask")
 
 
 def vol_column_names(vmask: int, s: _abi.Settings) -> List[str]:
@@ -609,6 +622,34 @@ class Context:
         t.inten_dtype = dtype; t.width = w; t.height = h; t.n_tiles = n; t.memory = _abi.MEM_DEVICE
         t.max_device_bytes = int(max_device_bytes)
         self._check(self._lib.nyxhip_imq_slides(self._h, C.byref(t), C.byref(s), C.c_void_p(out_ptr), ld))
+
+    def wsgroup_slides_host(self, inten: np.ndarray, ws_mask: int, s: _abi.Settings, max_device_bytes: int = 0) -> np.ndarray:
+        """Whole-slide mode of the contour, moment and radial classes (nyxhip_wsgroup_slides): a stack [n, H, W] of uint8 / uint16 /
+        uint32 host slides, every slide one ROI whose contour is its four corners.  Returns the table [n, nyxhip_wsgroup_n_columns],
+        rows in input order; NaN / inf are left in place."""
+        dt = {np.dtype(np.uint8): _abi.U8, np.dtype(np.uint16): _abi.U16, np.dtype(np.uint32): _abi.U32}
+        if inten.ndim != 3 or inten.dtype not in dt:
+            raise ValueError("slides must be a 3-D array [n, H, W] of uint8, uint16 or uint32")
+        inten = np.ascontiguousarray(inten)
+        n, h, w = inten.shape
+        ncol = self._lib.nyxhip_wsgroup_n_columns(ws_mask)
+        out = np.empty((n, max(ncol, 0)), np.float64)
+        t = _abi.Tiles()
+        t.inten = inten.ctypes.data; t.label = None
+        t.inten_dtype = dt[inten.dtype]; t.width = w; t.height = h; t.n_tiles = n; t.memory = _abi.MEM_HOST
+        t.max_device_bytes = int(max_device_bytes)
+        self._check(self._lib.nyxhip_wsgroup_slides(self._h, C.byref(t), ws_mask, C.byref(s), out.ctypes.data, max(ncol, 1)))
+        return out
+
+    def wsgroup_slides_device(self, inten_ptr: int, dtype: int, n: int, h: int, w: int, ws_mask: int, s: _abi.Settings, out_ptr: int, ld: int,
+                              max_device_bytes: int = 0):
+        """The same entry on device memory: `inten_ptr` is a device array [n, h, w] of element type `dtype` (_abi.U8 / U16 / U32),
+        `out_ptr` a device table [n x ld] of doubles.  Synchronous."""
+        t = _abi.Tiles()
+        t.inten = inten_ptr; t.label = None
+        t.inten_dtype = dtype; t.width = w; t.height = h; t.n_tiles = n; t.memory = _abi.MEM_DEVICE
+        t.max_device_bytes = int(max_device_bytes)
+        self._check(self._lib.nyxhip_wsgroup_slides(self._h, C.byref(t), ws_mask, C.byref(s), C.c_void_p(out_ptr), ld))
 
     def featurize_device_async(self, cb: _abi.Batch, mask: int, s: _abi.Settings, out_ptr: int, ld: int, origin_x_ptr: Optional[int] = None,
                                origin_y_ptr: Optional[int] = None):

@@ -2,6 +2,7 @@
 // erosion) and the contour chain with its readers (moments, radial, outline, circle).  Each kernel carves its LDS for a cap; the ROIs
 // beyond it go through a deferred list (deferred_list.h).
 #include "nyxhip_ctx.h"
+#include "radial_close.h"
 #include "deferred_list.h"
 
 using namespace nyxhip;
@@ -265,17 +266,7 @@ int nyxhip::launch_contour_families(nyxhip_ctx* ctx, const nyxhip_batch* b, uint
         ra.col_frac = nyxhip_n_columns(mask & before, s);
         ra.col_mean = ra.col_frac + kRadialBins + ((mask & NYXHIP_FAM_GABOR) ? s->gabor_n_filters : 0);
         ra.col_cv = ra.col_mean + kRadialBins;
-        // the wedge of the eight directions that lie ON an octant boundary: the reference expression (radial_distribution.cpp:92-96)
-        // on the host's libm, as the reference evaluates it; every other direction is an exact integer test in the kernel
-        static const int kDirX[8] = {1, 1, 0, -1, -1, -1, 0, 1}, kDirY[8] = {0, 1, 1, 1, 0, -1, -1, -1};
-        const double two_pi = 2.0 * 3.14159265358979323846;
-        for (int k = 0; k < 8; k++) {
-            double ang = std::atan2((double)kDirY[k], (double)kDirX[k]);
-            if (ang < 0) ang = two_pi + ang;
-            const double angW = two_pi / double(kRadialBins);
-            const int w_bin = std::min(std::max(int(ang / angW), 0), kRadialBins - 1);
-            ra.wedge_tab |= (uint32_t)w_bin << (4 * k);
-        }
+        ra.wedge_tab = radial_wedge_tab();                 // the eight boundary directions on the host's libm (radial_close.h)
     }
     // the readers of a contour launch, on its stream: the moments of `mm` and / or the radial distribution over the same ROIs
     auto launch_readers = [&](const MomArgs& mm, hipStream_t s_, uint32_t g) -> int {

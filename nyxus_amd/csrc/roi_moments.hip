@@ -22,6 +22,7 @@
 #include "knobs.h"
 #include "deferred_list.h"
 #include "contour_descent.h"
+#include "moments_close.h"
 #include "../../include/nyxhip.h"
 
 namespace nyxhip {
@@ -347,24 +348,9 @@ __device__ __forceinline__ double min_sqdist_packed(int px, int py, const uint32
     return (double)(key >> 15);
 }
 
-__device__ __forceinline__ double ipow(double a, int b) { double r = 1.0; for (int i = 0; i < b; i++) r *= a; return r; }
-
-__device__ void hu7(double _02, double _03, double _11, double _12, double _20, double _21, double _30, double* h)
-{   // calcHu_imp, 2d_geomoments_basic.cpp:231-253
-    h[0] = _20 + _02;
-    h[1] = ipow((_20 - _02), 2) + 4 * (ipow(_11, 2));
-    h[2] = ipow((_30 - 3 * _12), 2) + ipow((3 * _21 - _03), 2);
-    h[3] = ipow((_30 + _12), 2) + ipow((_21 + _03), 2);
-    h[4] = (_30 - 3 * _12) * (_30 + _12) * (ipow(_30 + _12, 2) - 3 * ipow(_21 + _03, 2)) +
-           (3 * _21 - _03) * (_21 + _03) * (3 * ipow(_30 + _12, 2) - ipow(_21 + _03, 2));
-    h[5] = (_20 - _02) * (ipow(_30 + _12, 2) - ipow(_21 + _03, 2)) + 4 * _11 * (_30 + _12) * (_21 + _03);
-    h[6] = (3 * _21 - _03) * (_30 + _12) * (ipow(_30 + _12, 2) - 3 * ipow(_21 + _03, 2)) -
-           (_30 - 3 * _12) * (_21 + _03) * (3 * ipow(_30 + _12, 2) - ipow(_21 + _03, 2));
-}
-
 } // namespace
 
-// Column layout of one 90-wide block (Feature2D order): RM(13) CM(16) NRM(16) NCM(7) HU(7) WRM(10) WCM(7) WNCM(7) WHU(7)
+// Column layout of one 90-wide block and the closing math: moments_close.h
 // diagnostic builds (-DNYX_MOM_EXIT_AT=k): the kernel ends after pass k (results are wrong by design)
 #ifdef NYX_MOM_EXIT_AT
 #define MSTAMP(k) do { if ((k) == NYX_MOM_EXIT_AT) return; } while (0)
@@ -511,16 +497,8 @@ __global__ __launch_bounds__(kMB, OCC) void roi_moments_kernel(const MomArgs A)
         mom_block_sum<16, false>(acc, s_red, s_mo[var], TID());
     }
     __syncthreads();
-    // m[p][q] about the origin o - e from the sums about o (binomial coefficients of orders 0..3)
-    // (no local arrays: an array indexed at run time lives in scratch memory)
-    auto shifted = [](const double* mo, int p, int q, double ex, double ey) -> double {
-        auto binom = [](int n, int k) -> double { return (n == 3 && (k == 1 || k == 2)) ? 3.0 : (n == 2 && k == 1) ? 2.0 : 1.0; };
-        auto pw = [](double e, int n) -> double { const double e2 = e * e; return n == 0 ? 1.0 : n == 1 ? e : n == 2 ? e2 : e2 * e; };
-        double r = 0.0;
-        for (int k = 0; k <= p; k++)
-            for (int l = 0; l <= q; l++) r += binom(p, k) * binom(q, l) * pw(ex, p - k) * pw(ey, q - l) * mo[k * 4 + l];
-        return r;
-    };
+    // m[p][q] about the origin o - e from the sums about o: mom_shifted (moments_close.h)
+    auto shifted = [](const double* mo, int p, int q, double ex, double ey) -> double { return mom_shifted(mo, p, q, ex, ey); };
     if (TID() < 32) {                                       // raw moments: origin 0, e = o
         const int var = TID() >> 4, pq = TID() & 15;
         s_raw[var][pq] = shifted(s_mo[var], pq >> 2, pq & 3, obx, oby);
@@ -534,7 +512,8 @@ __global__ __launch_bounds__(kMB, OCC) void roi_moments_kernel(const MomArgs A)
     __syncthreads();
     MSTAMP(1);
     MSTAMP(2);
-    // (p, q) of the 10 weighted raw moments and of the 7 (weighted / normalized) central ones
+    // (p, q) of the 10 weighted raw moments and of the 7 (weighted / normalized) central ones: MomPQ of moments_close.h, kept as
+    // function-local tables here (read through the struct's members this kernel spills 179 scalar registers)
     static constexpr int wr_p[10] = {0, 0, 0, 0, 1, 1, 1, 2, 2, 3}, wr_q[10] = {0, 1, 2, 3, 0, 1, 2, 0, 1, 0};
     static constexpr int nc_p[7] = {0, 0, 1, 1, 2, 2, 3}, nc_q[7] = {2, 3, 1, 2, 0, 1, 0};
     const bool packed = compact && K == s_K && nK >= 1 && nK <= 32766 && (bw_ + 2u) * (bw_ + 2u) + (bh_ + 2u) * (bh_ + 2u) < (1u << 17);   // (min_sqdist_packed)
@@ -615,43 +594,7 @@ __global__ __launch_bounds__(kMB, OCC) void roi_moments_kernel(const MomArgs A)
     if (TID() < 2 && (TID() ? do_i : do_s)) {
         const int var = TID();
         double* o = row_out + (var ? A.col_imoms : A.col_smoms);
-        const double* raw = s_raw[var];
-        const double* cen = s_cen[var];
-        const double m00 = raw[0], w00 = s_wraw[var][0];
-        // x / pow(m, (p + q) / 2 + 1) for p + q = 0..6: the seven powers are m^(1 + j/2) = m^(1 + j div 2) * sqrt(m)^(j mod 2) -- one
-        // square root, a few products and seven divisions per normalising mass, where thirty pow() calls (a couple of hundred
-        // instructions each, on two lanes of one wave) were a tenth of the kernel.  Tolerance-class values; 1-2 ulp from pow().
-        double rm[7], rw[7];
-        {
-            const double sm = sqrt(m00), sw = sqrt(w00);
-            double pm = m00, pw = w00;
-#pragma unroll
-            for (int j = 0; j < 7; j += 2) {
-                rm[j] = 1.0 / pm; rw[j] = 1.0 / pw;
-                if (j + 1 < 7) { rm[j + 1] = 1.0 / (pm * sm); rw[j + 1] = 1.0 / (pw * sw); }
-                pm *= m00; pw *= w00;
-            }
-        }
-        for (int k = 0; k < 13; k++) o[k] = raw[k];                                       // RM 00..23, 30
-        for (int k = 0; k < 16; k++) o[13 + k] = cen[k];                                          // CM
-#pragma unroll
-        for (int k = 0; k < 16; k++)                                                               // NRM :204-209
-            o[29 + k] = raw[k] * rm[(k >> 2) + (k & 3)];
-        double nu[7], wn[7];
-#pragma unroll
-        for (int k = 0; k < 7; k++) {                                                              // NCM :212-217
-            nu[k] = cen[nc_p[k] * 4 + nc_q[k]] * rm[nc_p[k] + nc_q[k]];
-            o[45 + k] = nu[k];
-        }
-        hu7(nu[0], nu[1], nu[2], nu[3], nu[4], nu[5], nu[6], o + 52);
-        for (int k = 0; k < 10; k++) o[59 + k] = s_wraw[var][k];                                   // WRM
-        for (int k = 0; k < 7; k++) o[69 + k] = s_wcen[var][k];                                    // WCM
-#pragma unroll
-        for (int k = 0; k < 7; k++) {                                                              // WNCM :220-225
-            wn[k] = s_wcen[var][k] * rw[nc_p[k] + nc_q[k]];
-            o[76 + k] = wn[k];
-        }
-        hu7(wn[0], wn[1], wn[2], wn[3], wn[4], wn[5], wn[6], o + 83);
+        mom_write_block(o, s_raw[var], s_cen[var], s_wraw[var], s_wcen[var]);
     }
 }
 

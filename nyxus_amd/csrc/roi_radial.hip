@@ -17,6 +17,7 @@
 #include <hip/hip_runtime.h>
 #include "device_math.h"
 #include "roi_radial.h"
+#include "radial_close.h"
 #include "launch_util.h"
 #include "contour_descent.h"
 #include "../../include/nyxhip.h"
@@ -27,23 +28,6 @@ namespace {
 
 constexpr int kRB = 256;
 constexpr int kRW = kRB / 64;                 // waves: one replica of the bin tables each (LDS atomics of a wave meet only their own)
-
-// int(ang / (2 pi / 8)), ang = atan2(dy, dx) [+ 2 pi if negative] (radial_distribution.cpp:90-96) for integer dx, dy.
-// Octant k covers [k, k + 1) * 45 degrees.  A direction off the eight boundary directions is at least 1e-10 rad away from one
-// (|dx|, |dy| < 2^16), eleven orders above the rounding of atan2 and of the division: its bin is the octant it lies in.
-__device__ __forceinline__ int wedge_of(int dx, int dy, uint32_t tab)
-{
-    const int ax = dx < 0 ? -dx : dx, ay = dy < 0 ? -dy : dy;
-    if ((ax | ay) == 0) return 0;                                        // atan2(0, 0) = 0
-    if (ay == 0) return (int)((tab >> (dx > 0 ? 0 : 16)) & 15u);         // 0, 180 degrees
-    if (ax == 0) return (int)((tab >> (dy > 0 ? 8 : 24)) & 15u);         // 90, 270
-    if (ax == ay) {
-        const int k = dy > 0 ? (dx > 0 ? 1 : 3) : (dx < 0 ? 5 : 7);      // 45, 135, 225, 315
-        return (int)((tab >> (4 * k)) & 15u);
-    }
-    if (dy > 0) return dx > 0 ? (ax > ay ? 0 : 1) : (ax < ay ? 2 : 3);
-    return dx < 0 ? (ax > ay ? 4 : 5) : (ax < ay ? 6 : 7);
-}
 
 } // namespace
 
@@ -151,11 +135,7 @@ __global__ __launch_bounds__(kRB) void roi_radial_kernel(const RadArgs R)
     // ---- pass B: rings and wedges (:74-99) ------------------------------------------------------------------------------
     sweep([&](uint32_t, uint32_t vi, uint32_t xi, uint32_t yi) {
         const int dx = (int)xi - cx, dy = (int)yi - cy;
-        const double ddx = (double)dx, ddy = (double)dy;
-        const double dstOA = sqrt(ddx * ddx + ddy * ddy);                 // exact integer below 2^53 under the root
-        const double rat = dstOA / dstOC;
-        int ring = (int)(rat * (double)(kRadialBins - 1));                // 0 <= rat < 2^17: the conversion is defined
-        if (ring >= kRadialBins) ring = kRadialBins - 1;
+        const int ring = ring_of(dx, dy, dstOC);
         const int wdg = wedge_of(dx, dy, R.wedge_tab);
         atomicAdd(&s_cnt[wave][ring], 1u);
         atomicAdd(&s_wedge[wave][ring * kRadialBins + wdg], (unsigned long long)vi);
@@ -163,9 +143,8 @@ __global__ __launch_bounds__(kRB) void roi_radial_kernel(const RadArgs R)
     __syncthreads();
     // ---- tail: get_FracAtD, get_MeanFrac, get_RadialCV (:212-247), one lane per ring ----------------------------------------
     if (tid < kRadialBins) {
-        const double epsilon = 0.000000001;                               // radial_distribution.h:71
         uint32_t cnt = 0;
-        unsigned long long wsum[kRadialBins], isum = 0;
+        unsigned long long wsum[kRadialBins];
 #pragma unroll
         for (int k = 0; k < kRadialBins; k++) wsum[k] = 0;
 #pragma unroll
@@ -174,19 +153,11 @@ __global__ __launch_bounds__(kRB) void roi_radial_kernel(const RadArgs R)
 #pragma unroll
             for (int k = 0; k < kRadialBins; k++) wsum[k] += s_wedge[w][tid * kRadialBins + k];
         }
-#pragma unroll
-        for (int k = 0; k < kRadialBins; k++) isum += wsum[k];            // radial_intensity_bins[ring]: the same pixels, summed exactly
-        row_out[R.col_frac + tid] = (double)cnt / ((double)n + epsilon);
-        row_out[R.col_mean + tid] = (double)isum / ((double)cnt + epsilon);
-        double sum = 0.0;
-#pragma unroll
-        for (int k = 0; k < kRadialBins; k++) sum += (double)wsum[k];
-        const double mean = sum / (double)kRadialBins;
-        sum = 0;
-#pragma unroll
-        for (int k = 0; k < kRadialBins; k++) sum += ((double)wsum[k] - mean) * ((double)wsum[k] - mean);
-        const double var = sum / (double)kRadialBins;
-        row_out[R.col_cv + tid] = sqrt(var) / (mean + epsilon);
+        double frac, mean_frac, cv;
+        radial_tail((double)cnt, wsum, (double)n, frac, mean_frac, cv);
+        row_out[R.col_frac + tid] = frac;
+        row_out[R.col_mean + tid] = mean_frac;
+        row_out[R.col_cv + tid] = cv;
     }
 }
 
